@@ -4,11 +4,16 @@ Hot path = SeqRush::new UF state -> (orientation ->) all-vs-all biWFA alignment 
 union-find unite (-> label merge across GPUs).  One step = one pass of that path over the whole pair list with the
 packed sequences already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--full] [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 Rank 0 prints ONE JSON line.  The pair list is sharded over ranks (cost-balanced; strong scaling: the list is
 fixed); per-rank forests are merged with one RCCL all-gather of canonical u32 labels + replay-unite.
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, ms_per_step, dtype, gcups,
+config).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs()).  --full adds everything
+below: the roofline and per-kernel times (K more untimed steps), the device counters (`kernels`), clock / power
+telemetry, the host stages, the CPU baseline and h2h (each of the last three can be left out with its --no-* option).
 
 roofline (dominant kernel = the alignment kernel), all per launch, everything measured in THIS run unless it sits under
 `recorded`:
@@ -252,6 +257,29 @@ def host_to_host(ss, prm, dev, config):
     return res
 
 
+DUMP_CAP = 1 << 20          # elements per dumped array; above it a seeded sample (float64: <= 48 MB in all)
+
+
+def dump_outputs(ctx, d):
+    """--dump-outputs: what a caller of the timed path receives after the last timed step, as float64 .npy files (exact:
+    every value is an integer below 2^53) -- the canonical union-find labels (minimum node of each set; the raw node array
+    depends on the order of the concurrent unites) and this rank's per-pair score, strand flag and CIGAR op count.  A group
+    longer than DUMP_CAP is written at DUMP_CAP fixed, seeded indices, saved beside it as <group>_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    score, rev, ops = ctx.pair_results()
+    groups = {"labels": {"labels": ctx.download_labels()},
+              "pairs": {"pair_score": score, "pair_is_reverse": rev, "pair_cigar_ops": ops}}
+    for group, arrays in groups.items():
+        n = len(next(iter(arrays.values())))
+        idx = None
+        if n > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(2001).choice(n, DUMP_CAP, replace=False))
+            np.save(os.path.join(d, f"{group}_index.npy"), idx.astype(np.float64))
+        for name, a in arrays.items():
+            np.save(os.path.join(d, f"{name}.npy"), (a if idx is None else a[idx]).astype(np.float64))
+
+
 def build_config(name, nseq, fasta=None):
     from seqrush_amd import synth
     if name == "C2":
@@ -295,9 +323,14 @@ def main():
     ap.add_argument("--config", default="C2", choices=["C2", "C3", "C4", "C5"])
     ap.add_argument("--nseq", type=int, default=None, help="C2 / C5: number of sequences (default 64 / 256)")
     ap.add_argument("--fasta", default=None, help="C3 only: the real HLA-zoo DRB1 FASTA (also SR_C3_FASTA); default: the surrogate")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-h2h", action="store_true", help="skip the host-to-host (pack + upload + step + download) measurement")
-    ap.add_argument("--no-host-stages", action="store_true", help="skip the FASTA / induction / compaction / GFA-write timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times and the roofline (K more untimed "
+                         "steps), device counters, clock / power telemetry, host stages, the CPU baseline and h2h")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (canonical labels, per-pair results) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-h2h", action="store_true", help="--full: skip the host-to-host (pack + upload + step + download) measurement")
+    ap.add_argument("--no-host-stages", action="store_true", help="--full: skip the FASTA / induction / compaction / GFA-write timings")
     args = ap.parse_args()
     if args.nseq is None:
         args.nseq = 256 if args.config == "C5" else 64
@@ -305,6 +338,8 @@ def main():
         args.steps = 1 if args.config == "C5" else 5
     if args.warmup is None:
         args.warmup = 0 if args.config == "C5" else 1
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` started plainly: one process per GPU under torch.distributed.run, started as a
@@ -395,7 +430,7 @@ def main():
     fence()
     ctx.sync()
     tel = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             pr = torch.cuda.get_device_properties(dev)
             pci = "%04x:%02x:%02x.0" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id)
@@ -411,22 +446,25 @@ def main():
     dt = time.perf_counter() - t0
     telemetry = tel.stop() if tel else None
     ctx.sync()                              # raises on device fault bits
-    # per-kernel durations (hipEvents on the context's stream): for the long configs the timed steps' own events
-    # are read; otherwise K more untimed steps with event reads keep the timed region free of host syncs
-    align_ms, unite_ms, orient_ms = [], [], []
-    reread = args.config != "C5"
-    for _ in range(args.steps if reread else 1):
-        if reread:
-            step()
-            torch.cuda.synchronize()
-        align_ms.append(ctx.kernel_ms(0))
-        unite_ms.append(ctx.kernel_ms(1))
-        try:
-            orient_ms.append(ctx.kernel_ms(4))          # orientation runs as its own kernel (sr_orient_kernel)
-        except Exception:
-            pass
-    cnt = ctx.counters()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
     rep = ctx.workspace_report()
+    if args.full:
+        # per-kernel durations (hipEvents on the context's stream): for the long configs the timed steps' own events
+        # are read; otherwise K more untimed steps with event reads keep the timed region free of host syncs
+        align_ms, unite_ms, orient_ms = [], [], []
+        reread = args.config != "C5"
+        for _ in range(args.steps if reread else 1):
+            if reread:
+                step()
+                torch.cuda.synchronize()
+            align_ms.append(ctx.kernel_ms(0))
+            unite_ms.append(ctx.kernel_ms(1))
+            try:
+                orient_ms.append(ctx.kernel_ms(4))          # orientation runs as its own kernel (sr_orient_kernel)
+            except Exception:
+                pass
+        cnt = ctx.counters()
     labels_sha = None
     if os.environ.get("SR_BENCH_LABEL_SHA") == "1":
         import hashlib
@@ -438,6 +476,20 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     out = None
     if rank == 0:
+        out = {
+            "metric": metric, "value": total_pairs * args.steps / dt, "unit": "pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "i16" if rep.get("offset_bytes") == 2 else "i32", "data": "synthetic",
+            "gcups": total_cells * args.steps / dt / 1e9,
+            "config": {"workload": workload + ", -k 0 -S 0,5,8,2,24,1 --orientation-scores 0,1,1,1, biWFA (Ultralow)",
+                       "pairs_total": total_pairs, "pairs_per_gpu": ctx.num_pairs,
+                       "parallelism": f"pair-shard x{world} (cost-balanced), u32 label all-gather" if world > 1 else "pair-shard x1",
+                       "workspace": rep},
+        }
+        if labels_sha:
+            out["labels_sha256"] = labels_sha
+    if rank == 0 and args.full:
         a_ms = sum(align_ms) / len(align_ms)
         u_ms = sum(unite_ms) / len(unite_ms)
         o_ms = sum(orient_ms) / len(orient_ms) if orient_ms else None
@@ -551,21 +603,8 @@ def main():
             basis["note"] = ("no resource within a quarter of what it can attain (closest: %s at %.2f%s): latency of dependent steps"
                              % (top, closeness[top], "" if rec else "; no PMC pass recorded for this workload, device-counted rows only"))
         roof["bound_basis"] = basis
-        out = {
-            "metric": metric, "value": total_pairs * args.steps / dt, "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "i16" if rep.get("offset_bytes") == 2 else "i32", "data": "synthetic",
-            "gcups": total_cells * args.steps / dt / 1e9,
-            "config": {"workload": workload + ", -k 0 -S 0,5,8,2,24,1 --orientation-scores 0,1,1,1, biWFA (Ultralow)",
-                       "pairs_total": total_pairs, "pairs_per_gpu": ctx.num_pairs,
-                       "parallelism": f"pair-shard x{world} (cost-balanced), u32 label all-gather" if world > 1 else "pair-shard x1",
-                       "workspace": rep},
-            "roofline": roof,
-            "kernels": cnt,
-        }
-        if labels_sha:
-            out["labels_sha256"] = labels_sha
+        out["roofline"] = roof
+        out["kernels"] = cnt
         if telemetry:
             out["telemetry"] = telemetry
         if world == 1 and not args.no_host_stages:
@@ -574,7 +613,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(recs, my_pairs, workload.split(":")[0])
             out["speedup_vs_cpu_best_leg"] = out["value"] / out["cpu_baseline"]["value"]
     ctx.close()
-    if out is not None and world == 1 and not args.no_h2h:
+    if out is not None and args.full and world == 1 and not args.no_h2h:
         out["h2h"] = host_to_host(ss, prm, dev, args.config)
         out["h2h_ms"] = out["h2h"]["total_ms"]
     if world > 1:

@@ -2,7 +2,7 @@
 # usage: bench_sweep.sh "ENV1=.. ENV2=.." "ENV.." ...   -> one short bench line per configuration
 for cfg in "$@"; do
   echo "== $cfg"
-  env $cfg timeout -k 10 200 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+  env $cfg timeout -k 10 200 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernels']

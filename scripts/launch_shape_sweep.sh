@@ -1,7 +1,8 @@
 #!/bin/bash
 # launch-shape sweep on C4 (2 kb pairs) and C3 (33 kb pairs): which workgroup shape the host should pick per workload
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 cd $GRAFT_REPO_ROOT
 show() { python - "$1" "$2" <<'PY'
 import json,sys
@@ -10,7 +11,7 @@ r=d["roofline"]; w=d["config"]["workspace"]
 print(sys.argv[1], "| ms/step", round(d["ms_per_step"],2), "align", round(r["kernel_ms"],2), "wg", w["workgroups"], "thr", w["threads_per_workgroup"], "blk", w["block_levels"], "wsGB", round(w["workspace_bytes"]/1e9,1), flush=True)
 PY
 }
-run() { cfg=$1; name=$2; shift; shift; env "$@" timeout -k 10 200 python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-host-stages > gpurun_out/v.json 2> gpurun_out/v.err && show "$cfg $name" gpurun_out/v.json || { echo "$cfg $name FAILED"; tail -3 gpurun_out/v.err; }; }
+run() { cfg=$1; name=$2; shift; shift; env "$@" timeout -k 10 200 python bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-host-stages > $OUT/v.json 2> $OUT/v.err && show "$cfg $name" $OUT/v.json || { echo "$cfg $name FAILED"; tail -3 $OUT/v.err; }; }
 run C4 "default" SR_X=1
 run C4 "128 threads x8/CU" SR_ALIGN_THREADS=128
 run C4 "64 threads x16/CU" SR_ALIGN_THREADS=64

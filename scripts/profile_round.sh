@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.."
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-h2h --no-host-stages $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-h2h --no-host-stages $*"
 python3 bench.py $ARGS > "$OUT/bench_plain.json"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/bench_under_stats.json" 2> "$OUT/stats.log"

@@ -776,13 +776,13 @@ def test_multi_rank_bench_matches_single_rank(gpu, world, nseq):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SR_BENCH_LABEL_SHA="1")
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "C2", "--nseq", str(nseq), "--steps", "1", "--warmup", "0",
-                          "--no-cpu-baseline", "--no-h2h", "--no-host-stages"], capture_output=True, text=True, timeout=600, env=env)
+                          "--full", "--no-cpu-baseline", "--no-h2h", "--no-host-stages"], capture_output=True, text=True, timeout=600, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads(one.stdout.strip().split("\n")[-1])
     env["SR_BENCH_SINGLE_DEVICE"] = "1"
     # started plainly, the way the driver starts `--gpus 1`: bench.py launches its own ranks as a child process
     two = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--config", "C2", "--nseq", str(nseq), "--steps", "1",
-                          "--warmup", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
+                          "--warmup", "0", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
     assert two.returncode == 0, two.stderr[-2000:]
     d2 = json.loads(two.stdout.strip().split("\n")[-1])
     assert d2["n_gpus"] == world and d2["config"]["pairs_total"] == nseq * nseq
@@ -824,7 +824,7 @@ def test_deep_levels_reset_creeping_nulls(gpu):
 
 
 def test_bounds_checked_build_when_present(gpu, monkeypatch):
-    """the -DSR_BOUNDS instance of the blocked kernel (scripts/build_variant.sh bounds "-DSR_BOUNDS=1"), when it was built:
+    """the -DSR_BOUNDS instance of the blocked kernel (libseqrush_amd_bounds.so, which build() makes with the library):
     every row access tested against the workgroup's extent, every LDS window of a live cell against the staged sequences --
     a C2 subset, a family with indels and reverse complements and several pairs per workgroup run clean (no
     SR_DEV_ERR_ADDRESS) and equal the oracle.  A subprocess, because the library is chosen at load time."""
@@ -832,8 +832,7 @@ def test_bounds_checked_build_when_present(gpu, monkeypatch):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = os.path.join(root, "seqrush_amd", "libseqrush_amd_bounds.so")
-    if not os.path.exists(lib):
-        pytest.skip("libseqrush_amd_bounds.so not built (scripts/build_variant.sh bounds \"-DSR_BOUNDS=1\")")
+    assert os.path.exists(lib), "build() did not make libseqrush_amd_bounds.so"
     code = ("import sys; sys.path.insert(0, 'tests'); import test_gpu_parity as t; from seqrush_amd import synth\n"
             "from seqrush_amd.seqrush import SeqSet, Params, Context\n"
             "ss = SeqSet(synth.config_c2(8)); c = Context(0); c.load(ss, Params()); assert c.workspace_report()['kernel_build'] == 'bounds'; c.close()\n"
