@@ -276,6 +276,50 @@ int sr_build_gfa_opts(const sr_seqset *seqs, const uint64_t *labels, int compact
 int sr_build_gfa_from_nodes(const sr_seqset *seqs, const uint64_t *nodes, int compact, char **gfa,
                             uint64_t *n_nodes, uint64_t *n_edges);
 int sr_ctx_build_gfa_opts(sr_ctx *c, const sr_seqset *seqs, int compact, char **gfa, uint64_t *n_nodes, uint64_t *n_edges);
+
+/* -------- Ygs layout (`seqrush` without --no-sort; src/bidirected_gfa_writer.rs:53-117, src/ygs_sort.rs:96-162) ----
+ * Y: path-guided SGD, deterministic (counter-based draws, Zipf by table, sub-rounds with order-free int64 accumulation;
+ *    DESIGN.md section 8): the device result is bit-identical to the host twin's;
+ * g: BFS grooming from the head nodes (flipped nodes store their reverse complement);
+ * s: topological sort seeded by the head nodes.  Node ids come out dense 1..N in the final order, edges sorted.
+ * Every path must still spell what it spelled before the sort, else SR_ERR_DEVICE_FAULT and no GFA.
+ * Zero fields are derived from the graph like YgsParams::from_graph (src/ygs_sort.rs:50-95). */
+#define SR_SORT_DEVICE_HOST_TWIN (-1)     /* the batched SGD on one host thread (bit-identical to the device) */
+#define SR_SORT_DEVICE_SEQUENTIAL (-2)    /* every term applied at once, like the reference with one thread (yardstick) */
+typedef struct {
+    uint64_t seed;              /* counter-based draws: splitmix64(seed, iteration, term, draw) */
+    uint64_t iter_max;          /* 100: iterations 0..iter_max, as the reference's checker runs them */
+    double theta;               /* 0.99; cooling iterations use 0.001 */
+    double eps;                 /* 0.01 */
+    double eta_max;             /* 0 = (longest path's step count)^2 */
+    double cooling_start;       /* 0.5: cooling for iterations > floor(cooling_start * iter_max) */
+    uint64_t space;             /* 0 = longest path length in bp */
+    uint64_t space_max;         /* 100 */
+    uint64_t space_quant;       /* 100 */
+    uint64_t min_term_updates;  /* 0 = total path steps: terms per iteration */
+    uint64_t terms_per_round;   /* terms per sub-round (0 = default) */
+    int32_t skip_sgd, skip_groom, skip_topo;   /* the reference's hidden --skip-* flags (src/seqrush.rs:90-99) */
+    int32_t device;             /* >= 0: HIP device, SR_SORT_DEVICE_HOST_TWIN, SR_SORT_DEVICE_SEQUENTIAL */
+} sr_sort_params;
+void sr_sort_params_default(sr_sort_params *p);
+/* induction on the device, optional compaction + renumbering, Ygs, GFA text (device >= 0 runs the SGD on the context's
+ * device and stream) */
+int sr_ctx_build_gfa_sorted(sr_ctx *c, const sr_seqset *seqs, int compact, const sr_sort_params *p, char **gfa,
+                            uint64_t *n_nodes, uint64_t *n_edges);
+/* Ygs of any GFA with S / L / P lines and numeric node ids (the reference's sort_gfa binary) */
+int sr_sort_gfa(const char *gfa_in, const sr_sort_params *p, char **gfa_out, uint64_t *n_nodes, uint64_t *n_edges);
+/* the SGD positions alone, one per node in ascending id order of gfa_in (n = its number of nodes) */
+int sr_sgd_layout(const char *gfa_in, const sr_sort_params *p, double *pos_out, uint64_t n);
+/* the resolved parameters and tables of gfa_in: sizes[0..3] = entries of etas (iter_max + 1), zetas, each prefix table
+ * (space + 1), number of nodes; arrays may be NULL (call once for the sizes) */
+int sr_sgd_tables(const char *gfa_in, const sr_sort_params *p, sr_sort_params *resolved, uint64_t sizes[4], double *etas,
+                  double *zetas, double *prefix_theta, double *prefix_cool);
+/* timings and counts of the calling thread's last sort: [0] SGD ms (device: hipEvents), [1] groom ms, [2] topological
+ * sort ms, [3] GFA writing ms, [4] terms per iteration, [5] iterations, [6] sub-rounds per iteration, [7] nodes,
+ * [8] path steps, [9] wall time of the whole sort stage on a host clock (parameters and tables, device buffers and
+ * copies, SGD, ordering, groom, topological sort, path verification, GFA writing).  Returns the number of slots written. */
+int sr_sort_stats(double *out, uint32_t cap);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

@@ -23,12 +23,22 @@ def main(argv=None):
     ap.add_argument("--output-alignments", default=None)
     ap.add_argument("--no-compact", action="store_true")
     ap.add_argument("--no-sort", action="store_true")
+    ap.add_argument("--sort", action="store_true",
+                    help="Ygs layout: path-guided SGD on the GPU (reproducible), grooming, topological sort")
+    ap.add_argument("--sort-seed", type=int, default=9399220)
+    ap.add_argument("--sgd-iter-max", type=int, default=100)
+    ap.add_argument("--skip-sgd", action="store_true")
+    ap.add_argument("--skip-groom", action="store_true")
+    ap.add_argument("--skip-topo", action="store_true")
     ap.add_argument("--aligner", default="allwave")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs of this node: the pair list is sharded, one process per GPU (torch.distributed.run, RCCL)")
     ns = ap.parse_args(argv)
+    if ns.sort and ns.no_sort:
+        print("Error: --sort and --no-sort exclude each other", file=sys.stderr)
+        return 1
     if ns.gpus > 1 and "RANK" not in os.environ:
         # start one process per GPU BEFORE anything here touches the GPU (never exec from a process that has)
         port = os.environ.get("MASTER_PORT", str(29400 + os.getpid() % 2000))
@@ -41,6 +51,8 @@ def main(argv=None):
                 threads=ns.threads, scores=ns.scores, orientation_scores=ns.orientation_scores,
                 max_divergence=ns.max_divergence, sparsification=ns.sparsification, paf=ns.paf,
                 output_alignments=ns.output_alignments, no_compact=ns.no_compact, no_sort=ns.no_sort,
+                sort=ns.sort, sort_seed=ns.sort_seed, sgd_iter_max=ns.sgd_iter_max, skip_sgd=ns.skip_sgd,
+                skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
                 aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus)
     try:
         if ns.gpus > 1:

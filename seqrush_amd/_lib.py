@@ -27,6 +27,7 @@ EXPORTS = [
     "sr_build_gfa_opts", "sr_ctx_build_gfa_opts", "sr_ctx_merge_labels_host",
     "sr_uf_init_host", "sr_uf_unite_host", "sr_uf_merge_labels_host", "sr_uf_canonical_labels_host",
     "sr_build_gfa_from_nodes", "sr_ctx_counters_all", "sr_knobs_doc",
+    "sr_sort_params_default", "sr_ctx_build_gfa_sorted", "sr_sort_gfa", "sr_sgd_layout", "sr_sgd_tables", "sr_sort_stats",
 ]
 
 
@@ -49,6 +50,16 @@ class ParamsC(C.Structure):
         ("shard_rank", C.c_uint32), ("shard_count", C.c_uint32),
         ("tree_k_nearest", C.c_uint32), ("tree_k_farthest", C.c_uint32), ("tree_rand_frac", C.c_double),
         ("tree_kmer", C.c_uint32),
+    ]
+
+
+class SortParamsC(C.Structure):
+    """sr_sort_params (include/seqrush_amd.h, Ygs layout)"""
+    _fields_ = [
+        ("seed", C.c_uint64), ("iter_max", C.c_uint64), ("theta", C.c_double), ("eps", C.c_double),
+        ("eta_max", C.c_double), ("cooling_start", C.c_double), ("space", C.c_uint64), ("space_max", C.c_uint64),
+        ("space_quant", C.c_uint64), ("min_term_updates", C.c_uint64), ("terms_per_round", C.c_uint64),
+        ("skip_sgd", C.c_int32), ("skip_groom", C.c_int32), ("skip_topo", C.c_int32), ("device", C.c_int32),
     ]
 
 
@@ -135,6 +146,13 @@ def load():
     L.sr_uf_merge_labels_host.argtypes = [C.POINTER(u64), u64, C.POINTER(u64), C.c_uint32]
     L.sr_uf_canonical_labels_host.argtypes = [C.POINTER(u64), u64, C.POINTER(u64)]
     L.sr_build_gfa_from_nodes.argtypes = [PS, C.POINTER(u64), i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    SP, PD = C.POINTER(SortParamsC), C.POINTER(C.c_double)
+    L.sr_sort_params_default.argtypes = [SP]; L.sr_sort_params_default.restype = None
+    L.sr_ctx_build_gfa_sorted.argtypes = [vp, PS, i32, SP, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.sr_sort_gfa.argtypes = [C.c_char_p, SP, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.sr_sgd_layout.argtypes = [C.c_char_p, SP, PD, u64]
+    L.sr_sgd_tables.argtypes = [C.c_char_p, SP, SP, C.POINTER(u64), PD, PD, PD, PD]
+    L.sr_sort_stats.argtypes = [PD, C.c_uint32]
     L.sr_pair_list.argtypes = [C.c_uint32, PP, C.POINTER(C.POINTER(C.c_uint32)),
                                C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None

@@ -1,7 +1,7 @@
 // seqrush_cli.cpp -- C++ host side above the C ABI: the reference's CLI surface for the hot path
 // (src/main.rs:4-7, Args src/seqrush.rs:17-152, run_seqrush :1839-1853, load_sequences :1801-1837).
-// Everything that computes goes through include/seqrush_amd.h; output is the --no-sort graph, compacted unless
-// --no-compact (the Ygs layout is outside the hot path).
+// Everything that computes goes through include/seqrush_amd.h; output is the --no-sort graph or, with --sort, the Ygs
+// layout (sr_ctx_build_gfa_sorted), compacted unless --no-compact.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,7 +52,8 @@ static uint64_t fnv1a(const void *data, size_t n, uint64_t h = 0xcbf29ce48422232
 
 static void usage() {
     fprintf(stderr, "usage: seqrush_mi355x -s in.fa [-o output.gfa] [-k 0] [-S 0,5,8,2,24,1] [--orientation-scores 0,1,1,1]\n"
-                    "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort [--no-compact] [--device N]\n"
+                    "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--device N]\n"
+                    "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
@@ -62,7 +63,9 @@ int main(int argc, char **argv) {
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
-    bool no_sort = false, no_compact = false;
+    bool no_sort = false, no_compact = false, sort = false;
+    sr_sort_params sp;
+    sr_sort_params_default(&sp);
     // multi-GPU without a collective library in this host: every process aligns one shard (--shard R/N) and writes its
     // canonical labels (--labels-out); a last run merges the files (--labels-in, repeatable) and writes the graph.
     // (With RCCL at hand the exchange is one all-gather: python -m seqrush_amd --gpus N, bench.py.)
@@ -88,6 +91,12 @@ int main(int argc, char **argv) {
         else if (a == "--aligner") aligner = val("--aligner");
         else if (a == "--no-sort") no_sort = true;
         else if (a == "--no-compact") no_compact = true;
+        else if (a == "--sort") sort = true;
+        else if (a == "--sort-seed") sp.seed = strtoull(val("--sort-seed"), nullptr, 10);
+        else if (a == "--sgd-iter-max") sp.iter_max = strtoull(val("--sgd-iter-max"), nullptr, 10);
+        else if (a == "--skip-sgd") sp.skip_sgd = 1;
+        else if (a == "--skip-groom") sp.skip_groom = 1;
+        else if (a == "--skip-topo") sp.skip_topo = 1;
         else if (a == "--device") device = atoi(val("--device"));
         else if (a == "--shard") { if (sscanf(val("--shard"), "%u/%u", &shard_rank, &shard_count) != 2 || shard_count == 0 || shard_rank >= shard_count) { fprintf(stderr, "error: --shard R/N\n"); return 2; } }
         else if (a == "--labels-out") labels_out = val("--labels-out");
@@ -103,7 +112,8 @@ int main(int argc, char **argv) {
     }
     if (!labels_in.empty() && (shard_count > 1 || !labels_out.empty())) { fprintf(stderr, "Error: --labels-in is the merge run: no --shard / --labels-out\n"); return 1; }
     if (aligner != "allwave" && aligner != "AllWave") { fprintf(stderr, "Error: aligner '%s' is out of scope; only 'allwave'\n", aligner.c_str()); return 1; }
-    if (!no_sort) { fprintf(stderr, "Error: only --no-sort output is implemented (the Ygs layout is outside the hot path); compaction runs unless --no-compact\n"); return 1; }
+    if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
+    if (!no_sort && !sort) { fprintf(stderr, "Error: only --no-sort output is implemented by default; pass --sort for the Ygs layout; compaction runs unless --no-compact\n"); return 1; }
     std::vector<Seq> seqs;
     if (!load_sequences(sequences, seqs)) { fprintf(stderr, "Error: cannot read %s\n", sequences.c_str()); return 1; }
     printf("Loaded %zu sequences\n", seqs.size());
@@ -189,7 +199,9 @@ int main(int argc, char **argv) {
     }
     char *gfa = nullptr;
     uint64_t nn = 0, ne = 0;
-    if (sr_ctx_build_gfa_opts(ctx, &set, no_compact ? 0 : 1, &gfa, &nn, &ne)) return die();   // compact + renumber unless --no-compact
+    sp.device = device;
+    if (sort ? sr_ctx_build_gfa_sorted(ctx, &set, no_compact ? 0 : 1, &sp, &gfa, &nn, &ne)
+             : sr_ctx_build_gfa_opts(ctx, &set, no_compact ? 0 : 1, &gfa, &nn, &ne)) return die();   // compact + renumber unless --no-compact
     sr_ctx_destroy(ctx);
     std::ofstream o(output, std::ios::binary);
     o << gfa;

@@ -5,6 +5,7 @@
 // compute entry points fail with SR_ERR_NO_DEVICE.
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
+#include <chrono>
 #include <climits>
 #include <functional>
 #include <queue>
@@ -19,9 +20,11 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_graph.h"
+#include "sr_sort.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
+int sr_fail(int code, const std::string &msg) { return fail(code, msg); }      // for sr_sort.cpp / sr_sort.hip
 extern "C" const char *sr_last_error(void) { return g_err.c_str(); }
 
 // ------------------------------------------------------------------ environment knobs
@@ -1833,9 +1836,9 @@ extern "C" int sr_build_gfa_from_nodes(const sr_seqset *seqs, const uint64_t *no
 
 // graph induction on the device from the context's union-find (sr_graph.hip); same
 // text as sr_build_gfa() on the downloaded canonical labels.  which = 3 of sr_ctx_kernel_ms times it.
-extern "C" int sr_ctx_build_gfa_opts(sr_ctx *c, const sr_seqset *seqs, int compact, char **gfa, uint64_t *n_nodes, uint64_t *n_edges) {
+static int ctx_induce_graph(sr_ctx *c, const sr_seqset *seqs, SrGraph &g) {
     if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");
-    if (!seqs || !gfa || !seqs->names) return fail(SR_ERR_INVALID, "null argument");
+    if (!seqs || !seqs->names) return fail(SR_ERR_INVALID, "null argument");
     const uint64_t N = seqs->offsets[seqs->n];
     if (seqs->n != c->n || N != c->total_len) return fail(SR_ERR_INVALID, "sequence set differs from the loaded one");
     if (N >= 0x7fffffffULL) return fail(SR_ERR_UNSUPPORTED, "graph induction on device supports < 2^31 bases");
@@ -1874,7 +1877,7 @@ extern "C" int sr_ctx_build_gfa_opts(sr_ctx *c, const sr_seqset *seqs, int compa
     HIPCHK(hipMemcpy(counts, d_counts, 8, hipMemcpyDeviceToHost));
     std::vector<uint8_t> nbase(counts[0] ? counts[0] : 1);
     std::vector<unsigned long long> edges(counts[1] ? counts[1] : 1);
-    SrGraph g;
+    g = SrGraph();
     g.steps.resize(N);
     HIPCHK(hipMemcpy(nbase.data(), d_nbase, counts[0], hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(g.steps.data(), d_steps, N * 4, hipMemcpyDeviceToHost));
@@ -1886,7 +1889,31 @@ extern "C" int sr_ctx_build_gfa_opts(sr_ctx *c, const sr_seqset *seqs, int compa
     for (uint32_t s = 0; s < seqs->n; s++) g.path_off.push_back(seqs->offsets[s + 1]);
     g.edges.resize(counts[1]);
     for (uint32_t i = 0; i < counts[1]; i++) g.edges[i] = {(uint32_t)(edges[i] >> 32), (uint32_t)(edges[i] & 0xffffffffULL)};
+    return SR_OK;
+}
+extern "C" int sr_ctx_build_gfa_opts(sr_ctx *c, const sr_seqset *seqs, int compact, char **gfa, uint64_t *n_nodes, uint64_t *n_edges) {
+    if (!gfa) return fail(SR_ERR_INVALID, "null argument");
+    SrGraph g;
+    int r = ctx_induce_graph(c, seqs, g);
+    if (r) return r;
     *gfa = finish_gfa(g, seqs, compact, n_nodes, n_edges);
+    return SR_OK;
+}
+// the same graph, compacted + renumbered unless compact == 0, then the Ygs layout (sr_sort.cpp) before the writer
+// (src/bidirected_gfa_writer.rs:39-117); the device SGD runs on this context's device and stream
+extern "C" int sr_ctx_build_gfa_sorted(sr_ctx *c, const sr_seqset *seqs, int compact, const sr_sort_params *p, char **gfa,
+                                       uint64_t *n_nodes, uint64_t *n_edges) {
+    if (!p || !gfa) return fail(SR_ERR_INVALID, "null argument");
+    SrGraph g;
+    int r = ctx_induce_graph(c, seqs, g);
+    if (r) return r;
+    if (compact) { sr_graph_compact(g); sr_graph_renumber(g); }
+    sr_sort_params prm = *p;
+    if (prm.device >= 0) prm.device = c->device;
+    if ((r = sr_graph_ygs(g, prm, prm.device >= 0 ? (void *)c->stream : nullptr))) return r;
+    const auto t0 = std::chrono::steady_clock::now();
+    *gfa = sr_graph_format_gfa(g, seqs->names, n_nodes, n_edges);
+    sr_sort_note_write_ms(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return SR_OK;
 }
 extern "C" int sr_ctx_build_gfa(sr_ctx *c, const sr_seqset *seqs, char **gfa, uint64_t *n_nodes, uint64_t *n_edges) {

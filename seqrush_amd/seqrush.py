@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence as Seq
 import numpy as np
 
 from . import _lib
-from ._lib import ParamsC, SeqSetC, AlignmentsC, check, SeqRushError
+from ._lib import ParamsC, SeqSetC, AlignmentsC, SortParamsC, check, SeqRushError
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -33,7 +33,13 @@ class Args:
     paf: Optional[str] = None               # -p: replay alignments from a PAF file instead of aligning
     output_alignments: Optional[str] = None  # --output-alignments
     no_compact: bool = False                # --no-compact (default: compact + renumber, bidirected_gfa_writer.rs:39-51)
-    no_sort: bool = True                    # only --no-sort is implemented (Ygs layout out of scope)
+    no_sort: bool = True                    # --no-sort: the unsorted graph
+    sort: bool = False                      # added: --sort, the Ygs layout (the reference's default); wins over no_sort
+    sort_seed: int = 9399220                # added: --sort-seed, seed of the counter-based SGD draws
+    sgd_iter_max: int = 100                 # --sgd-iter-max (the reference's hidden flag)
+    skip_sgd: bool = False                  # --skip-sgd / --skip-groom / --skip-topo (src/seqrush.rs:90-99)
+    skip_groom: bool = False
+    skip_topo: bool = False
     aligner: str = "allwave"
     verbose: bool = False
     device: int = 0                         # added: HIP device ordinal
@@ -291,13 +297,18 @@ class Context:
         self.seqset = seqset
         check(self.L.sr_ctx_load_paf(self._h, C.byref(seqset.c), C.byref(params.c), paf_path.encode()))
 
-    def build_gfa(self, compact: bool = False):
+    def build_gfa(self, compact: bool = False, sort: "Optional[SortParams]" = None):
         """graph induction on the device from this context's union-find (+ compaction and
         renumbering, src/bidirected_gfa_writer.rs:39-51) + GFA text;
-        -> (gfa_text, n_nodes, n_edges), byte-identical to build_gfa(seqset, download_labels(), compact)"""
+        -> (gfa_text, n_nodes, n_edges), byte-identical to build_gfa(seqset, download_labels(), compact).
+        sort: SortParams -> the Ygs layout before the writer (src/bidirected_gfa_writer.rs:53-117)"""
         out = C.c_void_p(); nn = C.c_uint64(); ne = C.c_uint64()
-        check(self.L.sr_ctx_build_gfa_opts(self._h, C.byref(self.seqset.c), 1 if compact else 0, C.byref(out),
-                                           C.byref(nn), C.byref(ne)))
+        if sort is None:
+            check(self.L.sr_ctx_build_gfa_opts(self._h, C.byref(self.seqset.c), 1 if compact else 0, C.byref(out),
+                                               C.byref(nn), C.byref(ne)))
+        else:
+            check(self.L.sr_ctx_build_gfa_sorted(self._h, C.byref(self.seqset.c), 1 if compact else 0, C.byref(sort.c),
+                                                 C.byref(out), C.byref(nn), C.byref(ne)))
         text = C.cast(out, C.c_char_p).value.decode()
         self.L.sr_free(out)
         return text, int(nn.value), int(ne.value)
@@ -394,6 +405,82 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class SortParams:
+    """``sr_sort_params``: the Ygs layout's settings (zero fields are derived from the graph, YgsParams::from_graph
+    src/ygs_sort.rs:50-95); device >= 0: SGD on that GPU, -1: host twin (bit-identical), -2: sequential yardstick"""
+
+    HOST_TWIN, SEQUENTIAL = -1, -2
+
+    def __init__(self, **kw):
+        self.c = SortParamsC()
+        _lib.load().sr_sort_params_default(C.byref(self.c))
+        for k, v in kw.items():
+            if not hasattr(self.c, k):
+                raise AttributeError(k)
+            setattr(self.c, k, int(v) if isinstance(v, bool) else v)
+
+    @staticmethod
+    def from_args(args: Args) -> "SortParams":
+        return SortParams(seed=args.sort_seed, iter_max=args.sgd_iter_max, skip_sgd=args.skip_sgd,
+                          skip_groom=args.skip_groom, skip_topo=args.skip_topo, device=args.device)
+
+    def as_dict(self):
+        return {f: getattr(self.c, f) for f, _ in SortParamsC._fields_}
+
+
+def _sort_params(params) -> SortParams:
+    return params if isinstance(params, SortParams) else SortParams(**params)
+
+
+def sort_gfa(text: str, **params) -> str:
+    """the Ygs layout of any GFA with S / L / P lines and numeric node ids (the reference's sort_gfa binary);
+    params: sr_sort_params fields (device=-1 for the host twin).  -> sorted GFA text"""
+    L = _lib.load()
+    sp = _sort_params(params)
+    out = C.c_void_p(); nn = C.c_uint64(); ne = C.c_uint64()
+    check(L.sr_sort_gfa(text.encode(), C.byref(sp.c), C.byref(out), C.byref(nn), C.byref(ne)))
+    res = C.cast(out, C.c_char_p).value.decode()
+    L.sr_free(out)
+    return res
+
+
+def sgd_layout(text: str, **params) -> np.ndarray:
+    """the path-guided SGD positions of a GFA's nodes (ascending id order) -> float64 array"""
+    L = _lib.load()
+    sp = _sort_params(params)
+    n = sum(1 for line in text.split("\n") if line.startswith("S\t"))
+    out = np.zeros(max(n, 1), dtype=np.float64)
+    check(L.sr_sgd_layout(text.encode(), C.byref(sp.c), out.ctypes.data_as(C.POINTER(C.c_double)), n))
+    return out[:n]
+
+
+def sgd_tables(text: str, **params):
+    """resolved parameters and tables of the SGD on a GFA -> (dict of sr_sort_params, etas, zetas, prefix_theta,
+    prefix_cooling)"""
+    L = _lib.load()
+    sp = _sort_params(params)
+    res = SortParamsC()
+    sizes = (C.c_uint64 * 4)()
+    check(L.sr_sgd_tables(text.encode(), C.byref(sp.c), C.byref(res), sizes, None, None, None, None))
+    arrs = [np.zeros(max(int(sizes[i]), 1), dtype=np.float64) for i in (0, 1, 2, 2)]
+    ptr = [a.ctypes.data_as(C.POINTER(C.c_double)) for a in arrs]
+    check(L.sr_sgd_tables(text.encode(), C.byref(sp.c), C.byref(res), sizes, *ptr))
+    d = {f: getattr(res, f) for f, _ in SortParamsC._fields_}
+    return d, arrs[0][:int(sizes[0])], arrs[1][:int(sizes[1])], arrs[2][:int(sizes[2])], arrs[3][:int(sizes[2])]
+
+
+def sort_stats():
+    """the calling thread's last sort: dict of sgd_ms, groom_ms, topo_ms, write_ms, terms_per_iter, iterations,
+    subrounds_per_iter, nodes, steps, stage_ms (host-clock wall time of the whole stage, everything included)"""
+    out = (C.c_double * 10)()
+    n = _lib.load().sr_sort_stats(out, 10)
+    if n < 0:
+        check(n)
+    keys = ("sgd_ms", "groom_ms", "topo_ms", "write_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps",
+            "stage_ms")
+    return {k: float(out[i]) for i, k in enumerate(keys)}
 
 
 def build_gfa(seqset: SeqSet, labels: np.ndarray, compact: bool = False):
@@ -511,11 +598,15 @@ class SeqRush:
         self.write_gfa(args)
 
     def write_gfa(self, args: Args):
-        if not args.no_sort:
-            raise SeqRushError(-6, "only --no-sort output is implemented (the Ygs layout -- path-guided SGD, grooming, "
-                                   "topological sort -- is outside the hot path and not reproducible run to run, "
-                                   "SURVEY 0.4); compaction runs unless --no-compact")
-        text, _, _ = self.ctx.build_gfa(compact=not args.no_compact)   # graph induction on the device, compaction on the host
+        # Args.sort selects the Ygs layout whatever no_sort says: no_sort defaults to True for the Python API, and both
+        # CLIs refuse `--sort --no-sort` before anything runs
+        if not args.no_sort and not args.sort:
+            raise SeqRushError(-6, "only --no-sort output is implemented by default (the reference's unseeded Ygs layout "
+                                   "is not reproducible run to run, SURVEY 0.4); pass --sort for the Ygs layout; "
+                                   "compaction runs unless --no-compact")
+        sort = SortParams.from_args(args) if args.sort else None
+        # graph induction on the device, compaction on the host, Ygs: SGD on the device, groom + topological sort on the host
+        text, _, _ = self.ctx.build_gfa(compact=not args.no_compact, sort=sort)
         with open(args.output, "w") as fh:
             fh.write(text)
 
