@@ -1,6 +1,8 @@
 #!/bin/bash
-# A/B build: scripts/build_variant.sh NAME "-DFLAG=.. ..." -> seqrush_amd/libseqrush_amd_NAME.so (only the 2-bit blocked
-# alignment unit is recompiled with the extra flags; select it at run time with SEQRUSH_AMD_LIB=<path>)
+# A/B build: scripts/build_variant.sh NAME ["-D..."] -> seqrush_amd/libseqrush_amd_NAME.so: the 2-bit blocked alignment unit
+# of the working tree (plus optional extra flags, e.g. "-DSR_BOUNDS=1"), linked with the default library's other objects
+# (build/ from `make`).  Build the reference library first, edit, then build the candidate; select one at run time with
+# SEQRUSH_AMD_LIB=<path> (scripts/ab_variants.sh runs them against the default).
 set -e
 name=$1; flags=$2
 cd "$(dirname "$0")/../seqrush_amd/csrc"

@@ -14,6 +14,7 @@
 #define SR_BFS_SUB lvl
 #define SRK_BFS_ENTRY SRK_NAME(srk_align_bfs)
 #endif
+#define SR_BT_ATTR __noinline__   // (the blocked unit inlines the backtrace: sr_align_blk.hip)
 namespace SR_NS { namespace SR_BFS_SUB {
 #include "sr_align_bfs.inc"
 } }  // namespaces

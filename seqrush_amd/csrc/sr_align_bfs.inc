@@ -532,9 +532,6 @@ __device__ __forceinline__ void bfs_bt_push(GP<uint32_t> buf, int &n, int op, in
 // one thread: backtrace of base case `bj` (oracle wfa_full); reversed run-length ops into buf
 template <typename OT, bool TWO>
 // hist / hstride: first cell and cells per row of the history rows [level][component] the job's columns live in
-#ifndef SR_BT_ATTR
-#define SR_BT_ATTR __noinline__
-#endif
 __device__ SR_BT_ATTR int bfs_backtrace(GP<OT> hist, unsigned hstride, int bj, int score, GP<uint32_t> buf, int *n_out) {
     const SrPen pen = b_sh.pen[0];
     const BJob &b = b_sh.job[bj];

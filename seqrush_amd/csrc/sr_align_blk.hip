@@ -13,6 +13,7 @@
 #else
 // 16 segments (32 aligners) per pass keep the static LDS of a workgroup below 20 KB
 #define SR_BFS_MAXACT 16
+#define K_P2 16
 #define SR_BLK_SUB wg4
 #endif
 #define BFS_MAK_SLOTS SR_BLK_MAK_SLOTS
@@ -24,14 +25,9 @@
 // mismatch penalty of 0 in the score of the CIGAR), or left the private aperture ("Memory access fault", round 3's
 // "unexplained" faults and this round's first runs of the 512-thread 32-bit instance).  Same source, SR_BT_ATTR =
 // __noinline__: wrong / faulting; __forceinline__: right (profiles/r04_backtrace_call.log).  DESIGN.md section 4.1.
-#ifndef SR_BT_ATTR
 #define SR_BT_ATTR __forceinline__
-#endif
 namespace SR_NS { namespace SR_BLK_SUB {
 #include "sr_align_bfs.inc"
-#ifndef SR_BLK_MIN_WAVES
-#define SR_BLK_MIN_WAVES 4
-#endif
 #include "sr_align_blk.inc"
 } }  // namespaces
 using namespace SR_NS::SR_BLK_SUB;
@@ -95,24 +91,9 @@ extern "C" int SRK_NAME(srk_align_blkw)(const SrAlignArgs *a, int nwg, size_t ld
 extern "C" int SRK_NAME(srk_align_blk)(const SrAlignArgs *a, int nwg, size_t lds_bytes, int off16, int nthreads, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const bool two = a->pen.two != 0;
-#ifdef SR_BLK_ONLY_C5     // experiment builds: the C5 instance only (32-bit search, 16-bit ring, 512 threads)
-    if (a->kblock == 10 && !off16 && two && a->ring_u16 && nthreads == 512) return launch_blk10<int32_t, 512, true, false, uint16_t>(a, nwg, lds_bytes, st);
-    return -1;
-}
-#elif defined(SR_BLK_ONLY_PROD)   // experiment builds (seconds instead of minutes, one kernel in the disassembly): the C2 / C4 production instance only
-    if (a->kblock == 10 && off16 && two && nthreads == 256 && !a->profile_ticks) return launch_blk10<int16_t, 256, true>(a, nwg, lds_bytes, st);
-#ifdef SR_NT192                   // (experiment: three-wave workgroups, five per CU)
-    if (a->kblock == 10 && off16 && two && nthreads == 192 && !a->profile_ticks) return launch_blk10<int16_t, 192, true>(a, nwg, lds_bytes, st);
-#endif
-    return -1;
-}
-#else
     if (a->kblock == 10) {
         if (off16) {
 #if SR_SYMBITS == 2
-#ifdef SR_PROF_WIDE   // (A/B builds only: tick counters for the 1024-thread shape)
-            if (nthreads == 1024 && two && a->profile_ticks) return launch_blk10<int16_t, 1024, true, true>(a, nwg, lds_bytes, st);
-#endif
             if (nthreads == 1024 && two) return launch_blk10<int16_t, 1024, true>(a, nwg, lds_bytes, st);    // fewer pairs than CUs
 #endif
             if (nthreads >= 512) return two ? launch_blk10<int16_t, 512, true>(a, nwg, lds_bytes, st) : launch_blk10<int16_t, 512, false>(a, nwg, lds_bytes, st);
@@ -122,7 +103,7 @@ extern "C" int SRK_NAME(srk_align_blk)(const SrAlignArgs *a, int nwg, size_t lds
 #endif
             return two ? launch_blk10<int16_t, 256, true>(a, nwg, lds_bytes, st) : launch_blk10<int16_t, 256, false>(a, nwg, lds_bytes, st);
         }
-        // 32-bit searches with the ring stored as uint16 (offset + 8192): longest sequence < 57 k (host: ring_u16)
+        // 32-bit searches with the ring stored as 16-bit cells (offset - SR_RING_BIAS): longest sequence < 57 k (host: ring_u16)
         if (a->ring_u16 && nthreads == 512) return two ? launch_blk10<int32_t, 512, true, false, uint16_t>(a, nwg, lds_bytes, st)
                                                        : launch_blk10<int32_t, 512, false, false, uint16_t>(a, nwg, lds_bytes, st);
         if (a->ring_u16) return two ? launch_blk10<int32_t, 256, true, false, uint16_t>(a, nwg, lds_bytes, st)
@@ -136,5 +117,4 @@ extern "C" int SRK_NAME(srk_align_blk)(const SrAlignArgs *a, int nwg, size_t lds
     }
     return two ? launch_blk3<int32_t, 256, true>(a, nwg, lds_bytes, st) : launch_blk3<int32_t, 256, false>(a, nwg, lds_bytes, st);
 }
-#endif   // SR_BLK_ONLY_PROD
 #endif

@@ -18,1846 +18,11 @@
 //  * Rows: [level mod depth][component] in one ring (depth = scope + B + 1), the
 //    base-case history has the same shape with depth = all levels.
 //  * Breakpoint detection: see blk_overlap (upper-bound row filter + reduction).
-#ifndef SR_ORI_B
-#define SR_ORI_B 16              // levels per pass of the in-kernel orientation (default orientation penalties; round 4: 8 -> 16)
-#endif
-#ifndef SR_KB_MAX
-#define SR_KB_MAX 10             // deepest block any alignment instance of this build computes per pass (static LDS tables)
-#endif
-#define KB_LV (SR_ORI_B > SR_KB_MAX ? SR_ORI_B : SR_KB_MAX)      // levels of the per-level range / reach tables (orientation blocks may be deeper)
-#define KB_MAX SR_KB_MAX
-#ifndef K_P2
-#define K_P2 16
-#endif
-#ifndef SR_PASS_BARRIER3
-#define SR_PASS_BARRIER3 0         // 1: every pass of a search ends with a third barrier, as before round 4 (A/B builds)
-#endif
-#ifndef SR_BAND_FIRST
-#define SR_BAND_FIRST 0            // 1: the tile queue of a pass starts with every aligner's tile over diagonal 0 (A/B builds; measured +2 % on C2 / C4: kept off)
-#endif
-#ifndef SR_MASKED_LOADS
-#define SR_MASKED_LOADS 1          // edge tiles of the tight cover load under the lanes' coverage masks (0: load every lane, then mask; A/B builds)
-#endif
-#ifndef SR_TIGHT
-#define SR_TIGHT 1                 // ring tiles of the exact instance cover a block's own range only; readers mask what lies outside a source block's coverage (0: A/B builds)
-#endif
-#ifndef SR_BLK_PK16
-#define SR_BLK_PK16 1
-#endif
-#ifndef SR_LEAN_PASS
-#define SR_LEAN_PASS 1             // keep per-lane state out of the registers that live across a pass (they are spilled to scratch, and a pass's
-                                   // scratch traffic goes through the same memory system the rows do): cell tallies in LDS, the pass's level opaque
-                                   // to loop strength reduction (0: A/B builds)
-#endif
-#ifndef SR_LEAN_CTL
-#define SR_LEAN_CTL 1              // the control section forms its per-lane addresses from an opaque thread index, once per pass (0: A/B builds; run 39: -2.0 %)
-#endif
-#ifndef SR_MERGE_TAILS
-#define SR_MERGE_TAILS 0           // 1: ring searches of the exact instance put the last tiles of a segment's two aligners into the two halves of one
-                                   // wave when both fit.  Round 4, parity-green, -8 % tiles, owned-lane fill 0.79 -> 0.85 -- and +-0 in time on C2 and C4
-                                   // (profiles/r04_ab.log run 30: the edge tiles it removes are the cheap ones).  Kept as a switch, default off.
-#endif
-#ifndef SR_PK_U16
-#define SR_PK_U16 1                // the 16-bit ring of a 32-bit search runs the packed tile (0: 32-bit tile with conversions, A/B builds)
-#endif
-#define KPK_U16_OF(OT, ST, B, X) (SR_BLK_PK16 && SR_PK_U16 && SR_IMM_ROWS && sizeof(OT) == 4 && sizeof(ST) == 2 && (X) > 0 && (B) % 10 == 0)
-#define KTIGHT_OF(OT, ST, B, X) ((X) > 0 && (B) % 10 == 0 && (sizeof(OT) == 2 || KPK_U16_OF(OT, ST, B, X)) && SR_TIGHT && SR_IMM_ROWS && SR_BLK_PK16)
-#ifndef SR_IMM_ROWS
-#define SR_IMM_ROWS 1              // immediate-offset row addressing on the ring of the exact instance (0: A/B builds)
-#endif
-
-struct KShared {
-    int jklo[KB_LV][BJ_MAX + 2], jkhi[KB_LV][BJ_MAX + 2];     // (+2: the aligners of an I/D recompute pass)
-    int jak[KB_MAX][BJ_MAX], jreach[KB_LV][BJ_MAX];
-    int jtstart[BJ_MAX + 1], jglo[BJ_MAX + 2], jghi[BJ_MAX + 2];
-    int jmerge[BJ_MAX];                                // blk_setup: forward aligner of a segment: 1 + index of the tile that also carries the reverse aligner's last tile (0: none)
-    int jband[BJ_MAX], jbandown[BJ_MAX], nband;        // band-first tile order (blk_setup): an aligner's tile over diagonal 0, the aligners that have one
-    unsigned newmask;                                  // segments that entered phase 2 in this pass
-    int rt_n0, rt_total;                               // recompute pass: tiles of its first aligner, of both
-    int jgplo[BJ_MAX + 2], jgphi[BJ_MAX + 2];                  // groups the previous block of the aligner covered (U row validity)
-    int total_tiles;
-    int next_tile;                                     // tile queue of a pass: the next tile nobody has taken yet
-    // batched breakpoint detection (phase 2) of one pass: up to K_P2 segments, <= 2*KB_MAX overlap calls each
-    int p2n, p2seg[K_P2];
-    unsigned p2mask_lo, p2mask_hi;
-    int pc_n[K_P2], pc_s0[K_P2][2 * KB_MAX], pc_s1[K_P2][2 * KB_MAX];
-    unsigned char pc_side[K_P2][2 * KB_MAX];
-    signed char pc_idx[K_P2][2][KB_MAX];               // call index of (side, level of the block) or -1
-    unsigned long long pc_best[K_P2][2 * KB_MAX];
-    int pu_start[2 * K_P2 + 1], pu_glo[2 * K_P2];
-    int pu_kmin[2 * K_P2], pu_kmax[2 * K_P2];          // band of diagonals of a filter unit (segment, side) that passed the filter at some level
-    int cl_n;
-#ifdef SR_BOUNDS
-    unsigned lds_seq_bytes;                                // dynamic LDS of the workgroup: four sequence copies + read slack
-    int bnd_flag; unsigned bnd_off, bnd_ext, bnd_what;     // first offending access of the workgroup (offset, extent, what: 1 ring / 2 history row, 3 LDS window)
-#endif
-    int redo_from;                     // base cases: first job of the batch that outgrew the levels it was given (BJ_MAX: none)
-    int pend_op, pend_len;             // CIGAR emission: the run being built (not yet stored)
-    unsigned long long row_w[2][16];   // SR_LEAN_PASS: per wave, lane accesses of its tiles' row loads / stores (summed when the kernel ends)
-    unsigned long long cells_l[64];    // SR_LEAN_PASS: wavefront cells per lane of wave 0 (= aligner), summed when the kernel ends
-    unsigned long long t_c1, t_c2;                           // PROF: control section: max_ak stores, per-segment control
-    unsigned long long t_setup, t_p2a, t_p2f, t_p2e, t_p2w;     // PROF: ticks of the set-up sections, of breakpoint detection's stages
-    unsigned long long dg_steps, dg_nbase, dg_nbp, dg_npass;   // levels x aligners advanced, base cases, breakpoint searches, passes (lane 0 of wave 0 adds)
-    unsigned long long dg_f, dg_c, dg_e, dg_r;         // breakpoint detection: filter units, candidates, exact-test units, rounds
-    unsigned long long dg_redo;                        // base cases searched again with the worst-case region (outgrew their levels)
-#ifdef SR_TILE_STATS
-    unsigned long long ts[8];                          // experiment builds: tile statistics (blk_setup)
-#endif
-#ifdef SR_TILE_STAMPS                                  // diagnostic build only (scripts/build_variant.sh stamps -DSR_TILE_STAMPS)
-    unsigned long long st_wait[16], st_body[16], st_tiles[16], st_ext[16];   // per wave: shader cycles waiting for a tile's first rows, in its levels; tiles; extension-loop iterations
-#endif
-};
-__shared__ KShared k_sh;
-#ifdef SR_TILE_STAMPS
-#define ST_NOW() __builtin_amdgcn_s_memtime()
-#define ST_DRAIN() __builtin_amdgcn_s_waitcnt(0)
-#else
-#define ST_NOW() 0ull
-#define ST_DRAIN() ((void)0)
-#endif
-
-// Row storage of a workgroup.  A row (one component of one level) is addressed by a row offset (uniform) plus a
-// lane part that depends on the diagonal only:  element = rowoff(level, component) + klane(idx),
-//     rowoff = component * cstr + slot(level) * sstr,   klane(idx) = (idx >> 8) * chs + (idx & 255).
-//  * ring (breakpoint searches): chunk-major -- the 256-cell pieces (64 groups, one wave access) of all rows that
-//    cover the same diagonals are stored together, a component's levels next to each other (cstr = depth * 256,
-//    sstr = 256, chs = rows * 256).  The 10 M rows a tile loads as M[s-10] are then ten adjacent 512-byte pieces, the
-//    10 it stores likewise: runs of adjacent rows sustain 5.0-5.2 TB/s where rows 10+ KB apart reach 3.7
-//    (scripts/calib/chunk.hip, profiles/r02_chunk_locality.json).
-//  * base-case history: plain rows [level][component][diagonal] (cstr = w, sstr = 5 w, chs = 256: klane(idx) = idx),
-//    the layout the backtrace of sr_align_bfs.inc reads.
-// One uniform 64-bit base per workspace + 32-bit offsets: the accesses take the "saddr" form, a row costs one SGPR
-// (a 64-bit address per row would cost a pair each: 42 rows per 10-level tile, i.e. a tile living on spilled SGPRs).
-// The host keeps a workspace below 4 GB.
-// ST = storage type of the cells.  ST == OT, or (ring of 32-bit searches whose longest sequence is < 57 k) uint16_t
-// holding offset + 8192: NULL (-8192) is 0, the rows are half the bytes (C5 is bound by them), a load is one subtract.
-template <typename OT, typename ST = OT>
-struct KRows {
-    GP<ST> base;
-    unsigned cM, cst2, sstr, chs;      // component c's rows start at (c ? cM + (c - 1) * cst2 : 0); slot stride; chunk stride of klane()
-    unsigned urow, nuloff, trash;      // row offsets of the U row (0 = none), the NULL row, 256 cells nobody reads
-    int depth, depth2;                 // ring depth of the M rows / of the I and D rows (round 3: the latter only span
-                                       // breakpoint detection's window, scope + 2 B + 2 levels: 269 rows instead of 373)
-    bool perjob;                       // base-case history: every job has its own region and row width (BJob hbase / hw)
-    unsigned extent;                   // cells of the workgroup's region (bounds-checked build: every access is tested against it)
-};
-// ---- bounds-checked debug build (-DSR_BOUNDS, scripts/build_variant.sh bounds "-DSR_BOUNDS=1"; VERDICT r3 item 3) ------------
-// Every row access (ring and base-case history, 4 cells from `cell`) is tested against the workgroup's extent and every LDS
-// window address of a live cell against the sequence region; an offender sets SR_DEV_ERR_ADDRESS, is recorded (first one per
-// workgroup -> counters[40..43]: pair, what << 28 | level, offset, extent) and does NOT touch memory: loads return NULL
-// cells, stores are dropped.  Costs ~15 % of kernel time; production builds carry none of it.
-#ifdef SR_BOUNDS
-__device__ __forceinline__ void kbnd_fail(unsigned what, unsigned off, unsigned ext) {
-    atomicOr(&b_sh.err, SR_DEV_ERR_ADDRESS);
-    if (atomicCAS(&k_sh.bnd_flag, 0, 1) == 0) { k_sh.bnd_off = off; k_sh.bnd_ext = ext; k_sh.bnd_what = what; }
-}
-#define SR_BND_OK(R, CELL, WHAT) (((CELL) + 3u < (R).extent) ? true : (kbnd_fail((WHAT), (CELL), (R).extent), false))
-#else
-#define SR_BND_OK(R, CELL, WHAT) true
-#endif
-// per-tile addressing context (all wave-uniform)
-struct KAdr { unsigned hb, cM, cst2, sst; int slotM, slotD, depth, depth2; };
-template <typename OT, typename ST>
-__device__ __forceinline__ KAdr kadr(const KRows<OT, ST> &R, const BJob &jb, int slots) {
-    KAdr A;
-    if (R.perjob) { const unsigned hw = RFL(jb.hw); A.hb = RFL(jb.hbase); A.cM = hw; A.cst2 = hw; A.sst = 5u * hw; }
-    else { A.hb = 0u; A.cM = R.cM; A.cst2 = R.cst2; A.sst = R.sstr; }
-    A.slotM = slots & 0xffff; A.slotD = (int)((unsigned)slots >> 16); A.depth = R.depth; A.depth2 = R.depth2;
-    return A;
-}
-// the two ring slots of level s packed into one int (M rows: low half, I / D rows: high half)
-template <typename OT, typename ST>
-__device__ __forceinline__ int kslots(const KRows<OT, ST> &R, int s) { return (s % R.depth) | ((s % R.depth2) << 16); }
-// 16-bit ring of a 32-bit search (longest sequence < 57 k): a cell holds offset - SR_RING_BIAS as a SIGNED 16-bit value
-// (round 3 stored offset + 8192 unsigned -- the same bits with the top one flipped).  NULL (-8192) is -32768, the smallest
-// value, offsets up to 57343 fit, and -- the point of the signed form -- the packed 16-bit tile runs on the rows as they are
-// (signed packed max / saturating subtract for the limit test; blk_tile16<.., BIAS = SR_RING_BIAS>): no conversion at a
-// load or store, half the VALU of the 32-bit tile.  32-bit readers (breakpoint detection, control) add the bias back.
-#define SR_RING_BIAS 24576
-typedef short __attribute__((ext_vector_type(4))) S4;
-template <typename OT, typename ST> __device__ __forceinline__ V4<OT> kcvt_in(V4<ST> v) {
-    if constexpr (sizeof(ST) == sizeof(OT)) return v;
-    else { const V4<OT> b = {SR_RING_BIAS, SR_RING_BIAS, SR_RING_BIAS, SR_RING_BIAS}; return __builtin_convertvector((S4)v, V4<OT>) + b; }
-}
-template <typename OT, typename ST> __device__ __forceinline__ V4<ST> kcvt_out(V4<OT> v) {
-    if constexpr (sizeof(ST) == sizeof(OT)) return v;
-    else { const V4<OT> b = {SR_RING_BIAS, SR_RING_BIAS, SR_RING_BIAS, SR_RING_BIAS}; return (V4<ST>)__builtin_convertvector(v - b, S4); }
-}
-
-// ring slot of level s0 + d, given slot0 = s0 mod depth and |d| < depth
-__device__ __forceinline__ unsigned kslot(int slot0, int d, int depth) {
-    int t = slot0 + d;
-    t += (t < 0) ? depth : 0;
-    t -= (t >= depth) ? depth : 0;
-    return (unsigned)t;
-}
-template <typename OT, typename ST>
-__device__ __forceinline__ unsigned klane(const KRows<OT, ST> &R, unsigned idx) { return (idx >> 8) * R.chs + (idx & 255u); }
-template <typename OT, typename ST>
-__device__ __forceinline__ unsigned krow_rel(const KRows<OT, ST> &R, const KAdr &A, int s0, int lvl, int c) {
-    if (lvl < 0) return R.nuloff;
-    if (c == SR_C_M) return A.hb + kslot(A.slotM, lvl - s0, A.depth) * A.sst;
-    return A.hb + A.cM + (unsigned)(c - 1) * A.cst2 + kslot(A.slotD, lvl - s0, A.depth2) * A.sst;
-}
-// absolute level of the ring (breakpoint detection, walk)
-template <typename OT, typename ST>
-__device__ __forceinline__ unsigned krow_abs(const KRows<OT, ST> &R, int lvl, int c) {
-    if (c == SR_C_M) return (unsigned)(lvl % R.depth) * R.sstr;
-    return R.cM + (unsigned)(c - 1) * R.cst2 + (unsigned)(lvl % R.depth2) * R.sstr;
-}
-// row `slot` of component c of the ring (in-kernel orientation: fixed slots)
-template <typename OT, typename ST>
-__device__ __forceinline__ unsigned krow_fix(const KRows<OT, ST> &R, int c, int slot) {
-    return (c == SR_C_M ? 0u : R.cM + (unsigned)(c - 1) * R.cst2) + (unsigned)slot * R.sstr;
-}
-// li = klane(idx) of the lane's first cell (4 cells of a group never straddle a 256-cell piece)
-#define SR_ROWPTR(R, OFF, LI) ((V4<ST> __attribute__((address_space(1))) *)((char __attribute__((address_space(1))) *)(R).base + (((OFF) + (LI)) * (unsigned)sizeof(ST))))
-#define SR_BND_WHAT(R) ((R).perjob ? 2u : 1u)
-template <typename OT> __device__ __forceinline__ V4<OT> knull4() { const V4<OT> n = {(OT)NULLV, (OT)NULLV, (OT)NULLV, (OT)NULLV}; return n; }
-template <typename OT, typename ST> __device__ __forceinline__ V4<OT> rld(const KRows<OT, ST> &R, unsigned off, unsigned li) {
-    if (!SR_BND_OK(R, off + li, SR_BND_WHAT(R))) return knull4<OT>();
-    return kcvt_in<OT, ST>(*SR_ROWPTR(R, off, li));
-}
-template <typename OT, typename ST> __device__ __forceinline__ V4<OT> rld_nt(const KRows<OT, ST> &R, unsigned off, unsigned li) {
-    if (!SR_BND_OK(R, off + li, SR_BND_WHAT(R))) return knull4<OT>();
-    return kcvt_in<OT, ST>(__builtin_nontemporal_load(SR_ROWPTR(R, off, li)));
-}
-template <typename OT, typename ST> __device__ __forceinline__ void rst(const KRows<OT, ST> &R, unsigned off, unsigned li, V4<OT> v) {
-    if (!SR_BND_OK(R, off + li, SR_BND_WHAT(R))) return;
-    *SR_ROWPTR(R, off, li) = kcvt_out<OT, ST>(v);
-}
-template <typename OT, typename ST> __device__ __forceinline__ void rst_nt(const KRows<OT, ST> &R, unsigned off, unsigned li, V4<OT> v) {
-    if (!SR_BND_OK(R, off + li, SR_BND_WHAT(R))) return;
-    __builtin_nontemporal_store(kcvt_out<OT, ST>(v), SR_ROWPTR(R, off, li));
-}
-// one cell
-template <typename OT, typename ST> __device__ __forceinline__ int rcell(const KRows<OT, ST> &R, unsigned off, int idx) {
-    if (!SR_BND_OK(R, off + klane(R, (unsigned)idx), SR_BND_WHAT(R))) return NULLV;
-    const int v = (int)R.base[off + klane(R, (unsigned)idx)];
-    return sizeof(ST) == sizeof(OT) ? v : (int)(short)v + SR_RING_BIAS;
-}
-template <typename OT, typename ST> __device__ __forceinline__ void rput(const KRows<OT, ST> &R, unsigned off, unsigned idx, int val) {
-    if (!SR_BND_OK(R, off + klane(R, idx), SR_BND_WHAT(R))) return;
-    R.base[off + klane(R, idx)] = (ST)(sizeof(ST) == sizeof(OT) ? val : val - SR_RING_BIAS);
-}
-
-// ---- immediate-offset row addressing (round 4; exact 10-level instance on the ring) -------------------------------------
-// The ring is chunk-major with a component's levels adjacent, and the host keeps both ring depths multiples of the block
-// (80 / 50 levels for the default penalties), so a block's ten levels -- and any five consecutive levels that start at a
-// multiple of five -- are ten (five) ADJACENT 512-byte pieces that never straddle the ring's wrap.  A tile therefore
-// addresses its 42 rows as 13 uniform bases (SGPR pairs) + one lane offset (a VGPR for the whole tile) + the row's
-// distance as the instruction's immediate: no address VALU, no row offset per row in an SGPR (round 3: 42 offsets hoisted
-// out of the tile loop and spilled into VGPR lanes -- v_readlane + hazard s_nop + v_add per row).  Levels below 0 read a
-// NULL block of ten rows.  KBLK_C: a block base points at the block's fifth row, so that the immediates of its ten rows
-// (-4 .. +5 rows = -2048 .. +2560 bytes) fit the instruction's 13-bit signed field.
-typedef char __attribute__((address_space(1))) *GPB;
-#define KBLK_C 4
-template <typename OT, typename ST>
-__device__ __forceinline__ GPB kbase(const KRows<OT, ST> &R, unsigned off_cells) { return (GPB)R.base + (size_t)off_cells * sizeof(ST); }
-// lane_b = byte offset of the lane's group inside a row (klane(idx) * sizeof(ST)), IMM = distance in rows (compile time)
-#define SR_IMMPTR(B, LANE_B, IMM) ((V4<ST> __attribute__((address_space(1))) *)((B) + (LANE_B) + (IMM) * (256 * (int)sizeof(ST))))
-// (imm: a constant once the level loops are unrolled -- it folds into the instruction's offset field.  Instruction selection
-// works block by block and only sees the saddr form -- uniform 64-bit base + zero-extended 32-bit lane offset -- when the
-// zero extension happens in the block of the access: a level of the tile takes its own opaque copy of the lane offset
-// (kopaque_v, one v_mov); without it the compiler forms base + lane once per base as a 64-bit VGPR pair ahead of the loop)
-__device__ __forceinline__ unsigned kopaque_v(unsigned l) { asm volatile("" : "+v"(l)); return l; }
-__device__ __forceinline__ int kopaque_s(int x) { asm volatile("" : "+s"(x)); return x; }       // a uniform value the optimiser may not look through
-#define SR_IMMCELL(R, B, LANE_B, IMM) ((unsigned)(((B) - (GPB)(R).base) / (long)sizeof(ST)) + (LANE_B) / (unsigned)sizeof(ST) + (unsigned)((IMM) * 256))
-template <typename OT, typename ST, typename KR> __device__ __forceinline__ V4<OT> ild(const KR &R, GPB b, unsigned lane_b, int imm) {
-    if (!SR_BND_OK(R, SR_IMMCELL(R, b, lane_b, imm), 1u)) return knull4<OT>();
-    return kcvt_in<OT, ST>(*SR_IMMPTR(b, lane_b, imm));
-}
-template <typename OT, typename ST, typename KR> __device__ __forceinline__ V4<OT> ild_nt(const KR &R, GPB b, unsigned lane_b, int imm) {
-    if (!SR_BND_OK(R, SR_IMMCELL(R, b, lane_b, imm), 1u)) return knull4<OT>();
-    return kcvt_in<OT, ST>(__builtin_nontemporal_load(SR_IMMPTR(b, lane_b, imm)));
-}
-template <typename OT, typename ST, typename KR> __device__ __forceinline__ void ist(const KR &R, GPB b, unsigned lane_b, int imm, V4<OT> v) {
-    if (!SR_BND_OK(R, SR_IMMCELL(R, b, lane_b, imm), 1u)) return;
-    *SR_IMMPTR(b, lane_b, imm) = kcvt_out<OT, ST>(v);
-}
-template <typename OT, typename ST, typename KR> __device__ __forceinline__ void ist_nt(const KR &R, GPB b, unsigned lane_b, int imm, V4<OT> v) {
-    if (!SR_BND_OK(R, SR_IMMCELL(R, b, lane_b, imm), 1u)) return;
-    __builtin_nontemporal_store(kcvt_out<OT, ST>(v), SR_IMMPTR(b, lane_b, imm));
-}
-
-// 4 cells of a 16-bit row as they are stored (packed tiles: the U row)
-template <typename KR> __device__ __forceinline__ S4 rld_raw16(const KR &R, unsigned off, unsigned li) {
-    if (!SR_BND_OK(R, off + li, 1u)) { const S4 n = {(short)-32768, (short)-32768, (short)-32768, (short)-32768}; return n; }
-    return *(S4 __attribute__((address_space(1))) *)((char __attribute__((address_space(1))) *)R.base + (size_t)(off + li) * 2u);
-}
-template <typename KR> __device__ __forceinline__ void rst_raw16(const KR &R, unsigned off, unsigned li, S4 v) {
-    if (!SR_BND_OK(R, off + li, 1u)) return;
-    *(S4 __attribute__((address_space(1))) *)((char __attribute__((address_space(1))) *)R.base + (size_t)(off + li) * 2u) = v;
-}
-
-// value held by the previous / next lane (NULL at the wave's ends)
-__device__ __forceinline__ int lane_left(int x) { return __builtin_amdgcn_update_dpp(NULLV, x, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int lane_right(int x) { return __builtin_amdgcn_update_dpp(NULLV, x, 0x130, 0xf, 0xf, false); }
-// max over each row of 16 lanes, result in the row's last lane
-__device__ __forceinline__ int row16_max(int v) {
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x112, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x114, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x118, 0xf, 0xf, false));
-    return v;
-}
-
-// same for values >= 0: zero-filled shifts fold into v_max_i32_dpp (no copy of the operand first)
-__device__ __forceinline__ int row16_max_nn(int v) {
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true));
-    return v;
-}
-
-// lanes of halo on either side of a wave tile: the I2 / D2 chains (gap-extend 1) consume one diagonal per level
-template <int B> struct KGeo {
-    static constexpr int HL = B <= 5 ? 2 : (B + 3) / 4;
-    static constexpr int OWN = 64 - 2 * HL;              // owned 4-diagonal groups per tile
-};
-
-// (window reads, ffs_sym, min3u, lanes_or_zero: sr_dev_common.h)
-
-// one wave, one tile of aligner jid: levels s0 .. s0+B-1 of KGeo<B>::OWN owned groups
-// IDONLY: recompute pass -- only the I/D chains of the block (M comes from the stored rows of older levels, the
-// block's own M rows exist already); tix = index of the aligner's range tables (jid, or BJ_MAX + 0/1).
-// X, OE1 (exact-penalty instance, X = mismatch, OE1 = o1 + e1, B == OE1 <= o2 + e2): a block is twice as deep as the
-// mismatch distance, so M[s - x] of the block's later levels is the lane's own M of x levels earlier (registers), and
-// the rows M[s0-x .. s0-1] that feed the first x levels are the same rows levels x.. read as M[s - o1 - e1]: 26 row
-// loads + 16 row stores per 10 levels instead of 2 x (21 + 12).  The M[s - o2 - e2] rows are prefetched three
-// levels ahead instead of all up front (registers).  X = 0: generic instance, B <= min(x, o1+e1, o2+e2).
-template <typename OT, bool TWO, int B, int E1, int E2, bool IDONLY = false, int X = 0, int OE1 = 0, typename ST = OT>
-__device__ __forceinline__ void blk_tile(const KRows<OT, ST> &R, const int s0, const int slot0, const SrPen &pen,
-                                         const int jid, const int ti, const int tix, unsigned &row_ld, unsigned &row_st) {
-    constexpr int N1 = E1 < B ? E1 : B, N2 = E2 < B ? E2 : B;
-    constexpr bool XK = X > 0;
-    static_assert(!XK || (B == OE1 && X <= B), "exact-penalty instance: block depth == o1 + e1 >= x");
-    constexpr int HL = KGeo<B>::HL, OWN = KGeo<B>::OWN;
-    constexpr int PF = XK ? 3 : B;                        // prefetch distance of the M[s - o2 - e2] rows
-    const int lane = threadIdx.x & 63;
-    const BJob &jb = b_sh.job[jid];
-    const int base = RFL(jb.base), shift = RFL(jb.shift), plen = RFL(jb.plen), tlen = RFL(jb.tlen);
-    const int p0 = RFL(jb.p0), t0 = RFL(jb.t0), begin = RFL(jb.begin);
-    const int chk = RFL(jb.chk), kend = RFL(jb.kend), poff = RFL(jb.poff), toff = RFL(jb.pad0);
-    const bool rec = IDONLY || RFL(jb.pad2) != 0;             // store every I/D row (phase 2 / base case / recompute)
-    const int glo = RFL(k_sh.jglo[tix]), ghi = RFL(k_sh.jghi[tix]);
-    const int g = glo + ti * OWN + lane - HL;
-    const bool owned = (lane >= HL) && (lane < 64 - HL) && (g <= ghi);
-    const int k0 = (g << 2) - shift;
-    const unsigned idx0 = klane(R, (unsigned)(base + (g << 2)));      // lane part of the row addresses
-    const LP P = (LP)(lds_seq + poff), T = (LP)(lds_seq + toff);
-    // symbol index (LDS-wide: 16 / 8 / 4 symbols per word from LDS address 0) of P[p0 - k0] and T[t0]
-    const int cp0 = p0 - k0 + (int)(((uint32_t)(uintptr_t)P >> 2) << SR_WIN_LOG);
-    const int ct0 = t0 + (int)(((uint32_t)(uintptr_t)T >> 2) << SR_WIN_LOG);
-    const KAdr A = kadr(R, jb, slot0);
-#define KROW(LVL, C) krow_rel(R, A, s0, (LVL), (C))
-    // ---- every source row of the block that older blocks wrote: one load per row and lane
-    V4<OT> Lmx[XK ? 1 : B], Lmo1[B], Lmo2[B], Li1[N1], Ld1[N1], Li2[N2], Ld2[N2];
-#pragma unroll
-    for (int j = 0; j < B; j++) {
-        if (!IDONLY && !XK) Lmx[XK ? 0 : j] = rld<OT>(R, KROW(s0 + j - pen.x, SR_C_M), idx0);
-        // (exact instance: rows s0-x .. s0-1 double as the M[s-x] source of levels 0 .. x-1, so no last-use hint there)
-        Lmo1[j] = rld<OT>(R, KROW(s0 + j - pen.o1 - E1, SR_C_M), idx0);
-        if (TWO && j < PF) Lmo2[j] = rld_nt<OT>(R, KROW(s0 + j - pen.o2 - E2, SR_C_M), idx0);   // last use of that M level
-    }
-#pragma unroll
-    for (int j = 0; j < N1; j++) {
-        Li1[j] = rld_nt<OT>(R, KROW(s0 + j - E1, SR_C_I1), idx0);      // chain sources: read once
-        Ld1[j] = rld_nt<OT>(R, KROW(s0 + j - E1, SR_C_D1), idx0);
-    }
-    if (TWO) {
-#pragma unroll
-        for (int j = 0; j < N2; j++) {
-            Li2[j] = rld_nt<OT>(R, KROW(s0 + j - E2, SR_C_I2), idx0);
-            Ld2[j] = rld_nt<OT>(R, KROW(s0 + j - E2, SR_C_D2), idx0);
-        }
-    }
-    // U row (breakpoint detection filter): running max of the aligner's M offsets per diagonal
-    // (kept only while the search stores its I/D rows, i.e. in phase 2; the recompute pass builds it from the
-    // stored M rows of the scope window -- a superset bound of the window is all the filter needs)
-    const bool with_u = (chk < 0) && (R.urow != 0u) && rec;
-    {   // row traffic of this tile in 8-byte (int16) / 16-byte (int32) lane accesses: the kernel's algorithmic HBM bytes
-        // (bench.py roofline): every lane of the wave loads, the owned lanes store
-        const int nown = min(OWN, max(0, ghi - (glo + ti * OWN) + 1));
-        int nld = ((!IDONLY && !XK) ? B : 0) + (IDONLY ? B : 0) + B + (TWO ? B : 0) + 2 * N1 + (TWO ? 2 * N2 : 0) + ((with_u && s0 > 0) ? 1 : 0);
-        int nst = (IDONLY ? 0 : B) + (with_u ? 1 : 0);
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            nst += (j + E1 >= B || rec) ? 2 : 0;
-            if (TWO) nst += (j + E2 >= B || rec) ? 2 : 0;
-        }
-        row_ld += 64u * (unsigned)nld * (unsigned)(sizeof(ST) / 2); row_st += (unsigned)nown * (unsigned)nst * (unsigned)(sizeof(ST) / 2);
-    }
-    int uacc[4] = {NULLV, NULLV, NULLV, NULLV};
-    V4<OT> Lown[IDONLY ? B : 1];                           // recompute pass: the block's own (stored) M rows
-    if (IDONLY) {
-#pragma unroll
-        for (int j = 0; j < B; j++) Lown[IDONLY ? j : 0] = rld<OT>(R, KROW(s0 + j, SR_C_M), idx0);
-    }
-    if (with_u) {
-        const int gplo = RFL(k_sh.jgplo[tix]), gphi = RFL(k_sh.jgphi[tix]);
-        if (s0 > 0 && g >= gplo && g <= gphi) {
-            const V4<OT> u = rld<OT>(R, R.urow, idx0);
-#pragma unroll
-            for (int q = 0; q < 4; q++) uacc[q] = (int)u[q];
-        }
-    }
-    // Every negative offset is NULL to every reader (bounds, >= 0 tests, maxima); the cells computed here use -16, an
-    // inline constant of the ISA, instead of materialising SR_NULL_OFF (-8192, the value of the NULL rows) per select.
-#define KNULL (-16)
-#define KBND(C, L1) (((unsigned)(C) >= (L1)) ? KNULL : (C))      // L1 = bound + 1, or 0: nothing is a cell
-    int hI1[B][4], hD1[B][4], hI2[B][4], hD2[B][4];      // I/D cells of this block's levels (chain sources)
-    int mvh[XK ? B : 1][4];                              // exact instance: this lane's M cells of the block's levels
-#pragma unroll
-    for (int j = 0; j < B; j++) {
-        const int s = s0 + j;
-        const int klo = RFL(k_sh.jklo[j][tix]), khi = RFL(k_sh.jkhi[j][tix]);
-        if (TWO && XK && j + PF < B) Lmo2[j + PF < B ? j + PF : 0] = rld_nt<OT>(R, KROW(s0 + j + PF - pen.o2 - E2, SR_C_M), idx0);
-        int mx[4], mo1[4], mo2[4], si1[4], sd1[4], si2[4], sd2[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (IDONLY) mx[q] = NULLV;
-            else if (!XK) mx[q] = (int)Lmx[XK ? 0 : j][q];
-            else if (j >= X) mx[q] = mvh[(XK && j >= X) ? j - X : 0][q];                    // own M, x levels earlier
-            else mx[q] = (int)Lmo1[(XK && j + OE1 - X < B) ? j + OE1 - X : 0][q];           // row s0 + j - x
-            mo1[q] = (int)Lmo1[j][q];
-            if (j < N1) { si1[q] = (int)Li1[j < N1 ? j : 0][q]; sd1[q] = (int)Ld1[j < N1 ? j : 0][q]; }
-            else { si1[q] = hI1[j >= E1 ? j - E1 : 0][q]; sd1[q] = hD1[j >= E1 ? j - E1 : 0][q]; }
-            mo2[q] = si2[q] = sd2[q] = NULLV;
-            if (TWO) {
-                mo2[q] = (int)Lmo2[j][q];
-                if (j < N2) { si2[q] = (int)Li2[j < N2 ? j : 0][q]; sd2[q] = (int)Ld2[j < N2 ? j : 0][q]; }
-                else { si2[q] = hI2[j >= E2 ? j - E2 : 0][q]; sd2[q] = hD2[j >= E2 ? j - E2 : 0][q]; }
-            }
-        }
-        const int mo1L = lane_left(mo1[3]), mo1R = lane_right(mo1[0]);
-        const int i1L = lane_left(si1[3]), d1R = lane_right(sd1[0]);
-        int mo2L = NULLV, mo2R = NULLV, i2L = NULLV, d2R = NULLV;
-        if (TWO) { mo2L = lane_left(mo2[3]); mo2R = lane_right(mo2[0]); i2L = lane_left(si2[3]); d2R = lane_right(sd2[0]); }
-        int mv[4], i1v[4], i2v[4], d1v[4], d2v[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int k = k0 + q;
-            const bool inr = (k >= klo) && (k <= khi);
-            int m, i1, i2 = KNULL, d1, d2 = KNULL;
-            {
-                // cells of diagonal k: 0 <= offset <= min(tlen, plen + k); outside the level's range: none
-                const unsigned lim = inr ? (unsigned)(min(tlen, plen + k) + 1) : 0u;
-                const int a1 = (q == 0) ? mo1L : mo1[q == 0 ? 0 : q - 1];
-                const int b1 = (q == 0) ? i1L : si1[q == 0 ? 0 : q - 1];
-                const int c1 = (q == 3) ? mo1R : mo1[q == 3 ? 3 : q + 1];
-                const int f1 = (q == 3) ? d1R : sd1[q == 3 ? 3 : q + 1];
-                i1 = KBND(max(a1, b1) + 1, lim);
-                d1 = KBND(max(c1, f1), lim);
-                if (TWO) {
-                    const int a2 = (q == 0) ? mo2L : mo2[q == 0 ? 0 : q - 1];
-                    const int b2 = (q == 0) ? i2L : si2[q == 0 ? 0 : q - 1];
-                    const int c2 = (q == 3) ? mo2R : mo2[q == 3 ? 3 : q + 1];
-                    const int f2 = (q == 3) ? d2R : sd2[q == 3 ? 3 : q + 1];
-                    i2 = KBND(max(a2, b2) + 1, lim);
-                    d2 = KBND(max(c2, f2), lim);
-                }
-                m = KBND(mx[q] + 1, lim);
-                m = max(m, max(max(i1, i2), max(d1, d2)));
-            }
-            if (j == 0 && s0 == 0) {          // level 0: only the begin component's cell of diagonal 0 exists
-                const int z = (inr && k == 0) ? 0 : KNULL;
-                m = (begin == SR_C_M) ? z : KNULL; i1 = (begin == SR_C_I1) ? z : KNULL; i2 = (begin == SR_C_I2) ? z : KNULL;
-                d1 = (begin == SR_C_D1) ? z : KNULL; d2 = (begin == SR_C_D2) ? z : KNULL;
-            }
-            mv[q] = m; i1v[q] = i1; i2v[q] = i2; d1v[q] = d1; d2v[q] = d2;
-            hI1[j][q] = i1; hD1[j][q] = d1; hI2[j][q] = i2; hD2[j][q] = d2;
-        }
-        if (!IDONLY) {
-        // ---- extension of the owned M cells.  Reverse aligners walk the reverse-complement copies
-        // forward (equal bases <=> equal complements), so there is one code path; the first 16-base
-        // window of the four cells is branch-free, longer runs continue in one predicated loop.
-        // A cell at offset h of diagonal k compares P[p0 + h - k ..] with T[t0 + h ..]; at most L(k) - h symbols are left,
-        // L = min(tlen, plen + k) the cell's limit.  The eight window reads of the level are in flight together; a cell
-        // that does not extend (NULL, halo lane) reads wherever its coordinates point and adds nothing.
-        int more = 0;
-        if constexpr (sizeof(OT) == 2) {
-            uint32_t pl[4], ph[4], tl[4], th[4];
-            int sp[4], st[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                sp[q] = mv[q] + cp0 - q; st[q] = mv[q] + ct0;
-                win_words(sp[q], pl[q], ph[q]); win_words(st[q], tl[q], th[q]);
-            }
-            asm volatile("; 8 windows in flight" : "+v"(pl[0]), "+v"(ph[0]), "+v"(pl[1]), "+v"(ph[1]), "+v"(pl[2]), "+v"(ph[2]), "+v"(pl[3]), "+v"(ph[3]),
-                                                    "+v"(tl[0]), "+v"(th[0]), "+v"(tl[1]), "+v"(th[1]), "+v"(tl[2]), "+v"(th[2]), "+v"(tl[3]), "+v"(th[3]));
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const bool valid = owned && mv[q] >= 0;
-                const int nn = valid ? min(tlen, plen + k0 + q) - mv[q] : 0;
-                const uint32_t xw = __builtin_amdgcn_alignbit(ph[q], pl[q], (uint32_t)sp[q] << SR_SYM_LOG) ^
-                                    __builtin_amdgcn_alignbit(th[q], tl[q], (uint32_t)st[q] << SR_SYM_LOG);
-                mv[q] += (int)min3u(ffs_sym(xw), (unsigned)SR_WIN, (unsigned)nn);
-                more |= (xw == 0u && nn > SR_WIN) ? (1 << q) : 0;
-            }
-        } else {
-            // (32-bit rows: a row is four registers per lane, sixteen more for the windows of a level spill: cell by cell,
-            // every coordinate of a cell that does not extend forced to the sequences' first symbols)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const bool valid = owned && mv[q] >= 0;
-                const int h = valid ? mv[q] : 0, v = valid ? mv[q] - (k0 + q) : 0;
-                const int nn = valid ? min(plen - v, tlen - h) : 0;
-                const uint32_t xw = win_fwd(P, p0 + v) ^ win_fwd(T, t0 + h);
-                const unsigned z = (unsigned)(__ffs((int)xw) - 1) >> SR_SYM_LOG;          // 2^31-1 when the window is all equal
-                mv[q] += (int)min(min(z, (unsigned)SR_WIN), (unsigned)nn);
-                more |= (xw == 0u && nn > SR_WIN) ? (1 << q) : 0;
-            }
-        }
-        // runs longer than a window: the wave iterates, skipping the cell positions q no lane needs
-        unsigned long long pend[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) pend[q] = __ballot((more >> q) & 1);
-        while ((pend[0] | pend[1] | pend[2] | pend[3]) != 0ull) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if (pend[q] == 0ull) continue;
-                if constexpr (sizeof(OT) == 2) {
-                    const int nn = lanes_or_zero(pend[q], min(tlen, plen + k0 + q) - mv[q]);      // 0 for the lanes that are done
-                    const uint32_t xw = win_sym(mv[q] + cp0 - q) ^ win_sym(mv[q] + ct0);
-                    mv[q] += (int)min3u(ffs_sym(xw), (unsigned)SR_WIN, (unsigned)nn);
-                    pend[q] = __ballot(xw == 0u && nn > SR_WIN);
-                } else {
-                    const bool on = (more >> q) & 1;
-                    const int h = on ? mv[q] : 0, v = on ? mv[q] - (k0 + q) : 0;
-                    const int nn = on ? min(plen - v, tlen - h) : 0;
-                    const uint32_t xw = win_fwd(P, p0 + v) ^ win_fwd(T, t0 + h);
-                    const unsigned z = (unsigned)(__ffs((int)xw) - 1) >> SR_SYM_LOG;
-                    mv[q] += (int)min(min(z, (unsigned)SR_WIN), (unsigned)nn);
-                    if (!(xw == 0u && nn > SR_WIN)) more &= ~(1 << q);
-                    pend[q] = __ballot((more >> q) & 1);
-                }
-            }
-        }
-        int ak = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (XK) mvh[XK ? j : 0][q] = mv[q];
-            ak = max(ak, (owned && mv[q] >= 0) ? 2 * mv[q] - (k0 + q) : 0);
-            uacc[q] = max(uacc[q], mv[q]);
-            if (j == 0 && s0 == 0) uacc[q] = max(uacc[q], max(max(i1v[q], i2v[q]), max(d1v[q], d2v[q])));
-        }
-        if (chk >= 0) {                       // score-only / base-case aligners: has the end cell been reached?
-            bool reached = false;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int k = k0 + q;
-                int val = mv[q];
-                if (chk == SR_C_I1) val = i1v[q];
-                else if (chk == SR_C_I2) val = i2v[q];
-                else if (chk == SR_C_D1) val = d1v[q];
-                else if (chk == SR_C_D2) val = d2v[q];
-                reached |= owned && k == kend && k >= klo && k <= khi && val >= tlen;
-            }
-            if (reached) k_sh.jreach[j][jid] = 1;
-        }
-        ak = row16_max(ak);
-        if ((lane & 15) == 15 && ak > 0) atomicMax(&k_sh.jak[j][jid], ak);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                uacc[q] = max(uacc[q], (int)Lown[IDONLY ? j : 0][q]);
-                if (j == 0 && s0 == 0) uacc[q] = max(uacc[q], max(max(i1v[q], i2v[q]), max(d1v[q], d2v[q])));
-            }
-        }
-        if (owned) {
-            V4<OT> oM, oI1, oI2, oD1, oD2;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                oM[q] = (OT)mv[q]; oI1[q] = (OT)i1v[q]; oI2[q] = (OT)i2v[q]; oD1[q] = (OT)d1v[q]; oD2[q] = (OT)d2v[q];
-            }
-            // The I/D rows of all but the block's last e levels are read again only by breakpoint detection: a
-            // search in phase 1 does not store them at all (rec == 0); when it enters phase 2 the rows of the scope
-            // window are recomputed from the M rows (blk_recompute) and from then on stored (streaming).
-            if (!IDONLY) rst<OT>(R, KROW(s, SR_C_M), idx0, oM);
-            if (j + E1 < B) { if (rec) { rst_nt<OT>(R, KROW(s, SR_C_I1), idx0, oI1); rst_nt<OT>(R, KROW(s, SR_C_D1), idx0, oD1); } }
-            else { rst<OT>(R, KROW(s, SR_C_I1), idx0, oI1); rst<OT>(R, KROW(s, SR_C_D1), idx0, oD1); }
-            if (TWO) {
-                if (j + E2 < B) { if (rec) { rst_nt<OT>(R, KROW(s, SR_C_I2), idx0, oI2); rst_nt<OT>(R, KROW(s, SR_C_D2), idx0, oD2); } }
-                else { rst<OT>(R, KROW(s, SR_C_I2), idx0, oI2); rst<OT>(R, KROW(s, SR_C_D2), idx0, oD2); }
-            }
-        }
-    }
-    if (with_u && owned) {
-        V4<OT> u;
-#pragma unroll
-        for (int q = 0; q < 4; q++) u[q] = (OT)uacc[q];
-        rst<OT>(R, R.urow, idx0, u);
-    }
-#undef KROW
-#undef KBND
-#undef KNULL
-}
-
-// ---- packed 16-bit tile (int16 rows) --------------------------------------------------------------------------
-// Same tile, same rows, same results as blk_tile<short, ...>; the I/D chains, the M maximum, the limit tests and the
-// histories stay in the rows' own format -- two 16-bit cells per register (v_pk_max_i16 / v_pk_add_u16 / ...) -- so a
-// level costs half the chain instructions and none of the per-cell unpack / repack of the 32-bit version.  Only the
-// extension (sequence comparison) and the antidiagonal maximum work on 32-bit cells.
-//  * neighbours: the k-1 / k+1 cells of a register pair are one DPP lane shift + two v_alignbit.
-//  * limit test: a cell above its limit L becomes NULL16 via sat(L - v) >> 15 (three instructions per pair); cells
-//    outside the level's diagonal range get L = -32768, which sends every value there.  Negative inputs pass
-//    through; every cell outside the range or beyond the matrix is reset to NULL16 at every level, so a NULL can only
-//    creep upwards (+1 per chain step) through the few unreachable in-range cells of the first levels.
-typedef short __attribute__((ext_vector_type(2))) H2;
-struct Q4 { H2 a, b; };                                   // cells 0,1 | 2,3 of a lane's group
-#define NULL16 0xC000C000u                                // (-16384, -16384)
-__device__ __forceinline__ H2 h2_bits(uint32_t u) { return __builtin_bit_cast(H2, u); }
-__device__ __forceinline__ uint32_t h2_u(H2 h) { return __builtin_bit_cast(uint32_t, h); }
-__device__ __forceinline__ H2 h2_pack(int lo, int hi) { return h2_bits(((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16)); }
-__device__ __forceinline__ H2 h2_pack_perm(int lo, int hi) { return h2_bits(__builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u)); }   // one v_perm_b32
-__device__ __forceinline__ Q4 q4_from(V4<short> v) {
-    Q4 r; r.a = __builtin_shufflevector(v, v, 0, 1); r.b = __builtin_shufflevector(v, v, 2, 3); return r;
-}
-__device__ __forceinline__ V4<short> q4_vec(Q4 q) { return __builtin_shufflevector(q.a, q.b, 0, 1, 2, 3); }
-__device__ __forceinline__ Q4 q4_null() { Q4 r; r.a = h2_bits(NULL16); r.b = h2_bits(NULL16); return r; }
-__device__ __forceinline__ Q4 q4_max(Q4 x, Q4 y) {
-    Q4 r; r.a = __builtin_elementwise_max(x.a, y.a); r.b = __builtin_elementwise_max(x.b, y.b); return r;
-}
-__device__ __forceinline__ Q4 q4_inc(Q4 x) { const H2 one = {1, 1}; Q4 r; r.a = x.a + one; r.b = x.b + one; return r; }
-// cell of diagonal k-1 for every cell of the group: [left lane's cell 3, c0, c1, c2]; k+1: [c1, c2, c3, right lane's cell 0]
-__device__ __forceinline__ Q4 q4_from_left(Q4 x) {
-    // (zero fill at the wave's ends: those lanes are halo, see KGeo)
-    const uint32_t L = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h2_u(x.b), 0x138, 0xf, 0xf, true);
-    Q4 r;
-    r.a = h2_bits(__builtin_amdgcn_alignbit(h2_u(x.a), L, 16));
-    r.b = h2_bits(__builtin_amdgcn_alignbit(h2_u(x.b), h2_u(x.a), 16));
-    return r;
-}
-__device__ __forceinline__ Q4 q4_from_right(Q4 x) {
-    const uint32_t R = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h2_u(x.a), 0x130, 0xf, 0xf, true);
-    Q4 r;
-    r.a = h2_bits(__builtin_amdgcn_alignbit(h2_u(x.b), h2_u(x.a), 16));
-    r.b = h2_bits(__builtin_amdgcn_alignbit(R, h2_u(x.b), 16));
-    return r;
-}
-template <uint32_t NUL = NULL16>
-__device__ __forceinline__ Q4 q4_bound(Q4 v, Q4 L) {
-    // (inline assembly: written as C the compiler turns the three instructions per register back into two 16-bit
-    // compares and two selects, and between separate asm statements it pads with s_nop)
-    uint32_t ta, tb, ra, rb;
-    const uint32_t nul = NUL;
-    asm("v_pk_sub_i16 %0, %4, %6 clamp\n\t"
-        "v_pk_sub_i16 %1, %5, %7 clamp\n\t"
-        "v_pk_ashrrev_i16 %0, 15, %0 op_sel_hi:[0,1]\n\t"
-        "v_pk_ashrrev_i16 %1, 15, %1 op_sel_hi:[0,1]\n\t"
-        "v_bfi_b32 %2, %0, %8, %6\n\t"
-        "v_bfi_b32 %3, %1, %8, %7"
-        : "=&v"(ta), "=&v"(tb), "=&v"(ra), "=&v"(rb)
-        : "v"(h2_u(L.a)), "v"(h2_u(L.b)), "v"(h2_u(v.a)), "v"(h2_u(v.b)), "s"(nul));
-    Q4 r; r.a = h2_bits(ra); r.b = h2_bits(rb);
-    return r;
-}
-// cells below offset 0 (stored value < -BIAS) become exactly NULL again.  The packed chains let negatives pass (only "above
-// the limit" is tested), and a NULL creeps: +1 per chain step, up to +17 per M step once the extension has run over it (its
-// windows usually lie outside the LDS allocation, read 0 on both sides and "match" 16 symbols).  On diagonals that have run
-// off the matrix nothing real ever overrides it again, so after thousands of levels a NULL would cross into the valid range
-// (margin 16384 for int16 rows, 8192 for the 16-bit ring of 32-bit searches: ~4 800 / ~2 400 levels at 17 per 5 levels) and
-// be extended, stored and tested for overlaps like a cell (round 4: found by the bounds-checked build -- an LDS window of a
-// "live" cell 2 KB in front of the sequences -- on a 50 kb pair of score > 16 000; C5's mean score is 15 000).  Tiles of
-// deep levels (`deep`, uniform) therefore reset the sources a block takes its chains up from when they are loaded: the
-// creep of a chain is then bounded by one block.
-template <uint32_t NUL, int BIAS>
-__device__ __forceinline__ Q4 q4_renull(Q4 v) {
-    uint32_t ta, tb, ra, rb;
-    const uint32_t nul = NUL;
-    if constexpr (BIAS == 0) {
-        asm("v_pk_ashrrev_i16 %0, 15, %4 op_sel_hi:[0,1]\n\t"
-            "v_pk_ashrrev_i16 %1, 15, %5 op_sel_hi:[0,1]\n\t"
-            "v_bfi_b32 %2, %0, %6, %4\n\t"
-            "v_bfi_b32 %3, %1, %6, %5"
-            : "=&v"(ta), "=&v"(tb), "=&v"(ra), "=&v"(rb)
-            : "v"(h2_u(v.a)), "v"(h2_u(v.b)), "s"(nul));
-    } else {
-        const uint32_t bias2 = ((uint32_t)BIAS & 0xffffu) | ((uint32_t)BIAS << 16);
-        asm("v_pk_add_i16 %0, %4, %7 clamp\n\t"
-            "v_pk_add_i16 %1, %5, %7 clamp\n\t"
-            "v_pk_ashrrev_i16 %0, 15, %0 op_sel_hi:[0,1]\n\t"
-            "v_pk_ashrrev_i16 %1, 15, %1 op_sel_hi:[0,1]\n\t"
-            "v_bfi_b32 %2, %0, %6, %4\n\t"
-            "v_bfi_b32 %3, %1, %6, %5"
-            : "=&v"(ta), "=&v"(tb), "=&v"(ra), "=&v"(rb)
-            : "v"(h2_u(v.a)), "v"(h2_u(v.b)), "s"(nul), "v"(bias2));
-    }
-    Q4 r; r.a = h2_bits(ra); r.b = h2_bits(rb);
-    return r;
-}
-#ifndef SR_DEEP_INT16
-#define SR_DEEP_INT16 3000         // first level whose tiles reset creeping NULLs: int16 rows (creep <= 3.4 per level: 10 200 of the 16 384 margin)
-#define SR_DEEP_RING16 1500        // ... the 16-bit ring of 32-bit searches (5 100 of 8 192)
-#endif
-__device__ __forceinline__ int q4_get(Q4 x, int q) {       // q compile-time
-    return (q == 0) ? (int)x.a.x : (q == 1) ? (int)x.a.y : (q == 2) ? (int)x.b.x : (int)x.b.y;
-}
-
-// KR / BIAS: the rows' container and what a stored cell is short of its offset -- KRows<short>, 0: int16 searches;
-// KRows<int, uint16_t>, SR_RING_BIAS: the 16-bit ring of a 32-bit search (cell = offset - 24576, NULL = -32768; round 4:
-// C5's ring tiles ran the 32-bit tile with a conversion at every load and store).  Everything packed works on the stored
-// values; what looks at an offset -- limits, window addresses, validity, the antidiagonal -- carries the bias as a constant.
-template <bool TWO, int B, int E1, int E2, bool IDONLY = false, int X = 0, int OE1 = 0, bool RING = false, typename KR = KRows<short>, int BIAS = 0>
-__device__ __forceinline__ void blk_tile16(const KR &R, const int s0, const int slot0, const SrPen &pen,
-                                           const int jid, const int ti, const int tix, unsigned &row_ld, unsigned &row_st, const int mrg = 0) {
-    typedef short OT;
-    typedef short ST;
-    static_assert(BIAS == 0 || (RING && X > 0 && B % 10 == 0 && SR_IMM_ROWS), "the biased tile exists for ring rows with immediate addressing only");
-    constexpr uint32_t NUL = BIAS ? 0x80008000u : NULL16;          // two NULL cells
-    constexpr int NULC = BIAS ? -32768 : -16384;                  // one NULL cell
-    const Q4 nulq = {h2_bits(NUL), h2_bits(NUL)};
-    constexpr int N1 = E1 < B ? E1 : B, N2 = E2 < B ? E2 : B;
-    constexpr bool XK = X > 0;
-    static_assert(!XK || (B == OE1 && X <= B), "exact-penalty instance: block depth == o1 + e1 >= x");
-    constexpr int HL = KGeo<B>::HL, OWN = KGeo<B>::OWN;
-    constexpr int PF = XK ? 3 : B;
-    const int lane = threadIdx.x & 63;
-    const BJob &jb = b_sh.job[jid];
-    // Merged tile (round 4, blk_setup decides): the two aligners of a segment -- jid and jid + 1, same lengths, begin
-    // component, level ranges and window, hence the same last tile index and remainder -- put their last tiles into the two
-    // halves of this wave when the remainder fits 32 - 2 HL groups.  The rows are shared and the halves differ in what is
-    // per lane anyway: the aligner's columns (idx0), its sequence windows (cp0 / ct0), and the max_ak slot of the lane's row of
-    // sixteen.  Each half keeps HL halo lanes on either side, so what the DPP shifts carry across lane 31 | 32 ends in halo lanes.
-    const bool mg = RING && !IDONLY && SR_MERGE_TAILS && mrg != 0;
-    const int half = mg ? (lane >> 5) : 0, l32 = mg ? (lane & 31) : lane, wl = mg ? 32 : 64;
-    int base = RFL(jb.base), p0 = RFL(jb.p0), t0 = RFL(jb.t0), poff = RFL(jb.poff), toff = RFL(jb.pad0);
-    const int shift = RFL(jb.shift), plen = RFL(jb.plen), tlen = RFL(jb.tlen), begin = RFL(jb.begin);
-    const int chk = RFL(jb.chk), kend = RFL(jb.kend);
-    if (mg) {
-        const BJob &j2 = b_sh.job[jid + 1];
-        const int base2 = RFL(j2.base), p02 = RFL(j2.p0), t02 = RFL(j2.t0), poff2 = RFL(j2.poff), toff2 = RFL(j2.pad0);
-        base = half ? base2 : base; p0 = half ? p02 : p0; t0 = half ? t02 : t0; poff = half ? poff2 : poff; toff = half ? toff2 : toff;
-    }
-    const int jid_l = jid + half;                        // the aligner this lane works for
-    const bool rec = IDONLY || RFL(jb.pad2) != 0;
-    const int glo = RFL(k_sh.jglo[tix]), ghi = RFL(k_sh.jghi[tix]);
-    const int g = glo + ti * OWN + l32 - HL;
-    const bool owned = (l32 >= HL) && (l32 < wl - HL) && (g <= ghi);
-    const int k0 = (g << 2) - shift;
-    const unsigned idx0 = klane(R, (unsigned)(base + (g << 2)));      // lane part of the row addresses
-    const LP P = (LP)(lds_seq + poff), T = (LP)(lds_seq + toff);
-    const KAdr A = kadr(R, jb, slot0);
-#define KROW(LVL, C) krow_rel(R, A, s0, (LVL), (C))
-#define LDQ(LVL, C) q4_from(rld<OT>(R, KROW((LVL), (C)), idx0))
-#define LDQ_NT(LVL, C) q4_from(rld_nt<OT>(R, KROW((LVL), (C)), idx0))
-    // immediate-offset addressing (see kbase): ring rows of the exact instance whose second gap piece sits a multiple of
-    // five levels back (the host sends other penalties to the generic instance)
-    constexpr bool IMMR = RING && XK && (B % 10 == 0) && SR_IMM_ROWS;
-    const unsigned lane_b = idx0 * (unsigned)sizeof(ST);
-    // bases (uniform): the block below (its M rows feed levels 0..9 as M[s - o1 - e1] and 0..x-1 as M[s - x]), the two
-    // five-level runs of M[s - o2 - e2], the chain-source rows of the four gap components, this block's rows
-    GPB bM1 = nullptr, bM2a = nullptr, bM2b = nullptr, bI1 = nullptr, bD1 = nullptr, bI2 = nullptr, bD2 = nullptr;
-    GPB sM = nullptr, sI1 = nullptr, sD1 = nullptr, sI2 = nullptr, sD2 = nullptr;
-    if constexpr (IMMR) {
-        const int oe2 = pen.o2 + E2;
-        bM1 = kbase(R, s0 - B < 0 ? R.nuloff + KBLK_C * 256u : KROW(s0 - B + KBLK_C, SR_C_M));
-        bM2a = kbase(R, KROW(s0 - oe2, SR_C_M)); bM2b = kbase(R, KROW(s0 - oe2 + 5, SR_C_M));
-        bI1 = kbase(R, KROW(s0 - E1, SR_C_I1)); bD1 = kbase(R, KROW(s0 - E1, SR_C_D1));
-        bI2 = kbase(R, KROW(s0 - E2, SR_C_I2)); bD2 = kbase(R, KROW(s0 - E2, SR_C_D2));
-        sM = kbase(R, KROW(s0 + KBLK_C, SR_C_M));
-        sI1 = kbase(R, KROW(s0 + KBLK_C, SR_C_I1)); sD1 = kbase(R, KROW(s0 + KBLK_C, SR_C_D1));
-        sI2 = kbase(R, KROW(s0 + KBLK_C, SR_C_I2)); sD2 = kbase(R, KROW(s0 + KBLK_C, SR_C_D2));
-    }
-    // TIGHT coverage (kwindow): lanes outside the coverage of a source block would read cells nobody wrote -> they hold NULL
-    // instead and -- round 4b -- do not load at all.  The source blocks: s0 - B (M[s - o1 - e1] / M[s - x] rows and the chain
-    // sources) and the blocks the two five-level runs of M[s - o2 - e2] come from; blocks below level 0 are the NULL rows.
-    // Coverages are nested (older = narrower): a tile whose 64 lanes lie inside the oldest one (`msk == false`, most tiles
-    // of a wide search) loads every lane as before; an edge tile loads under the lanes' masks -- the last tile of an
-    // aligner covers half a tile's groups on average, and its other lanes' loads were 12 % of the kernel's row bytes.
-    constexpr bool TIGHT = IMMR && (BIAS ? (bool)(SR_TIGHT && SR_IMM_ROWS) : (bool)KTIGHT_OF(short, short, B, X));
-    bool msk = false, in10 = true, in2a = true, in2b = true;
-    if constexpr (TIGHT) {
-        const int oe2 = TWO ? pen.o2 + E2 : B;
-        const int l2a = s0 - oe2, l2b = s0 - oe2 + 5;                                      // first levels of the two runs (multiples of 5)
-        const int b2a = l2a >= 0 ? (l2a / B) * B : -1, b2b = l2b >= 0 ? (l2b / B) * B : -1;      // their blocks (-1: NULL rows)
-        int lo10 = INT_MIN / 2, hi10 = INT_MAX / 2, lo2a = lo10, hi2a = hi10, lo2b = lo10, hi2b = hi10;
-        if (s0 - B >= 0) kwindow<TWO, B, E1, E2, true>(pen, jb, s0 - B, lo10, hi10);
-        if (TWO && b2a >= 0) kwindow<TWO, B, E1, E2, true>(pen, jb, b2a, lo2a, hi2a);
-        if (TWO && b2b >= 0) kwindow<TWO, B, E1, E2, true>(pen, jb, b2b, lo2b, hi2b);
-        lo10 = RFL(lo10); hi10 = RFL(hi10); lo2a = RFL(lo2a); hi2a = RFL(hi2a); lo2b = RFL(lo2b); hi2b = RFL(hi2b);
-        in10 = g >= lo10 && g <= hi10; in2a = g >= lo2a && g <= hi2a; in2b = g >= lo2b && g <= hi2b;
-        msk = __builtin_amdgcn_ballot_w64(!(in10 && in2a && in2b)) != 0ull;
-    }
-    Q4 Lmx[XK ? 1 : B], Lmo1[B], Lmo2[B], Li1[N1], Ld1[N1], Li2[N2], Ld2[N2];
-    unsigned ld_lanes10 = 64u, ld_lanes2 = 64u;              // lanes that load from block s0 - B / from the first M[s - o2 - e2] rows (byte count)
-    if (TIGHT && msk && SR_MASKED_LOADS) {
-        // edge tile: NULL everywhere, loads under the lanes' masks
-#pragma unroll
-        for (int j = 0; j < B; j++) { Lmo1[j] = nulq; Lmo2[j] = nulq; }
-#pragma unroll
-        for (int j = 0; j < N1; j++) { Li1[j] = nulq; Ld1[j] = nulq; }
-#pragma unroll
-        for (int j = 0; j < N2; j++) { Li2[j] = nulq; Ld2[j] = nulq; }
-        if constexpr (IMMR) {
-            if (in10) {
-#pragma unroll
-                for (int j = 0; j < B; j++) Lmo1[j] = q4_from(ild<OT, ST>(R, bM1, lane_b, j - KBLK_C));
-#pragma unroll
-                for (int j = 0; j < N1; j++) { Li1[j] = q4_from(ild_nt<OT, ST>(R, bI1, lane_b, j)); Ld1[j] = q4_from(ild_nt<OT, ST>(R, bD1, lane_b, j)); }
-                if (TWO) {
-#pragma unroll
-                    for (int j = 0; j < N2; j++) { Li2[j] = q4_from(ild_nt<OT, ST>(R, bI2, lane_b, j)); Ld2[j] = q4_from(ild_nt<OT, ST>(R, bD2, lane_b, j)); }
-                }
-            }
-            if (TWO && in2a) {                                // (PF = 3 < 5: the first rows all come from the first run)
-#pragma unroll
-                for (int j = 0; j < PF && j < 5; j++) Lmo2[j] = q4_from(ild_nt<OT, ST>(R, bM2a, lane_b, j));
-            }
-        }
-        ld_lanes10 = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(in10)); ld_lanes2 = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(in2a));
-    } else {
-#pragma unroll
-    for (int j = 0; j < B; j++) {
-        if constexpr (!IDONLY && !XK) Lmx[XK ? 0 : j] = LDQ(s0 + j - pen.x, SR_C_M);
-        if constexpr (IMMR) {
-            Lmo1[j] = q4_from(ild<OT, ST>(R, bM1, lane_b, j - KBLK_C));
-            if (TWO && j < PF) Lmo2[j] = q4_from(ild_nt<OT, ST>(R, j < 5 ? bM2a : bM2b, lane_b, j < 5 ? j : j - 5));
-        } else {
-            Lmo1[j] = LDQ(s0 + j - pen.o1 - E1, SR_C_M);
-            if (TWO && j < PF) Lmo2[j] = LDQ_NT(s0 + j - pen.o2 - E2, SR_C_M);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < N1; j++) {
-        if constexpr (IMMR) {
-            Li1[j] = q4_from(ild_nt<OT, ST>(R, bI1, lane_b, j)); Ld1[j] = q4_from(ild_nt<OT, ST>(R, bD1, lane_b, j));
-        } else {
-            Li1[j] = LDQ_NT(s0 + j - E1, SR_C_I1);
-            Ld1[j] = LDQ_NT(s0 + j - E1, SR_C_D1);
-        }
-    }
-    if (TWO) {
-#pragma unroll
-        for (int j = 0; j < N2; j++) {
-            if constexpr (IMMR) {
-                Li2[j] = q4_from(ild_nt<OT, ST>(R, bI2, lane_b, j)); Ld2[j] = q4_from(ild_nt<OT, ST>(R, bD2, lane_b, j));
-            } else {
-                Li2[j] = LDQ_NT(s0 + j - E2, SR_C_I2);
-                Ld2[j] = LDQ_NT(s0 + j - E2, SR_C_D2);
-            }
-        }
-    }
-    }
-    const bool with_u = (chk < 0) && (R.urow != 0u) && rec;
-    {   // row traffic of this tile (see blk_tile): lane accesses really made
-        const int nown = min(OWN, max(0, ghi - (glo + ti * OWN) + 1)) * (mg ? 2 : 1);
-        const int n10 = ((!IDONLY && !XK) ? B : 0) + B + 2 * N1 + (TWO ? 2 * N2 : 0);          // rows of block s0 - B (and M[s - x] rows of the generic instance)
-        const int n2f = TWO ? (PF < B ? PF : B) : 0, n2p = TWO ? B - n2f : 0;                    // M[s - o2 - e2]: first rows, rows prefetched inside the level loop (all lanes)
-        int nst = (IDONLY ? 0 : B) + (with_u ? 1 : 0);
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            nst += (j + E1 >= B || rec) ? 2 : 0;
-            if (TWO) nst += (j + E2 >= B || rec) ? 2 : 0;
-        }
-        row_ld += ld_lanes10 * (unsigned)n10 + ld_lanes2 * (unsigned)n2f + 64u * (unsigned)(n2p + (IDONLY ? B : 0) + ((with_u && s0 > 0) ? 1 : 0));
-        row_st += (unsigned)nown * (unsigned)nst;
-    }
-#if defined(SR_INJECT_VALU) || defined(SR_INJECT_LOADS)
-    // Sensitivity builds (scripts/build_variant.sh, never shipped): what does the kernel's time follow?  SR_INJECT_VALU=K adds K
-    // dependent integer VALU instructions to every level of every ring tile (no memory, no extra live registers but one);
-    // SR_INJECT_LOADS=K makes every ring tile load K more rows -- M rows written four blocks earlier, cold in the L2 -- and
-    // folds them into the same register.  Results are unchanged (the register ends in an empty asm statement).
-    unsigned inj = (unsigned)lane;
-#endif
-#ifdef SR_INJECT_LOADS
-    if constexpr (RING && !IDONLY) {
-        if (s0 >= 5 * B) {
-#pragma unroll
-            for (int j = 0; j < SR_INJECT_LOADS; j++) {
-                const V4<OT> v = rld_nt<OT>(R, KROW(s0 - 4 * B - j, SR_C_M), idx0);
-                inj += (unsigned)(int)v[0] ^ (unsigned)(int)v[3];
-            }
-            row_ld += 64u * (unsigned)SR_INJECT_LOADS;
-        }
-    }
-#endif
-    Q4 uacc = nulq;
-    Q4 Lown[IDONLY ? B : 1];
-    if (IDONLY) {
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            if constexpr (IMMR) Lown[IDONLY ? j : 0] = q4_from(ild<OT, ST>(R, sM, lane_b, j - KBLK_C));
-            else Lown[IDONLY ? j : 0] = LDQ(s0 + j, SR_C_M);
-        }
-    }
-    if (with_u) {
-        const int gplo = RFL(k_sh.jgplo[tix]), gphi = RFL(k_sh.jgphi[tix]);
-        if (s0 > 0 && g >= gplo && g <= gphi) uacc = q4_from(rld_raw16(R, R.urow, idx0));
-    }
-    if (TIGHT && msk && !SR_MASKED_LOADS) {                  // (A/B builds: every lane loaded, then masked)
-        const Q4 nq = nulq;
-#pragma unroll
-        for (int j = 0; j < B; j++) { Lmo1[j].a = in10 ? Lmo1[j].a : nq.a; Lmo1[j].b = in10 ? Lmo1[j].b : nq.b; }
-#pragma unroll
-        for (int j = 0; j < N1; j++) {
-            Li1[j].a = in10 ? Li1[j].a : nq.a; Li1[j].b = in10 ? Li1[j].b : nq.b; Ld1[j].a = in10 ? Ld1[j].a : nq.a; Ld1[j].b = in10 ? Ld1[j].b : nq.b;
-        }
-        if (TWO) {
-#pragma unroll
-            for (int j = 0; j < N2; j++) {
-                Li2[j].a = in10 ? Li2[j].a : nq.a; Li2[j].b = in10 ? Li2[j].b : nq.b; Ld2[j].a = in10 ? Ld2[j].a : nq.a; Ld2[j].b = in10 ? Ld2[j].b : nq.b;
-            }
-#pragma unroll
-            for (int j = 0; j < PF; j++) {
-                const bool in_ = j < 5 ? in2a : in2b;
-                Lmo2[j].a = in_ ? Lmo2[j].a : nq.a; Lmo2[j].b = in_ ? Lmo2[j].b : nq.b;
-            }
-        }
-    }
-    // deep levels: creeping NULLs are reset (q4_renull) where a block takes its chains up -- the M[s - x] sources of the
-    // block's first levels and the gap chains' sources -- under ONE uniform branch per tile (nothing per level: the
-    // level code is not duplicated).  An M chain then creeps at most two steps (34) and a gap chain ten before the next reset.
-    const bool deep = s0 >= (BIAS ? SR_DEEP_RING16 : SR_DEEP_INT16);
-    if (deep) {
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            if (XK) { if (j + OE1 - X < B && j + OE1 - X >= 0 && j < X) Lmo1[(XK && j + OE1 - X < B) ? j + OE1 - X : 0] = q4_renull<NUL, BIAS>(Lmo1[(XK && j + OE1 - X < B) ? j + OE1 - X : 0]); }
-            else if (!IDONLY) Lmx[XK ? 0 : j] = q4_renull<NUL, BIAS>(Lmx[XK ? 0 : j]);
-        }
-#pragma unroll
-        for (int j = 0; j < N1; j++) { Li1[j] = q4_renull<NUL, BIAS>(Li1[j]); Ld1[j] = q4_renull<NUL, BIAS>(Ld1[j]); }
-        if (TWO) {
-#pragma unroll
-            for (int j = 0; j < N2; j++) { Li2[j] = q4_renull<NUL, BIAS>(Li2[j]); Ld2[j] = q4_renull<NUL, BIAS>(Ld2[j]); }
-        }
-    }
-    const unsigned long long st0_ = ST_NOW();
-    ST_DRAIN();
-    const unsigned long long st1_ = ST_NOW();
-    // limits of the lane's four diagonals: 0 <= offset <= min(tlen, plen + k), none when that is negative
-    Q4 Lb;
-    {
-        int l[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) l[q] = max(min(tlen, plen + k0 + q), -1) - BIAS;
-        Lb.a = h2_pack(l[0], l[1]); Lb.b = h2_pack(l[2], l[3]);
-    }
-    // symbol index (LDS-wide: 16 / 8 / 4 symbols per word from LDS address 0) of P[p0 - k0] and T[t0]
-    // (a stored cell is offset - BIAS: the constants carry the bias)
-    const int cp0 = p0 - k0 + BIAS + (int)(((uint32_t)(uintptr_t)P >> 2) << SR_WIN_LOG);
-    const int ct0 = t0 + BIAS + (int)(((uint32_t)(uintptr_t)T >> 2) << SR_WIN_LOG);
-    // the same as bit indices, per cell of the lane (P: cell q sits on diagonal k0 + q), and the owned lanes as a mask
-    const int cpb0 = cp0 << SR_SYM_LOG, cpb1 = (cp0 - 1) << SR_SYM_LOG, cpb2 = (cp0 - 2) << SR_SYM_LOG, cpb3 = (cp0 - 3) << SR_SYM_LOG;
-    const int ctb = ct0 << SR_SYM_LOG;
-    const unsigned long long ownb = __builtin_amdgcn_ballot_w64(owned);
-    Q4 kk;                                               // the lane's diagonals
-    kk.a = h2_pack(k0, k0 + 1); kk.b = h2_pack(k0 + 2, k0 + 3);
-    // the ranges of a block's levels are nested (level 0 the narrowest): a tile inside level 0's range needs no range masks
-    const int klo0 = RFL(k_sh.jklo[0][tix]), khi0 = RFL(k_sh.jkhi[0][tix]);
-    const bool inside = __builtin_amdgcn_ballot_w64(!(k0 >= klo0 && k0 + 3 <= khi0)) == 0ull;
-    Q4 hI1[B], hD1[B], hI2[B], hD2[B], mvh[XK ? B : 1];
-#pragma unroll
-    for (int j = 0; j < B; j++) {
-        const int s = s0 + j;
-        int klo = 0, khi = 0;                              // (only edge tiles and base-case aligners look at the level's range)
-        if (!inside || chk >= 0 || (j == 0 && s0 == 0)) { klo = RFL(k_sh.jklo[j][tix]); khi = RFL(k_sh.jkhi[j][tix]); }
-        if (TWO && XK && j + PF < B) {
-            if constexpr (IMMR) Lmo2[j + PF < B ? j + PF : 0] = q4_from(ild_nt<OT, ST>(R, j + PF < 5 ? bM2a : bM2b, kopaque_v(lane_b), j + PF < 5 ? j + PF : j + PF - 5));
-            else Lmo2[j + PF < B ? j + PF : 0] = LDQ_NT(s0 + j + PF - pen.o2 - E2, SR_C_M);
-        }
-        if (TIGHT && TWO && msk && j >= PF) {            // (the row prefetched PF levels ago, used by this level: same mask as the first ones)
-            const bool in_ = j < 5 ? in2a : in2b;
-            const Q4 nq = nulq;
-            Lmo2[j].a = in_ ? Lmo2[j].a : nq.a; Lmo2[j].b = in_ ? Lmo2[j].b : nq.b;
-        }
-        const unsigned lane_j = IMMR ? kopaque_v(lane_b) : 0u;
-        Q4 Lj = Lb;
-        if (!inside) {
-            int l[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) { const int k = k0 + q; l[q] = (k >= klo && k <= khi) ? q4_get(Lb, q) : -32768; }
-            Lj.a = h2_pack(l[0], l[1]); Lj.b = h2_pack(l[2], l[3]);
-        }
-        Q4 mx, mo1 = Lmo1[j], si1, sd1, mo2 = nulq, si2 = nulq, sd2 = nulq;
-        if (IDONLY) mx = nulq;
-        else if (!XK) mx = Lmx[XK ? 0 : j];
-        else if (j >= X) mx = mvh[(XK && j >= X) ? j - X : 0];
-        else mx = Lmo1[(XK && j + OE1 - X < B) ? j + OE1 - X : 0];
-        if (j < N1) { si1 = Li1[j < N1 ? j : 0]; sd1 = Ld1[j < N1 ? j : 0]; }
-        else { si1 = hI1[j >= E1 ? j - E1 : 0]; sd1 = hD1[j >= E1 ? j - E1 : 0]; }
-        if (TWO) {
-            mo2 = Lmo2[j];
-            if (j < N2) { si2 = Li2[j < N2 ? j : 0]; sd2 = Ld2[j < N2 ? j : 0]; }
-            else { si2 = hI2[j >= E2 ? j - E2 : 0]; sd2 = hD2[j >= E2 ? j - E2 : 0]; }
-        }
-        Q4 i1 = q4_bound<NUL>(q4_inc(q4_from_left(q4_max(mo1, si1))), Lj);
-        Q4 d1 = q4_bound<NUL>(q4_from_right(q4_max(mo1, sd1)), Lj);
-        Q4 i2 = nulq, d2 = nulq;
-        if (TWO) {
-            i2 = q4_bound<NUL>(q4_inc(q4_from_left(q4_max(mo2, si2))), Lj);
-            d2 = q4_bound<NUL>(q4_from_right(q4_max(mo2, sd2)), Lj);
-        }
-        Q4 m = q4_bound<NUL>(q4_inc(mx), Lj);
-        m = TWO ? q4_max(m, q4_max(q4_max(i1, i2), q4_max(d1, d2))) : q4_max(m, q4_max(i1, d1));
-        if (j == 0 && s0 == 0) {              // level 0: only the begin component's cell of diagonal 0 exists
-            int z[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) { const int k = k0 + q; z[q] = (k == 0 && k >= klo && k <= khi) ? -BIAS : NULC; }
-            // (selects on the 32-bit halves: a conditional on the struct would go through the stack)
-            const H2 za = h2_pack(z[0], z[1]), zb = h2_pack(z[2], z[3]), nh = h2_bits(NUL);
-            m.a = (begin == SR_C_M) ? za : nh; m.b = (begin == SR_C_M) ? zb : nh;
-            i1.a = (begin == SR_C_I1) ? za : nh; i1.b = (begin == SR_C_I1) ? zb : nh;
-            i2.a = (begin == SR_C_I2) ? za : nh; i2.b = (begin == SR_C_I2) ? zb : nh;
-            d1.a = (begin == SR_C_D1) ? za : nh; d1.b = (begin == SR_C_D1) ? zb : nh;
-            d2.a = (begin == SR_C_D2) ? za : nh; d2.b = (begin == SR_C_D2) ? zb : nh;
-        }
-        hI1[j] = i1; hD1[j] = d1; hI2[j] = i2; hD2[j] = d2;
-        if (!IDONLY) {
-            int mv[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) mv[q] = q4_get(m, q);
-            // A cell at offset h of diagonal k compares P[p0 + h - k ..] with T[t0 + h ..]; at most L(k) - h symbols are
-            // left, L the cell's limit.  Cells that do not extend (NULL, halo lanes) run through the same code: their
-            // addresses may lie anywhere (LDS reads outside the allocation return 0), a NULL stays far below 0 when a
-            // window's worth is added to it, and only the "longer than a window" flag is masked.
-            // The eight window reads of a level (two per cell) are issued together and waited for once: taken cell by
-            // cell the compiler serialises read - wait - use, eight exposed LDS round trips per level.
-            // Round 3: a window is addressed by its LDS-wide BIT index = cell * 2^SR_SYM_LOG + constant, one v_mad_i32_i16
-            // straight from the packed cell (it is the read address >> 3 and v_alignbit's shift at once); "longer than a
-            // window" is ext == SR_WIN (a cell with exactly SR_WIN symbols left takes one idle turn of the loop below).
-            unsigned long long pend[4];
-            {
-                uint32_t pl[4], ph[4], tl[4], th[4];
-                int bp[4], bt[4];
-                const uint32_t mwa = h2_u(m.a), mwb = h2_u(m.b);
-                bp[0] = bit_index<0>(mwa, cpb0); bp[1] = bit_index<1>(mwa, cpb1); bp[2] = bit_index<0>(mwb, cpb2); bp[3] = bit_index<1>(mwb, cpb3);
-                bt[0] = bit_index_u<0>(mwa, ctb); bt[1] = bit_index_u<1>(mwa, ctb); bt[2] = bit_index_u<0>(mwb, ctb); bt[3] = bit_index_u<1>(mwb, ctb);
-#ifdef SR_BOUNDS
-                {   // live cells (owned, offset >= 0, within their limit) must read their windows inside the staged sequences
-                    const unsigned lo_ = (unsigned)(uintptr_t)lds_seq;
-                    const unsigned seq_hi = lo_ + RFL(k_sh.lds_seq_bytes);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int mvq = q4_get(m, q);
-                        if (owned && mvq >= -BIAS && mvq <= q4_get(Lb, q)) {
-                            const unsigned ap = ((unsigned)bp[q] >> 3) & ~3u, at = ((unsigned)bt[q] >> 3) & ~3u;
-                            if (ap < lo_ || ap + 8u > seq_hi) kbnd_fail(3u, ap, seq_hi);
-                            if (at < lo_ || at + 8u > seq_hi) kbnd_fail(3u, at, seq_hi);
-                        }
-                    }
-                }
-#endif
-#pragma unroll
-                for (int q = 0; q < 4; q++) { win_words_bit(bp[q], pl[q], ph[q]); win_words_bit(bt[q], tl[q], th[q]); }
-                asm volatile("; 8 windows in flight" : "+v"(pl[0]), "+v"(ph[0]), "+v"(pl[1]), "+v"(ph[1]), "+v"(pl[2]), "+v"(ph[2]), "+v"(pl[3]), "+v"(ph[3]),
-                                                        "+v"(tl[0]), "+v"(th[0]), "+v"(tl[1]), "+v"(th[1]), "+v"(tl[2]), "+v"(th[2]), "+v"(tl[3]), "+v"(th[3]));
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int nn = q4_get(Lb, q) - mv[q];
-                    const uint32_t xw = __builtin_amdgcn_alignbit(ph[q], pl[q], (uint32_t)bp[q]) ^
-                                        __builtin_amdgcn_alignbit(th[q], tl[q], (uint32_t)bt[q]);
-                    const int ext_ = (int)min3u(ffs_sym(xw), (unsigned)SR_WIN, (unsigned)nn);
-                    mv[q] += (SR_NULL_NOEXT && mv[q] < -BIAS) ? 0 : ext_;
-                    // (one ballot per compare: a ballot of `a && b` goes through a 0 / 1 register and a third compare)
-                    pend[q] = __builtin_amdgcn_ballot_w64(ext_ == SR_WIN) & __builtin_amdgcn_ballot_w64(mv[q] >= -BIAS) & ownb;
-                }
-            }
-            // runs longer than a window: the wave iterates, skipping the cell positions q no lane needs
-            while ((pend[0] | pend[1] | pend[2] | pend[3]) != 0ull) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if (pend[q] == 0ull) continue;
-                    const int nn = lanes_or_zero(pend[q], q4_get(Lb, q) - mv[q]);      // 0 for the lanes that are done
-                    const uint32_t xw = win_sym(mv[q] + cp0 - q) ^ win_sym(mv[q] + ct0);
-                    mv[q] += (int)min3u(ffs_sym(xw), (unsigned)SR_WIN, (unsigned)nn);
-                    pend[q] = __builtin_amdgcn_ballot_w64(xw == 0u && nn > SR_WIN);
-                }
-            }
-            m.a = h2_pack_perm(mv[0], mv[1]); m.b = h2_pack_perm(mv[2], mv[3]);
-            if (XK) mvh[XK ? j : 0] = m;
-            // max antidiagonal 2h - k of the lane's valid cells (<= plen + tlen < 2^16: unsigned 16-bit lanes; the biased tile
-            // serves sequences up to 57 k: 32-bit there)
-            int ak;
-            if constexpr (BIAS == 0) {
-                typedef unsigned short __attribute__((ext_vector_type(2))) U2;
-                const uint32_t va = ~h2_u(m.a >> (H2){15, 15}), vb = ~h2_u(m.b >> (H2){15, 15});
-                const uint32_t aa = h2_u(m.a + m.a - kk.a) & va, ab = h2_u(m.b + m.b - kk.b) & vb;
-                const uint32_t mx2 = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(U2, aa), __builtin_bit_cast(U2, ab)));
-                ak = owned ? (int)max(mx2 >> 16, mx2 & 0xffffu) : 0;
-            } else {
-                ak = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++) ak = max(ak, mv[q] >= -BIAS ? 2 * (mv[q] + BIAS) - (k0 + q) : 0);
-                ak = owned ? ak : 0;
-            }
-            uacc = q4_max(uacc, m);
-            if (j == 0 && s0 == 0) uacc = TWO ? q4_max(uacc, q4_max(q4_max(i1, i2), q4_max(d1, d2))) : q4_max(uacc, q4_max(i1, d1));
-            if (chk >= 0) {                   // score-only / base-case aligners: has the end cell been reached?
-                const int qe = kend - k0;                                   // the end diagonal's cell of this lane, if any
-                if (owned && qe >= 0 && qe < 4 && kend >= klo && kend <= khi) {
-                    const uint32_t wa = (chk == SR_C_I1) ? h2_u(i1.a) : (chk == SR_C_I2) ? h2_u(i2.a) : (chk == SR_C_D1) ? h2_u(d1.a)
-                                      : (chk == SR_C_D2) ? h2_u(d2.a) : h2_u(m.a);
-                    const uint32_t wb = (chk == SR_C_I1) ? h2_u(i1.b) : (chk == SR_C_I2) ? h2_u(i2.b) : (chk == SR_C_D1) ? h2_u(d1.b)
-                                      : (chk == SR_C_D2) ? h2_u(d2.b) : h2_u(m.b);
-                    const uint32_t w = (qe & 2) ? wb : wa;
-                    const int val = (int)(short)((qe & 1) ? (w >> 16) : (w & 0xffffu));
-                    if (val + BIAS >= tlen) k_sh.jreach[j][jid] = 1;
-                }
-            }
-            ak = row16_max_nn(ak);
-#ifdef SR_INJECT_VALU
-            if constexpr (RING && !IDONLY) {
-#pragma unroll
-                for (int i = 0; i < SR_INJECT_VALU; i++) asm volatile("v_mad_u32_u24 %0, %0, 3, %0" : "+v"(inj));
-            }
-#endif
-            if ((lane & 15) == 15 && ak > 0) atomicMax(&k_sh.jak[j][jid_l], ak);
-        } else {
-            uacc = q4_max(uacc, Lown[IDONLY ? j : 0]);
-            if (j == 0 && s0 == 0) uacc = TWO ? q4_max(uacc, q4_max(q4_max(i1, i2), q4_max(d1, d2))) : q4_max(uacc, q4_max(i1, d1));
-        }
-        if (owned) {
-            if constexpr (IMMR) {
-                const int im = j - KBLK_C;
-                const bool l1 = j + E1 >= B, l2 = j + E2 >= B;       // the block's last e levels: chain sources of the next block
-                if (!IDONLY) ist<OT, ST>(R, sM, lane_j, im, q4_vec(m));
-                if (l1) { ist<OT, ST>(R, sI1, lane_j, im, q4_vec(i1)); ist<OT, ST>(R, sD1, lane_j, im, q4_vec(d1)); }
-                if (TWO && l2) { ist<OT, ST>(R, sI2, lane_j, im, q4_vec(i2)); ist<OT, ST>(R, sD2, lane_j, im, q4_vec(d2)); }
-                if (rec && (!l1 || (TWO && !l2))) {
-                    const unsigned lane_r = kopaque_v(lane_b);           // (own block: see kopaque_v)
-                    if (!l1) { ist_nt<OT, ST>(R, sI1, lane_r, im, q4_vec(i1)); ist_nt<OT, ST>(R, sD1, lane_r, im, q4_vec(d1)); }
-                    if (TWO && !l2) { ist_nt<OT, ST>(R, sI2, lane_r, im, q4_vec(i2)); ist_nt<OT, ST>(R, sD2, lane_r, im, q4_vec(d2)); }
-                }
-            } else {
-            if (!IDONLY) rst<OT>(R, KROW(s, SR_C_M), idx0, q4_vec(m));
-            if (j + E1 < B) { if (rec) { rst_nt<OT>(R, KROW(s, SR_C_I1), idx0, q4_vec(i1)); rst_nt<OT>(R, KROW(s, SR_C_D1), idx0, q4_vec(d1)); } }
-            else { rst<OT>(R, KROW(s, SR_C_I1), idx0, q4_vec(i1)); rst<OT>(R, KROW(s, SR_C_D1), idx0, q4_vec(d1)); }
-            if (TWO) {
-                if (j + E2 < B) { if (rec) { rst_nt<OT>(R, KROW(s, SR_C_I2), idx0, q4_vec(i2)); rst_nt<OT>(R, KROW(s, SR_C_D2), idx0, q4_vec(d2)); } }
-                else { rst<OT>(R, KROW(s, SR_C_I2), idx0, q4_vec(i2)); rst<OT>(R, KROW(s, SR_C_D2), idx0, q4_vec(d2)); }
-            }
-            }
-        }
-    }
-    if (with_u && owned) rst_raw16(R, R.urow, idx0, q4_vec(uacc));
-#if defined(SR_INJECT_VALU) || defined(SR_INJECT_LOADS)
-    asm volatile("; injected work ends here" :: "v"(inj));             // (keeps the injected loads / instructions alive)
-#endif
-#ifdef SR_TILE_STAMPS
-    if (lane == 0 && !IDONLY) {
-        const int w_ = (int)(threadIdx.x >> 6) & 15;
-        k_sh.st_wait[w_] += st1_ - st0_; k_sh.st_body[w_] += ST_NOW() - st1_; k_sh.st_tiles[w_] += 1;
-    }
-#endif
-#undef KROW
-#undef LDQ
-#undef LDQ_NT
-}
-
-// tile dispatch: int16 rows of the blocked instances take the packed tile
-template <typename OT, bool TWO, int B, int E1, int E2, bool IDONLY, int X, int OE1, typename ST = OT, bool RING = false>
-__device__ __forceinline__ void blk_tile_any(const KRows<OT, ST> &R, const int s0, const int slot0, const SrPen &pen,
-                                             const int jid, const int ti, const int tix, unsigned &row_ld, unsigned &row_st, const int mrg = 0) {
-    // (round 2 kept the packed tile off the generic 5-level instance: built with it, a workgroup's second pair failed in most
-    // builds, blamed on LDS reads outside the LDS.  Round 3: such reads return 0 and leave nothing behind
-    // (scripts/lds_oob, profiles/r03_lds_oob.log), and neither today's source nor the round-2 source rebuilt without the
-    // address wrap reproduces the failure -- 53 parity tests incl. several pairs per workgroup pass; enabled, DESIGN 4.1)
-#ifndef SR_PK_GENERIC
-#define SR_PK_GENERIC 1
-#endif
-    if constexpr (SR_BLK_PK16 && sizeof(OT) == 2 && (X > 0 || (SR_PK_GENERIC && B >= 5))) blk_tile16<TWO, B, E1, E2, IDONLY, X, OE1, RING>(R, s0, slot0, pen, jid, ti, tix, row_ld, row_st, mrg);
-    // 32-bit search, 16-bit ring (C5): the packed tile on the rows as stored (SR_PK_U16=0: the 32-bit tile with conversions, A/B builds)
-    else if constexpr (KPK_U16_OF(OT, ST, B, X) && RING) blk_tile16<TWO, B, E1, E2, IDONLY, X, OE1, true, KRows<OT, ST>, SR_RING_BIAS>(R, s0, slot0, pen, jid, ti, tix, row_ld, row_st, mrg);
-    else blk_tile<OT, TWO, B, E1, E2, IDONLY, X, OE1>(R, s0, slot0, pen, jid, ti, tix, row_ld, row_st);
-}
-
-// reach() with compile-time gap-extends (the host guarantees pen.e1 == E1, pen.e2 == E2): no runtime division
-template <bool TWO, int E1, int E2>
-__device__ __forceinline__ int kreach(const SrPen &p, int s, int begin) {
-    int r;
-    if (begin == SR_C_M) {
-        r = (s >= p.o1 + E1) ? (s - p.o1) / E1 : 0;
-        if (TWO && s >= p.o2 + E2) r = max(r, (s - p.o2) / E2);
-    } else {
-        r = s / E1;
-        if (TWO) r = max(r, s / E2);
-    }
-    return r;
-}
-
-// Groups [glo, ghi] the tiles of block s0 (levels s0 .. s0+B-1) of aligner b cover -- and store.
-//  * wide (round 1-3, still used by base-case histories and the generic instances): the last level's range + scope + 1
-//    diagonals either side, so that every later reader (levels up to scope + B above, one neighbour diagonal) finds NULL
-//    beyond the range instead of whatever the ring slot held before: 2 (scope + 1) = 54 extra diagonals per aligner and
-//    level for the default penalties -- 9 % of all tile lanes on C2, more the deeper the recursion (narrow segments).
-//  * TIGHT (round 4, ring tiles of the exact instance): the last level's range + the one neighbour diagonal.  What lies
-//    outside is never written and may hold anything; a tile that reads a source block (s0 - B: M[s - o1 - e1], M[s - x], the
-//    chain sources; the one or two blocks M[s - o2 - e2] comes from) masks the lanes outside THAT block's coverage to NULL
-//    (blk_tile16: `in10 / in2a / in2b`; a tile whose 64 lanes lie inside the narrowest source coverage skips the masks),
-//    breakpoint detection tests every cell against its level's range anyway.
-template <bool TWO, int B, int E1, int E2, bool TIGHT>
-__device__ __forceinline__ void kwindow(const SrPen &pen, const BJob &b, int s0, int &glo, int &ghi) {
-    const int Rw = kreach<TWO, E1, E2>(pen, s0 + B - 1, b.begin);
-    const int mg = TIGHT ? 1 : pen.scope + 1;
-    const int wlo = max(-b.plen - 1, -Rw - mg), whi = min(b.tlen + 1, Rw + mg);
-    glo = (wlo + b.shift) >> 2; ghi = (whi + b.shift) >> 2;
-}
-
-// One pass: levels s0 .. s0+B-1 of every active aligner.  Ends with the data of the
-// pass still in flight: the caller's __syncthreads() publishes rows and reductions.
-#define KTICK() (PROF ? __builtin_amdgcn_s_memrealtime() : 0ull)
-// Sections that one wave (or one lane) runs while the workgroup's other waves wait at the barrier are the pair's critical
-// path, and the SIMD they run on is shared with three waves of other workgroups that are usually in their tiles: raised
-// issue priority (s_setprio) lets the lone wave through first; back to 0 before the barrier.
-#ifndef SR_SERIAL_PRIO
-#define SR_SERIAL_PRIO 3
-#endif
-#define KPRIO_HI() __builtin_amdgcn_s_setprio(SR_SERIAL_PRIO)
-#define KPRIO_LO() __builtin_amdgcn_s_setprio(0)
-// Tables of one pass (levels s0 .. s0+B-1 of every active aligner): wave 0, one lane per aligner.  The first pass of a batch
-// of searches runs it inside blk_pass; later passes get their tables from the wave-0 section that ends the previous pass
-// (control, or the section after breakpoint detection), so a pass costs one barrier and one serial hop less.
-template <bool TWO, int NT, int B, int E1, int E2, bool TIGHT = false>
-__device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs, unsigned long long &cells_acc) {
-    const int tid = threadIdx.x;                         // (tid < 64)
-    int nt = 0, glo = 0, ghi = -1, cells = 0, band = 0;
-    const bool act = tid < njobs && b_sh.job[tid].active;
-    const int pglo = (tid < BJ_MAX) ? k_sh.jglo[tid] : 0, pghi = (tid < BJ_MAX) ? k_sh.jghi[tid] : -1;
-    if (act) {
-        const BJob &b = b_sh.job[tid];
-        int Rw = 0;
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            Rw = kreach<TWO, E1, E2>(pen, s0 + j, b.begin);
-            const int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
-            k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
-            cells += (khi >= klo) ? khi - klo + 1 : 0;
-        }
-        (void)Rw;
-        kwindow<TWO, B, E1, E2, TIGHT>(pen, b, s0, glo, ghi);
-        nt = (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN;
-    }
-    int mrg_at = 0;
-    if constexpr (TIGHT && SR_MERGE_TAILS) {
-        // the two aligners of a segment (lanes 2 sa, 2 sa + 1) with the same tables and a last tile that fits a half wave: the
-        // reverse aligner gives its last tile up, the forward one's carries both (blk_tile16, `mrg`)
-        const BJob &b = b_sh.job[act ? tid : 0];
-        const int ok = (act && nt > 0 && s0 > 0 && b.chk < 0) ? 1 : 0;
-        const int rem = nt > 0 ? (ghi - glo + 1) - (nt - 1) * KGeo<B>::OWN : 0;
-        const int key0 = ok ? b.begin : -1, key1 = ok ? b.plen : -1, key2 = ok ? b.tlen : -1, key3 = ok ? b.shift : -1, key4 = ok ? b.pad2 : -1;
-        // (every lane takes part in every shuffle: no short-circuit in front of them)
-        const int q_ok = __shfl_xor(ok, 1, 64), q_nt = __shfl_xor(nt, 1, 64), q_glo = __shfl_xor(glo, 1, 64), q_ghi = __shfl_xor(ghi, 1, 64);
-        const int q0 = __shfl_xor(key0, 1, 64), q1 = __shfl_xor(key1, 1, 64), q2 = __shfl_xor(key2, 1, 64), q3 = __shfl_xor(key3, 1, 64), q4 = __shfl_xor(key4, 1, 64);
-        const bool same = ok && q_ok && q_nt == nt && q_glo == glo && q_ghi == ghi && q0 == key0 && q1 == key1 && q2 == key2 && q3 == key3 &&
-                          q4 == key4 && rem <= 32 - 2 * KGeo<B>::HL;
-        if (same) { if (tid & 1) nt -= 1; else mrg_at = nt; }
-    }
-    if (act) {
-        const BJob &b = b_sh.job[tid];
-        // the tile over diagonal 0: where the alignment runs (few indels), i.e. where the extension loops are
-        band = min(max(((b.shift >> 2) - glo) / KGeo<B>::OWN, 0), nt - 1);
-    }
-    if (!SR_BAND_FIRST) band = INT_MAX / 2;            // (A/B builds: the queue in aligner order, as before round 4)
-    // Band-first order (round 4, -DSR_BAND_FIRST=1; off): the tile of an aligner that holds the alignment's own diagonals spends
-    // longer in the extension's loop (runs of tens of matches; everywhere else the first window ends a run), and a pass ends
-    // when its last tile does -- so the queue could start with the band tiles of all aligners.  Measured: C2 81.7 -> 83.4 ms,
-    // C4 1031 -> 1055 ms, C3 +0.3 % (profiles/r04_ab.log): tiles taken in index order read rows their neighbours just
-    // touched, and the longer fetch path costs more than the stragglers did.  Kept as a switch, default off.
-    const int has = (SR_BAND_FIRST && nt > 0) ? 1 : 0;
-    int incl = nt - has, hincl = has;                  // prefix sums: tiles but the band tile, aligners with tiles
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64), h = __shfl_up(hincl, o, 64);
-        if (tid >= o) { incl += v; hincl += h; }
-    }
-    if (tid < BJ_MAX) {
-        k_sh.jglo[tid] = glo; k_sh.jghi[tid] = ghi;
-        k_sh.jgplo[tid] = pglo; k_sh.jgphi[tid] = pghi;
-        k_sh.jtstart[tid + 1] = incl;
-        k_sh.jmerge[tid] = mrg_at;
-        k_sh.jband[tid] = band;
-        if (has) k_sh.jbandown[hincl - 1] = tid;
-#pragma unroll
-        for (int j = 0; j < B; j++) { k_sh.jak[j][tid] = 0; k_sh.jreach[j][tid] = 0; }
-    }
-    if (tid == 0) k_sh.jtstart[0] = 0;
-    if (tid == 63) { k_sh.nband = hincl; k_sh.total_tiles = incl + hincl; k_sh.next_tile = NT / 64; }
-    if (SR_LEAN_PASS) k_sh.cells_l[tid] += (unsigned long long)cells;    // (tid < 64)
-    else cells_acc += (unsigned long long)cells;          // per lane (= aligner); summed when the kernel ends
-#ifdef SR_TILE_STATS
-    {   // experiment builds (scripts/build_variant.sh stats "-DSR_BLK_ONLY_PROD -DSR_TILE_STATS"): how full the aligners' last
-        // tiles and a pass's tile rounds are -- the potential of "two aligners' remainders in one wave" (DESIGN.md section 7)
-        constexpr int OWNG = KGeo<B>::OWN;
-        const bool on = act && nt > 0;
-        const int groups = on ? ghi - glo + 1 : 0;
-        const int rem = on ? groups - (nt - 1) * OWNG : 0;
-        const bool small_ = on && rem <= (64 / 2) - (64 - OWNG);    // fits a half wave that keeps the tile's halo lanes on either side
-        const bool partner = __shfl_xor((int)small_, 1, 64) != 0;
-        const unsigned long long m_on = __ballot(on), m_small = __ballot(small_), m_both = __ballot(small_ && partner && !(tid & 1));
-        int tl = on ? nt : 0, gr = groups;
-        for (int o = 32; o > 0; o >>= 1) { tl += __shfl_xor(tl, o, 64); gr += __shfl_xor(gr, o, 64); }
-        if (tid == 0 && tl > 0) {
-            const int waves = NT / 64, rounds = (tl + waves - 1) / waves;
-            k_sh.ts[0] += (unsigned long long)__popcll(m_on); k_sh.ts[1] += (unsigned long long)tl; k_sh.ts[2] += (unsigned long long)gr;
-            k_sh.ts[3] += (unsigned long long)__popcll(m_small); k_sh.ts[4] += (unsigned long long)__popcll(m_both); k_sh.ts[5] += 1ull;
-            k_sh.ts[6] += (unsigned long long)rounds;
-            k_sh.ts[7] += (unsigned long long)((tl - __popcll(m_both) + waves - 1) / waves);      // rounds if every such pair of remainders shared a wave
-        }
-    }
-#endif
-}
-
-template <typename OT, bool TWO, int NT, int B, int E1, int E2, bool PROF, int X = 0, int OE1 = 0, typename ST = OT, bool RING = false>
-__device__ __forceinline__ void blk_pass(const KRows<OT, ST> &R, int s0, const SrPen &pen, int njobs,
-                                         unsigned long long &cells_acc, unsigned &row_ld, unsigned &row_st, const bool setup = true) {
-    const int tid = threadIdx.x;
-    if (setup) {
-        const unsigned long long tsu0 = KTICK();
-        if (tid < 64) blk_setup<TWO, NT, B, E1, E2, RING && KTIGHT_OF(OT, ST, B, X)>(s0, pen, njobs, cells_acc);
-        __syncthreads();
-        if (PROF && threadIdx.x == 0) k_sh.t_setup += KTICK() - tsu0;
-    }
-    const int total = RFL(k_sh.total_tiles);
-    const int slot0 = kslots(R, s0);
-    // Tiles differ in cost (extension loops, edge tiles): every wave takes its first tile by index and the following
-    // ones from a queue, so that the pass ends when the work does and not when the unluckiest wave's share does.
-    const int nband = RFL(k_sh.nband);
-    for (int t = (tid >> 6); t < total;) {
-        int lo, ti;
-        if (t < nband) { lo = RFL(k_sh.jbandown[t]); ti = RFL(k_sh.jband[lo]); }      // the band tiles first
-        else {
-            const int r = t - nband;
-            int hi = njobs; lo = 0;                 // last aligner with jtstart <= r (wave-uniform; jtstart counts the tiles but the band tile)
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (RFL(k_sh.jtstart[mid]) <= r) lo = mid; else hi = mid; }
-            ti = r - RFL(k_sh.jtstart[lo]);
-            ti += (ti >= RFL(k_sh.jband[lo])) ? 1 : 0;
-        }
-        const int mrg = (RING && KTIGHT_OF(OT, ST, B, X) && SR_MERGE_TAILS) ? (RFL(k_sh.jmerge[lo]) == ti + 1 ? 1 : 0) : 0;
-        blk_tile_any<OT, TWO, B, E1, E2, false, X, OE1, ST, RING>(R, s0, slot0, pen, lo, ti, lo, row_ld, row_st, mrg);
-        int nx = 0;
-        if ((tid & 63) == 0) nx = atomicAdd(&k_sh.next_tile, 1);
-        t = RFL(nx);
-    }
-}
-
-// Segment sa has just entered phase 2: recompute and store the I/D rows of the levels breakpoint detection will
-// read (the scope window below the entry level, up to the end of the current block), block by block from the last
-// block boundary before the window -- its chain sources, the previous block's last e levels, are always stored.
-// Needs the M rows down to (window start - scope): ring depth >= 2 * scope + 2 * B + 2.
-template <typename OT, bool TWO, int NT, int B, int E1, int E2, int X = 0, int OE1 = 0, typename ST = OT>
-__device__ __forceinline__ void blk_recompute(const KRows<OT, ST> &R, const SrPen &pen, int sa, int entry_level, int s0_now,
-                                              unsigned &row_ld, unsigned &row_st) {
-    const int tid = threadIdx.x;
-    const int wlo = max(0, entry_level - pen.scope);
-    for (int blk = (wlo / B) * B; blk <= s0_now; blk += B) {
-        __syncthreads();
-        if (tid < 2) {
-            const BJob &b = b_sh.job[2 * sa + tid];
-            int Rw = 0;
-#pragma unroll
-            for (int j = 0; j < B; j++) {
-                Rw = kreach<TWO, E1, E2>(pen, blk + j, b.begin);
-                k_sh.jklo[j][BJ_MAX + tid] = max(-b.plen, -Rw); k_sh.jkhi[j][BJ_MAX + tid] = min(b.tlen, Rw);
-            }
-            (void)Rw;
-            int glo, ghi;
-            kwindow<TWO, B, E1, E2, KTIGHT_OF(OT, ST, B, X)>(pen, b, blk, glo, ghi);      // (the coverage the block's own pass had)
-            const bool first = blk == (wlo / B) * B;        // U starts from NULL in the first recompute block
-            k_sh.jgplo[BJ_MAX + tid] = first ? 1 : k_sh.jglo[BJ_MAX + tid];
-            k_sh.jgphi[BJ_MAX + tid] = first ? 0 : k_sh.jghi[BJ_MAX + tid];
-            k_sh.jglo[BJ_MAX + tid] = glo; k_sh.jghi[BJ_MAX + tid] = ghi;
-            const int nt = (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN;
-            const int n0 = __shfl(nt, 0, 64), n1 = __shfl(nt, 1, 64);
-            if (tid == 0) { k_sh.rt_n0 = n0; k_sh.rt_total = n0 + n1; }
-        }
-        __syncthreads();
-        const int n0 = RFL(k_sh.rt_n0), total = RFL(k_sh.rt_total);
-        const int slot0 = kslots(R, blk);
-        for (int t = (tid >> 6); t < total; t += NT / 64) {
-            const int side = (t >= n0) ? 1 : 0;
-            blk_tile_any<OT, TWO, B, E1, E2, true, X, OE1, ST, true>(R, blk, slot0, pen, 2 * sa + side, t - (side ? n0 : 0), BJ_MAX + side, row_ld, row_st);
-        }
-    }
-    __syncthreads();
-    if (tid < 2) b_sh.job[2 * sa + tid].pad2 = 1;           // from now on the search stores its I/D rows
-}
-
-// cells of levels (l0, l1] of aligner jid -- work a block computed past the aligner's last level
-__device__ __forceinline__ long long blk_surplus(const SrPen &pen, int jid, int l0, int l1) {
-    const BJob &b = b_sh.job[jid];
-    long long c = 0;
-    for (int l = l0 + 1; l <= l1; l++) {
-        const int Rw = reach(pen, l, b.begin);
-        const int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
-        c += (khi >= klo) ? khi - klo + 1 : 0;
-    }
-    return c;
-}
-
-// ---- batched breakpoint detection ("phase 2") of one pass ------------------------------------
-// Reference loop (oracle bialign_find_breakpoint, WFA2 wavefront_bialign.c), per segment:
-//     if (last_fwd) { done-check; overlap(F@score_f vs R <= score_r); ++score_r; }
-//     done-check; overlap(R@score_r vs F <= score_f); ++score_f; last_fwd = 1
-// A block makes levels <= avail of both aligners available, so a segment runs the loop while
-// score_f <= avail: at most 2B overlap calls per pass.  overlap() walks (i ascending, component in the
-// order D2 I2 D1 I1 M), takes the smallest overlapping diagonal of each (i, component) and accepts it
-// when score_0 + score_i - gap(component) is strictly below the running best; the accepted value
-// depends on (i, component) only, so a call's outcome is its candidate with the smallest value,
-// earliest in walk order among equals (then the smallest diagonal), if that is below the best so far.
-// What a call can find does not depend on the running best, so all calls of all segments of the pass
-// are evaluated together:
-//   A  one thread per segment lists its calls
-//   F  filter: diagonals whose M offset plus the other aligner's U bound (blk_tile keeps U = running
-//      max of M per diagonal, a superset bound of the scope window) reaches tlen -> candidate list
-//   E  candidates x scope levels: exact overlap test per component, 64-bit atomicMin of the packed
-//      (value, walk order, diagonal) per call
-//   W  one thread per segment replays the reference loop with the done-checks over the calls' results.
-template <typename OT, bool TWO, int NT, int B, int E1, int E2, typename ST = OT, bool PROF = false>
-__device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t> clist, GP<int> gmak,
-                                           const SrPen &pen, const int s0, const int nact, const int gap_opening) {
-    const int depth = RR.depth;
-    const int tid = threadIdx.x;
-    const int avail = s0 + B - 1, scope = pen.scope;
-    const int gapmax = gap_opening;
-#define KR(S, C) krow_abs(RR, (S), (C))
-    // k_sh.p2mask (written by the control section of wave 0): segments in phase 2; rounds of <= K_P2 of them
-    for (;;) {
-        const unsigned long long pmask = ((unsigned long long)RFL(k_sh.p2mask_hi) << 32) | (unsigned)RFL(k_sh.p2mask_lo);
-        if (pmask == 0ull) break;
-        __syncthreads();                                   // every wave has read the mask before wave 0 replaces it
-        const int n2 = min(__popcll(pmask), K_P2);
-        const unsigned long long tp0 = PROF ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        if (tid < 64) KPRIO_HI();                          // wave 0 lists the calls and the filter units alone
-        if (tid < 64) {
-            const bool mine = (pmask >> tid) & 1ull;
-            const int rank = __popcll(pmask & ((1ull << tid) - 1ull));
-            if (mine && rank < K_P2) k_sh.p2seg[rank] = tid;
-            const unsigned long long rest = __ballot(mine && rank >= K_P2);      // next round
-            if (tid == 0) { k_sh.p2mask_lo = (unsigned)rest; k_sh.p2mask_hi = (unsigned)(rest >> 32); k_sh.cl_n = 0; }
-        }
-        // ---- A: calls of each segment; filter units (segment, side)
-        if (tid < n2) {
-            const BSeg &sg = b_sh.seg[k_sh.p2seg[tid]];
-            int n = 0, f = sg.score_f, r = sg.score_r, lf = sg.last_fwd;
-#pragma unroll
-            for (int j = 0; j < B; j++) { k_sh.pc_idx[tid][0][j] = -1; k_sh.pc_idx[tid][1][j] = -1; }
-            while (f <= avail) {
-                if (lf) {
-                    k_sh.pc_side[tid][n] = 0; k_sh.pc_s0[tid][n] = f; k_sh.pc_s1[tid][n] = r; k_sh.pc_best[tid][n] = ~0ull;
-                    k_sh.pc_idx[tid][0][f - s0] = n; n++; r++;
-                }
-                k_sh.pc_side[tid][n] = 1; k_sh.pc_s0[tid][n] = r; k_sh.pc_s1[tid][n] = f; k_sh.pc_best[tid][n] = ~0ull;
-                k_sh.pc_idx[tid][1][r - s0] = n; n++; f++; lf = 1;
-            }
-            k_sh.pc_n[tid] = n;
-        }
-        if (tid < 64) {
-            int ng = 0, glo = 0;
-            if (tid < 2 * n2) {
-                const int p = tid >> 1, side = tid & 1, sa = k_sh.p2seg[p];
-                const BJob &b0 = b_sh.job[2 * sa + side];
-                const int j0 = 2 * sa + side, j1 = 2 * sa + 1 - side, kinv = b0.tlen - b0.plen;
-                const int lo = max(k_sh.jklo[B - 1][j0], kinv - k_sh.jkhi[B - 1][j1]);
-                const int hi = min(k_sh.jkhi[B - 1][j0], kinv - k_sh.jklo[B - 1][j1]);
-                if (hi >= lo) { glo = (lo + b0.shift) >> 2; ng = ((hi + b0.shift) >> 2) - glo + 1; }
-            }
-            int incl = ng;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if (tid >= o) incl += v; }
-            if (tid < 2 * K_P2) { k_sh.pu_glo[tid] = glo; k_sh.pu_start[tid + 1] = incl; k_sh.pu_kmin[tid] = INT_MAX; k_sh.pu_kmax[tid] = INT_MIN; }
-            if (tid == 0) k_sh.pu_start[0] = 0;
-            KPRIO_LO();
-        }
-        __syncthreads();
-        const unsigned long long tp1 = PROF ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        // ---- F: filter
-        {
-            const int total = RFL(k_sh.pu_start[2 * n2]);
-            if (tid == 0) { k_sh.dg_f += (unsigned long long)total; k_sh.dg_r += 1ull; }
-            for (int it = tid; it < total; it += NT) {
-                int lo = 0, hi = 2 * n2;
-                while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (k_sh.pu_start[mid] <= it) lo = mid; else hi = mid; }
-                const int unit = lo, p = unit >> 1, side = unit & 1, sa = k_sh.p2seg[p];
-                const int j0 = 2 * sa + side, j1 = 2 * sa + 1 - side;
-                const BJob &b0 = b_sh.job[j0];
-                const BJob &b1 = b_sh.job[j1];
-                const int tlen = b0.tlen, kinv = b0.tlen - b0.plen;
-                const int g = k_sh.pu_glo[unit] + (it - k_sh.pu_start[unit]);
-                const int k0 = (g << 2) - b0.shift;
-                const unsigned idx0 = klane(RR, (unsigned)(b0.base + (g << 2)));
-                const int klo1 = k_sh.jklo[B - 1][j1], khi1 = k_sh.jkhi[B - 1][j1];
-                const int u1off = b1.base + b1.shift;
-                // every load of the unit is issued before the first one is looked at: the block's M rows of the group
-                // (all stored, whether a level has a call or not) and the other aligner's U cells
-                V4<OT> mrows[B];
-#pragma unroll
-                for (int j = 0; j < B; j++) mrows[j] = rld<OT>(RR, KR(s0 + j, SR_C_M), idx0);
-                int u1[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int k1 = kinv - (k0 + q);
-                    const int uv = rcell<OT>(RR, RR.urow, u1off + min(max(k1, klo1), khi1));
-                    u1[q] = (k1 >= klo1 && k1 <= khi1) ? uv : NULLV;
-                }
-#pragma unroll
-                for (int j = 0; j < B; j++) {
-                    const int ci = k_sh.pc_idx[p][side][j];
-                    if (ci < 0) continue;
-                    const int lvl = s0 + j;
-                    const int klo0 = k_sh.jklo[j][j0], khi0 = k_sh.jkhi[j][j0];
-                    int m0[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) m0[q] = (int)mrows[j][q];
-                    if (lvl == 0) {                        // the begin component need not be M
-#pragma unroll
-                        for (int c = 1; c < 5; c++) {
-                            if (!TWO && (c == SR_C_I2 || c == SR_C_D2)) continue;
-                            const V4<OT> x = rld<OT>(RR, KR(0, c), idx0);
-#pragma unroll
-                            for (int q = 0; q < 4; q++) m0[q] = max(m0[q], (int)x[q]);
-                        }
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int k = k0 + q;
-                        if (k >= klo0 && k <= khi0 && m0[q] >= 0 && u1[q] >= 0 && m0[q] + u1[q] >= tlen) {
-                            atomicMin(&k_sh.pu_kmin[unit], k); atomicMax(&k_sh.pu_kmax[unit], k);
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned long long tp2 = PROF ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        // ---- E: exact overlap tests.  One wave per (segment, side, 64 diagonals of the unit's band): lanes are adjacent
-        // diagonals, so the cells of a (level, component) row are one coalesced access (the other aligner's run downwards).
-        // The calls of a side are consecutive levels of its own aligner and their scope windows of the other aligner overlap
-        // almost entirely, so the loops run over ABSOLUTE levels: five calls' own cells (5 x 5 registers) against blocks of
-        // five levels of the other aligner (5 x 5 registers), every (call, level) pair inside a call's window tested from
-        // registers -- one memory round trip per 125 (call, level, component) tests.  All skips are wave-uniform.  Diagonals
-        // of the band that did not pass the filter at a call's level cannot pass here either (a component never exceeds
-        // its level's M, an M never the U bound).
-        {
-            int mch = 0;                                        // most 64-diagonal chunks of a unit
-            for (int u = 0; u < 2 * n2; u++) {
-                const int a0 = RFL(k_sh.pu_kmin[u]), a1 = RFL(k_sh.pu_kmax[u]);
-                if (a1 >= a0) mch = max(mch, (a1 - a0 + 64) >> 6);
-            }
-            const int total = 2 * n2 * mch, lane = tid & 63;
-            if (tid == 0) { k_sh.dg_c += (unsigned long long)total; }
-            for (int it = tid >> 6; it < total; it += NT / 64) {
-                const int unit = it / mch, ch = it - unit * mch, p = unit >> 1, side = unit & 1;
-                const int kmin = RFL(k_sh.pu_kmin[unit]), kmax = RFL(k_sh.pu_kmax[unit]);
-                if (kmax < kmin || kmin + 64 * ch > kmax) continue;
-                const int sa = RFL(k_sh.p2seg[p]);
-                const int bp0 = RFL(b_sh.seg[sa].bp_score);
-                const int j0 = 2 * sa + side, j1 = 2 * sa + 1 - side;
-                const BJob &b0 = b_sh.job[j0];
-                const BJob &b1 = b_sh.job[j1];
-                const int plen = RFL(b0.plen), tlen = RFL(b0.tlen), beg0 = RFL(b0.begin), beg1 = RFL(b1.begin);
-                const int off0 = RFL(b0.base) + RFL(b0.shift), off1 = RFL(b1.base) + RFL(b1.shift);
-                const int k0 = kmin + 64 * ch + lane, k1 = tlen - plen - k0;
-                const bool onb = k0 <= kmax;
-                if (lane == 0) atomicAdd(&k_sh.dg_e, 1ull);
-                for (int jb = 0; jb < B; jb += 5) {             // five levels of the own aligner = up to five calls
-                    int cix[5], sc1[5];                         // call index (-1: the level has no call on this side), other aligner's level
-                    int lmin = INT_MAX, lmax = INT_MIN;
-#pragma unroll
-                    for (int jj = 0; jj < 5; jj++) {
-                        cix[jj] = (jb + jj < B) ? RFL((int)k_sh.pc_idx[p][side][jb + jj < B ? jb + jj : 0]) : -1;
-                        sc1[jj] = cix[jj] >= 0 ? RFL(k_sh.pc_s1[p][cix[jj] >= 0 ? cix[jj] : 0]) : 0;
-                        const int score_0 = s0 + jb + jj;
-                        // levels of the other aligner this call can still accept something from
-                        if (cix[jj] >= 0) {
-                            const int lo_l = max(0, sc1[jj] - (scope - 1)), hi_l = min(sc1[jj], bp0 == INT_MAX ? INT_MAX : bp0 + gapmax - 1 - score_0);
-                            if (hi_l >= lo_l) { lmin = min(lmin, lo_l); lmax = max(lmax, hi_l); }
-                            else cix[jj] = -1;
-                        }
-                    }
-                    if (lmax < lmin) continue;
-                    int c0[5][5], ak0[5];
-#pragma unroll
-                    for (int jj = 0; jj < 5; jj++) {
-                        const int score_0 = s0 + jb + jj;
-                        const int R0 = kreach<TWO, E1, E2>(pen, score_0, beg0);
-                        const bool on0 = onb && cix[jj] >= 0 && k0 >= max(-plen, -R0) && k0 <= min(tlen, R0);
-                        ak0[jj] = cix[jj] >= 0 ? gmak[j0 * BFS_MAK_SLOTS + score_0 % depth] : 0;
-#pragma unroll
-                        for (int c = 0; c < 5; c++) {
-                            c0[jj][c] = NULLV;
-                            if (!TWO && (c == SR_C_I2 || c == SR_C_D2)) continue;
-                            if (on0) c0[jj][c] = rcell<OT>(RR, KR(score_0, c), off0 + k0);
-                        }
-                    }
-                    // Levels of the other aligner whose furthest antidiagonal cannot meet any of these calls' own levels hold no
-                    // overlap: one lane per level of the window looks its max_ak up, the ballot is the set of levels worth
-                    // loading (round 3: at first contact that is the top few of the 26 + 4; their rows were all loaded before).
-                    int ak0max = 0;
-#pragma unroll
-                    for (int jj = 0; jj < 5; jj++) ak0max = max(ak0max, RFL(ak0[jj]));
-                    const int nlev = lmax - lmin + 1;                                  // <= scope + 4 <= 78 (ring depth <= 80): two words
-                    const int akv = (lane < nlev) ? gmak[j1 * BFS_MAK_SLOTS + (lmin + lane) % depth] : 0;
-                    const unsigned long long need = __builtin_amdgcn_ballot_w64(lane < nlev && akv + ak0max >= plen + tlen);
-                    unsigned long long need_hi = 0ull;                                 // levels lmin + 64 .. (deep scopes only)
-                    if (nlev > 64) {
-                        const int akw = (lane + 64 < nlev) ? gmak[j1 * BFS_MAK_SLOTS + (lmin + 64 + lane) % depth] : 0;
-                        need_hi = __builtin_amdgcn_ballot_w64(lane + 64 < nlev && akw + ak0max >= plen + tlen);
-                    }
-                    if ((need | need_hi) == 0ull) continue;
-                    for (int lb = lmin; lb <= lmax; lb += 5) {   // five levels of the other aligner
-                        const int off = lb - lmin;
-                        unsigned long long w = off < 64 ? need >> off : need_hi >> (off - 64);
-                        if (off < 64 && off > 59) w |= need_hi << (64 - off);
-                        const unsigned bits = (unsigned)w & 31u;
-                        if (bits == 0u) continue;
-                        int c1[5][5];
-#pragma unroll
-                        for (int u = 0; u < 5; u++) {
-                            const int L = lb + u;
-                            const bool lon = (bits >> u) & 1u;
-                            const int R1 = kreach<TWO, E1, E2>(pen, L, beg1);
-                            const bool on1 = lon && onb && k1 >= max(-plen, -R1) && k1 <= min(tlen, R1);
-#pragma unroll
-                            for (int c = 0; c < 5; c++) {
-                                c1[u][c] = NULLV;
-                                if (!TWO && (c == SR_C_I2 || c == SR_C_D2)) continue;
-                                if (on1) c1[u][c] = rcell<OT>(RR, KR(L, c), off1 + k1);
-                            }
-                        }
-#pragma unroll
-                        for (int jj = 0; jj < 5; jj++) {
-                            if (cix[jj] < 0) continue;
-                            const int score_0 = s0 + jb + jj;
-#pragma unroll
-                            for (int u = 0; u < 5; u++) {
-                                const int L = lb + u, i = sc1[jj] - L;
-                                if (i < 0 || i >= scope || !((bits >> u) & 1u)) continue;      // outside this call's window / level cannot meet
-                                if (score_0 + L - gapmax >= bp0) continue;                     // no component could be accepted
-#pragma unroll
-                                for (int c = 0; c < 5; c++) {
-                                    if (!TWO && (c == SR_C_I2 || c == SR_C_D2)) continue;
-                                    const int gap = (c == SR_C_M) ? 0 : ((c == SR_C_I1 || c == SR_C_D1) ? pen.o1 : pen.o2);
-                                    const int val = score_0 + L - gap;
-                                    const int o0 = c0[jj][c], o1 = c1[u][c];
-                                    if (val < bp0 && o0 >= 0 && o1 >= 0 && o0 + o1 >= tlen) {
-                                        const int rank = (c == SR_C_D2) ? 0 : (c == SR_C_I2) ? 1 : (c == SR_C_D1) ? 2 : (c == SR_C_I1) ? 3 : 4;
-                                        const unsigned long long key = ((unsigned long long)(unsigned)(val + gapmax) << 42) |   // (i * 5 + rank < 5 * SR_BLK_MAK_SLOTS: 10 bits)
-                                                                       ((unsigned long long)(unsigned)(i * 5 + rank) << 32) |
-                                                                       (unsigned long long)(unsigned)(k0 + (1 << 30));
-                                        atomicMin(&k_sh.pc_best[p][cix[jj]], key);
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned long long tp3 = PROF ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        // ---- W: replay the reference loop
-        if (tid < 64) KPRIO_HI();
-        if (tid < n2) {
-            const int sa = k_sh.p2seg[tid];
-            BSeg &sg = b_sh.seg[sa];
-            int f = sg.score_f, r = sg.score_r, lf = sg.last_fwd, ph = 2, ci = 0;
-            const long long smax = 2LL * ((long long)pen.o1 * 2 + (long long)pen.e1 * (sg.max_ad + 1)) + 1024;
-            const BJob &bF = b_sh.job[2 * sa];
-            const BJob &bR = b_sh.job[2 * sa + 1];
-            const int kinv = bF.tlen - bF.plen;
-            while (ph == 2 && f <= avail) {
-                for (int half = lf ? 0 : 1; half < 2; half++) {
-                    // half 0: F@f against R <= r (then ++r);  half 1: R@r against F <= f (then ++f)
-                    const int score_0 = half ? r : f, score_1 = half ? f : r;
-                    const int min_1 = (score_1 > scope - 1) ? score_1 - (scope - 1) : 0;
-                    if (score_0 + min_1 - gap_opening >= sg.bp_score) { ph = 3; break; }
-                    const unsigned long long key = k_sh.pc_best[tid][ci++];
-                    if (key != ~0ull) {
-                        const int val = (int)(key >> 42) - gapmax;
-                        if (val < sg.bp_score) {
-                            const int ord = (int)((key >> 32) & 1023ull), i = ord / 5, rank = ord - i * 5;
-                            const int c = (rank == 0) ? SR_C_D2 : (rank == 1) ? SR_C_I2 : (rank == 2) ? SR_C_D1 : (rank == 3) ? SR_C_I1 : SR_C_M;
-                            const int k0 = (int)(unsigned)(key & 0xffffffffull) - (1 << 30), k1 = kinv - k0;
-                            const int score_i = score_1 - i;
-                            const BJob &b0 = half ? bR : bF;
-                            const BJob &b1 = half ? bF : bR;
-                            const int o0 = rcell<OT>(RR, KR(score_0, c), b0.base + b0.shift + k0);
-                            const int o1 = rcell<OT>(RR, KR(score_i, c), b1.base + b1.shift + k1);
-                            if (!half) {
-                                sg.bp_score_f = score_0; sg.bp_score_r = score_i;
-                                sg.bp_k_f = k0; sg.bp_k_r = k1; sg.bp_off_f = o0; sg.bp_off_r = o1;
-                            } else {
-                                sg.bp_score_f = score_i; sg.bp_score_r = score_0;
-                                sg.bp_k_f = k1; sg.bp_k_r = k0; sg.bp_off_f = o1; sg.bp_off_r = o0;
-                            }
-                            sg.bp_score = val;
-                            sg.bp_comp = c;
-                        }
-                    }
-                    if (half) ++f; else ++r;
-                }
-                if (ph != 2) break;
-                lf = 1;
-                if ((long long)f + r > smax) ph = 4;
-            }
-            sg.score_f = f; sg.score_r = r; sg.last_fwd = lf; sg.phase = ph;
-            if (ph != 2) {                                  // levels past the last one the search needed were surplus
-                const int last = min(avail, max(f, r));
-                const long long sur = blk_surplus(pen, 2 * sa, last, avail) + blk_surplus(pen, 2 * sa + 1, last, avail);
-                atomicAdd(&b_sh.cells, (unsigned long long)(-sur));
-            }
-        }
-        if (tid < 64) KPRIO_LO();
-        __syncthreads();
-        if (PROF && tid == 0) {
-            const unsigned long long tp4 = __builtin_amdgcn_s_memrealtime();
-            k_sh.t_p2a += tp1 - tp0; k_sh.t_p2f += tp2 - tp1; k_sh.t_p2e += tp3 - tp2; k_sh.t_p2w += tp4 - tp3;
-        }
-    }
-#undef KR
-}
-
-// ---- in-kernel orientation, default penalties (mismatch 1, gap-open 1, gap-extend 1, one piece): register blocks --------
-// Same scheme as sr_orient_blk_kernel (sr_orient.hip): a cell of level s depends on levels s-1, s-2 at diagonals k-1..k+1
-// only, so a wave tile keeps M[s-1], M[s-2], I[s-1], D[s-1] of its 4 diagonals per lane in registers and walks ORI_B levels
-// without touching memory (neighbours by DPP, one diagonal of halo per level and side: 2 lanes).  One workgroup pass = one
-// block of both aligners: 1/8 of the barriers and table set-ups of the level-per-pass version, rows read and written
-// once per block.  Rows of a block: {M last, M last-1, I last, D last} in ring slots chosen by the block's parity.
-#define ORI_B SR_ORI_B           // (one diagonal of halo per level and side: (ORI_B + 3) / 4 lanes; round 3: 8 levels.  The passes of an
-                                 // orientation are pure latency -- set-up, one or two tile rounds, three barriers -- and C3 / C5 spend
-                                 // 16 % / ~8 % of a pair in them: half as many passes)
-template <typename OT, int NT, typename ST>
-__device__ __forceinline__ void ori_pass8(const KRows<OT, ST> &R, const int s0, const SrPen &pen,
-                                          unsigned long long &cells_acc, unsigned &row_ld, unsigned &row_st) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    constexpr int HL = (ORI_B + 3) / 4, OWN = 64 - 2 * HL;
-    static_assert(ORI_B <= KB_LV && HL * 4 + 5 <= 24, "orientation block: level tables / the 24-cell margin of the orientation jobs hold the halo");
-    if (tid < 64) {
-        int nt = 0, glo = 0, ghi = -1, cells = 0;
-        if (tid < 2) {
-            const BJob &b = b_sh.job[tid];
-            int Rw = 0;
-#pragma unroll
-            for (int j = 0; j < ORI_B; j++) {
-                Rw = kreach<false, 1, 1>(pen, s0 + j, SR_C_M);
-                const int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
-                k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
-                k_sh.jreach[j][tid] = 0;
-                cells += (khi >= klo) ? khi - klo + 1 : 0;
-            }
-            // window of the block: the last level's range + one diagonal per level of the next block's reach + neighbours
-            const int wlo = max(-b.plen - 1, -Rw - ORI_B - 2), whi = min(b.tlen + 1, Rw + ORI_B + 2);
-            glo = (wlo + b.shift) >> 2; ghi = (whi + b.shift) >> 2;
-            nt = (ghi - glo + OWN) / OWN;
-            k_sh.jglo[tid] = glo; k_sh.jghi[tid] = ghi;
-        }
-        const int n0 = __shfl(nt, 0, 64), n1 = __shfl(nt, 1, 64);
-        if (tid == 0) { k_sh.jtstart[0] = 0; k_sh.jtstart[1] = n0; k_sh.total_tiles = n0 + n1; k_sh.next_tile = NT / 64; }
-        if (SR_LEAN_PASS) k_sh.cells_l[tid] += (unsigned long long)cells; else cells_acc += (unsigned long long)cells;
-    }
-    __syncthreads();
-    const int total = RFL(k_sh.total_tiles), n0 = RFL(k_sh.jtstart[1]);
-    const int par = (s0 / ORI_B) & 1;
-    // rows of the previous block (NULL row before the first one) and of this one
-    const unsigned pM1 = s0 ? krow_fix(R, SR_C_M, (1 - par) * 2) : R.nuloff;
-    const unsigned pM2 = s0 ? krow_fix(R, SR_C_M, (1 - par) * 2 + 1) : R.nuloff;
-    const unsigned pI = s0 ? krow_fix(R, SR_C_I1, 1 - par) : R.nuloff;
-    const unsigned pD = s0 ? krow_fix(R, SR_C_D1, 1 - par) : R.nuloff;
-    const unsigned oM1 = krow_fix(R, SR_C_M, par * 2), oM2 = krow_fix(R, SR_C_M, par * 2 + 1);
-    const unsigned oI = krow_fix(R, SR_C_I1, par), oD = krow_fix(R, SR_C_D1, par);
-    for (int t = (tid >> 6); t < total;) {
-        const int jid = t >= n0 ? 1 : 0, ti = t - (jid ? n0 : 0);
-        const BJob &jb = b_sh.job[jid];
-        const int base = RFL(jb.base), shift = RFL(jb.shift), plen = RFL(jb.plen), tlen = RFL(jb.tlen);
-        const int kend = RFL(jb.kend), poff = RFL(jb.poff), toff = RFL(jb.pad0);
-        const int glo = RFL(k_sh.jglo[jid]), ghi = RFL(k_sh.jghi[jid]);
-        const int g = glo + ti * OWN + lane - HL;
-        const bool owned = (lane >= HL) && (lane < 64 - HL) && (g <= ghi);
-        const int k0 = (g << 2) - shift;
-        const unsigned idx0 = klane(R, (unsigned)(base + (g << 2)));
-        const LP P = (LP)(lds_seq + poff), T = (LP)(lds_seq + toff);
-        const V4<OT> v1 = rld<OT>(R, pM1, idx0), v2 = rld<OT>(R, pM2, idx0), vi = rld_nt<OT>(R, pI, idx0), vd = rld_nt<OT>(R, pD, idx0);
-        {
-            const int nown = min(OWN, max(0, ghi - (glo + ti * OWN) + 1));
-            row_ld += 64u * 4u * (unsigned)(sizeof(ST) / 2); row_st += (unsigned)nown * 4u * (unsigned)(sizeof(ST) / 2);
-        }
-        int m1[4], m2[4], i1[4], d1[4];
-        unsigned lim[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            m1[q] = (int)v1[q]; m2[q] = (int)v2[q]; i1[q] = (int)vi[q]; d1[q] = (int)vd[q];
-            lim[q] = (unsigned)min(tlen, plen + k0 + q);
-        }
-        // LDS-wide symbol / bit index of P[-k0] and T[0] (the orientation aligners span the whole sequences)
-        const int cp0 = -k0 + (int)(((uint32_t)(uintptr_t)P >> 2) << SR_WIN_LOG), ct0 = (int)(((uint32_t)(uintptr_t)T >> 2) << SR_WIN_LOG);
-        const int cpb = cp0 << SR_SYM_LOG, ctb = ct0 << SR_SYM_LOG;
-#pragma unroll
-        for (int j = 0; j < ORI_B; j++) {
-            const int s = s0 + j;
-            const int klo = RFL(k_sh.jklo[j][jid]), khi = RFL(k_sh.jkhi[j][jid]);
-            int tiq[4], tdq[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) { tiq[q] = max(m2[q], i1[q]); tdq[q] = max(m2[q], d1[q]); }
-            const int tiL = lane_left(tiq[3]), tdR = lane_right(tdq[0]);
-            int mv[4], iv[4], dv[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int k = k0 + q;
-                const bool inr = (k >= klo) && (k <= khi);
-                int in_ = bnd(((q == 0) ? tiL : tiq[q == 0 ? 0 : q - 1]) + 1, lim[q]);
-                int dn_ = bnd((q == 3) ? tdR : tdq[q == 3 ? 3 : q + 1], lim[q]);
-                int m = bnd(m1[q] + 1, lim[q]);
-                m = max(m, max(in_, dn_));
-                if (!inr) { m = NULLV; in_ = NULLV; dn_ = NULLV; }
-                if (s == 0) { m = (inr && k == 0) ? 0 : NULLV; in_ = NULLV; dn_ = NULLV; }
-                mv[q] = m; iv[q] = in_; dv[q] = dn_;
-            }
-            // extension of every cell of the wave (halo lanes feed owned cells of later levels), as in blk_tile16: the eight
-            // window reads of the level are in flight together, a window is addressed by its LDS-wide bit index, a NULL
-            // cell runs through the same code (it stays negative and bnd() resets it at the next level).  Round 3; before,
-            // every cell waited for its own two reads.
-            unsigned long long pend[4];
-            {
-                uint32_t pl[4], ph[4], tl[4], th[4];
-                int bp[4], bt[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    bp[q] = (mv[q] << SR_SYM_LOG) + cpb - (q << SR_SYM_LOG); bt[q] = (mv[q] << SR_SYM_LOG) + ctb;
-                    win_words_bit(bp[q], pl[q], ph[q]); win_words_bit(bt[q], tl[q], th[q]);
-                }
-                asm volatile("; 8 windows in flight" : "+v"(pl[0]), "+v"(ph[0]), "+v"(pl[1]), "+v"(ph[1]), "+v"(pl[2]), "+v"(ph[2]), "+v"(pl[3]), "+v"(ph[3]),
-                                                        "+v"(tl[0]), "+v"(th[0]), "+v"(tl[1]), "+v"(th[1]), "+v"(tl[2]), "+v"(th[2]), "+v"(tl[3]), "+v"(th[3]));
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int nn = (int)lim[q] - mv[q];
-                    const uint32_t xw = __builtin_amdgcn_alignbit(ph[q], pl[q], (uint32_t)bp[q]) ^
-                                        __builtin_amdgcn_alignbit(th[q], tl[q], (uint32_t)bt[q]);
-                    const int ext_ = (int)min3u(ffs_sym(xw), (unsigned)SR_WIN, (unsigned)nn);
-                    mv[q] += ext_;
-                    pend[q] = __builtin_amdgcn_ballot_w64(ext_ == SR_WIN) & __builtin_amdgcn_ballot_w64(mv[q] >= 0);
-                }
-            }
-            while ((pend[0] | pend[1] | pend[2] | pend[3]) != 0ull) {        // runs longer than a window
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if (pend[q] == 0ull) continue;
-                    const int nn = lanes_or_zero(pend[q], (int)lim[q] - mv[q]);          // 0 for the lanes that are done
-                    const uint32_t xw = win_sym(mv[q] + cp0 - q) ^ win_sym(mv[q] + ct0);
-                    mv[q] += (int)min3u(ffs_sym(xw), (unsigned)SR_WIN, (unsigned)nn);
-                    pend[q] = __builtin_amdgcn_ballot_w64(xw == 0u && nn > SR_WIN);
-                }
-            }
-            bool reached = false;
-#pragma unroll
-            for (int q = 0; q < 4; q++) reached |= owned && (k0 + q) == kend && (k0 + q) >= klo && (k0 + q) <= khi && mv[q] >= tlen;
-            if (reached) k_sh.jreach[j][jid] = 1;
-#pragma unroll
-            for (int q = 0; q < 4; q++) { m2[q] = m1[q]; m1[q] = mv[q]; i1[q] = iv[q]; d1[q] = dv[q]; }
-        }
-        if (owned) {
-            V4<OT> a1, a2, ai, ad;
-#pragma unroll
-            for (int q = 0; q < 4; q++) { a1[q] = (OT)m1[q]; a2[q] = (OT)m2[q]; ai[q] = (OT)i1[q]; ad[q] = (OT)d1[q]; }
-            rst<OT>(R, oM1, idx0, a1); rst<OT>(R, oM2, idx0, a2); rst<OT>(R, oI, idx0, ai); rst<OT>(R, oD, idx0, ad);
-        }
-        int nx = 0;
-        if (lane == 0) nx = atomicAdd(&k_sh.next_tile, 1);
-        t = RFL(nx);
-    }
-}
+#include "sr_blk_rows.inc"      // LDS state, row storage and addressing, lane helpers
+#include "sr_blk_tile.inc"      // wave tiles
+#include "sr_blk_pass.inc"      // pass tables, tile queue, I/D recompute
+#include "sr_blk_phase2.inc"    // batched breakpoint detection
+#include "sr_blk_orient.inc"    // in-kernel orientation
 
 // Margins of an aligner's range in the shared rows: diagonal k lives at base + |p| + K_SHIFT0 + k so that the halo
 // lanes of the widest tile geometry (ceil(B / 4) groups: 7 = 28 diagonals for 25-level blocks, + the -|p| - 1 margin diagonal) stay
@@ -1883,7 +48,8 @@ __device__ __forceinline__ int kjob_width(int plen, int tlen) { return (plen + t
 // the orientation penalties run level by level (B = 1) and must be one-piece with gap-extend 1.
 // PROF: 100 MHz tick counters of the phases of a pair (counters[6..15]); only the instance SR_PROFILE_TICKS=1 selects
 // carries the s_memrealtime reads (they cost ~10 % of the wave cycles)
-// RT: storage type of the ring's cells (OT, or uint16_t = offset + 8192 for 32-bit searches below 57 k, see KRows)
+// RT: storage type of the ring's cells (OT, or uint16_t = offset - SR_RING_BIAS for 32-bit searches below 57 k, see KRows)
+#define SR_BLK_MIN_WAVES 4         // second __launch_bounds__ argument: the occupancy the kernel's registers are budgeted for
 template <typename OT, int NT, bool TWO, int B, int E1, int E2, bool PROF = false, int X = 0, int OE1 = 0, typename RT = OT>
 __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAlignArgs a) {
     const int tid = threadIdx.x;
@@ -1894,9 +60,8 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
     GP<uint32_t> clist = (GP<uint32_t>)a.bcl + (size_t)blockIdx.x * a.bcl_wg_stride;
     GP<int> gmak = (GP<int>)a.bmak + (size_t)blockIdx.x * (BJ_MAX * BFS_MAK_SLOTS);   // [aligner][level mod depth] max antidiagonal
     unsigned long long t_ori = 0, t_bp = 0, t_base = 0, t_all = 0, tb_bt = 0, tb_emit = 0;
-    unsigned long long tq_pass = 0, tq_bar = 0, tq_ctl = 0, tq_ph2 = 0, tq_tail = 0, tq_rec = 0, cells_acc = 0;
-    unsigned long long row_ld_acc = 0, row_st_acc = 0;
-    unsigned row_ld = 0, row_st = 0;                     // per pair, in lane accesses (flushed to the 64-bit sums per pair)
+    unsigned long long tq_pass = 0, tq_bar = 0, tq_ctl = 0, tq_ph2 = 0, tq_tail = 0, tq_rec = 0;
+    unsigned row_ld = 0, row_st = 0;                     // per pair, in lane accesses (flushed to the wave's sums in LDS per pair)
     const int depth = a.kdepth;
     // ring: chunk-major rows (see KRows); rows = 5 components x depth levels + NULL row + U row
     const int depth2 = a.kdepth2;
@@ -1926,12 +91,6 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             k_sh.bnd_flag = 0; k_sh.bnd_off = k_sh.bnd_ext = k_sh.bnd_what = 0; k_sh.lds_seq_bytes = 16u * a.max_words + 16u;
 #endif
             k_sh.dg_steps = k_sh.dg_nbase = k_sh.dg_nbp = k_sh.dg_npass = 0;
-#ifdef SR_TILE_STATS
-            for (int w_ = 0; w_ < 8; w_++) k_sh.ts[w_] = 0;
-#endif
-#ifdef SR_TILE_STAMPS
-            for (int w_ = 0; w_ < 16; w_++) { k_sh.st_wait[w_] = 0; k_sh.st_body[w_] = 0; k_sh.st_tiles[w_] = 0; k_sh.st_ext[w_] = 0; }
-#endif
             b_sh.geom.brow = a.brow; b_sh.geom.ring_scope = a.ring_scope; b_sh.geom.ring_hot = a.ring_hot;
             b_sh.geom.bbase_jobs = a.bbase_jobs; b_sh.geom.hist_w = a.hist_w; b_sh.geom.hist_levels = a.hist_levels;
             b_sh.geom.urow = urow;
@@ -1989,7 +148,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             }
             __syncthreads();
             for (int s0 = 0;; s0 += ORI_B) {
-                ori_pass8<OT, NT>(RR, s0, ori, cells_acc, row_ld, row_st);
+                ori_pass8<OT, NT>(RR, s0, ori, row_ld, row_st);
                 __syncthreads();
                 int hit = -1, who = 0;                         // per level the forward aligner is looked at first
 #pragma unroll
@@ -2016,7 +175,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             }
         } else {
             for (int s = 0;; s++) {
-                blk_pass<OT, false, NT, 1, 1, 1, PROF>(RR, s, ori, 2, cells_acc, row_ld, row_st);
+                blk_pass<OT, false, NT, 1, 1, 1, PROF>(RR, s, ori, 2, row_ld, row_st);
                 __syncthreads();
                 if (tid == 0) k_sh.dg_steps += 2ull;
                 const bool rf = RFL(k_sh.jreach[0][0]) != 0, rr = RFL(k_sh.jreach[0][1]) != 0;
@@ -2080,9 +239,9 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                 const unsigned long long tb0 = KTICK();
                 const int njobs = 2 * nact;
                 for (int s0i = 0; RFL(b_sh.nrunning) > 0; s0i += B) {
-                    const int s0 = SR_LEAN_PASS ? kopaque_s(s0i) : s0i;      // (no per-lane induction variables derived from the level across the pass)
+                    const int s0 = kopaque_s(s0i);      // (no per-lane induction variables derived from the level across the pass)
                     const unsigned long long q0 = KTICK();
-                    blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1, RT, true>(RR, s0, pen, njobs, cells_acc, row_ld, row_st, s0 == 0);
+                    blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1, RT, true>(RR, s0, pen, njobs, row_ld, row_st, s0 == 0);
                     const unsigned long long q1 = KTICK();
                     __syncthreads();
                     const unsigned long long q2 = KTICK();
@@ -2093,9 +252,9 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     // lane each), the set of segments in phase 2 and -- when there is none -- the pass's tail
                     const int tid_o = tid;
                     if (tid < 64) {
-                        // (SR_LEAN_CTL: the section's per-lane addresses -- the lane's max_ak slots, its segment record -- are formed from an
-                        //  opaque copy of the thread index, here, once per pass: hoisted out of the pass loop they lived, spilled, across the tiles)
-                        const int tid = SR_LEAN_CTL ? (int)kopaque_v((unsigned)tid_o) : tid_o;
+                        // (the section's per-lane addresses -- the lane's max_ak slots, its segment record -- are formed from an opaque
+                        //  copy of the thread index, here, once per pass: hoisted out of the pass loop they lived, spilled, across the tiles)
+                        const int tid = (int)kopaque_v((unsigned)tid_o);
                         KPRIO_HI();
                         if (tid < njobs) {
 #pragma unroll
@@ -2141,7 +300,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             if (tid < nact && ph != 1) { b_sh.job[2 * tid].active = 0; b_sh.job[2 * tid + 1].active = 0; }
                             if (tid == 0) b_sh.nrunning = __popcll(run);
                             // (the lanes' stores to job[].active above are read by other lanes below: same wave, LDS in order)
-                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs, cells_acc);   // tables of the next pass
+                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs);   // tables of the next pass
                         }
                         KPRIO_LO();
                     }
@@ -2165,14 +324,14 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             const unsigned long long run = __ballot(ph == 1 || ph == 2);
                             if (tid < nact && ph != 1 && ph != 2) { b_sh.job[2 * tid].active = 0; b_sh.job[2 * tid + 1].active = 0; }
                             if (tid == 0) b_sh.nrunning = __popcll(run);
-                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs, cells_acc);   // tables of the next pass
+                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs);   // tables of the next pass
                             KPRIO_LO();
                         }
                     }
                     const unsigned long long q4 = KTICK();
                     // (a pass without a recompute or breakpoint detection ends at the control section's barrier: its wave-0
                     // section already wrote the next pass's tables; round 4: one barrier less for most passes)
-                    if (SR_PASS_BARRIER3 || p2_or_rec) __syncthreads();
+                    if (p2_or_rec) __syncthreads();
                     tq_ph2 += q4 - q3; tq_tail += KTICK() - q4;
                     if (tid == 0) k_sh.dg_npass += 1ull;
                 }
@@ -2182,9 +341,6 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     GP<int> e = cur + (size_t)sg.list_pos * SR_BFS_SEGREC;
                     const int sp = sg.pe - sg.pb, st = sg.te - sg.tb;
                     const int bh = sg.bp_off_f, bv = sg.bp_off_f - sg.bp_k_f;
-    #ifdef SR_DBG_PRINT
-                    printf("bp seg %d: phase %d bp_score %d sf %d sr %d kf %d kr %d of %d or %d comp %d | f %d r %d\n", tid, sg.phase, sg.bp_score, sg.bp_score_f, sg.bp_score_r, sg.bp_k_f, sg.bp_k_r, sg.bp_off_f, sg.bp_off_r, sg.bp_comp, sg.score_f, sg.score_r);
-#endif
                     if (sg.phase != 3 || sg.bp_score == INT_MAX) atomicOr(&b_sh.err, SR_DEV_ERR_SCORE_BOUND);
                     else if (bv < 0 || bv > sp || bh < 0 || bh > st) atomicOr(&b_sh.err, SR_DEV_ERR_BREAKPOINT);
                     else { e[SL_BV] = bv; e[SL_BH] = bh; e[SL_BCOMP] = sg.bp_comp; e[SL_BSF] = sg.bp_score_f; e[SL_BSR] = sg.bp_score_r; }
@@ -2268,10 +424,6 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     }
                     b_sh.nbase = nb; b_sh.next_pos = p; b_sh.njobs = nb; b_sh.nrunning = nb;
                     b_sh.geom.hist_levels = lmax;
-#if defined(SR_DBG_PRINT) && SR_DBG_PRINT >= 2
-                    for (int z = 0; z < n_cur; z++) { GP<int> e = cur + (size_t)z * SR_BFS_SEGREC; printf("seg %d: p[%d,%d) t[%d,%d) cb %d ce %d rem %d kind %d\n", z, e[SL_PB], e[SL_PE], e[SL_TB], e[SL_TE], e[SL_CB], e[SL_CE], e[SL_REM], e[SL_KIND]); }
-                    printf("batch: nb %d pos %d next %d lmax %d\n", nb, pos, p, lmax);
-#endif
                 }
                 __syncthreads();
                 int nb = RFL(b_sh.nbase);
@@ -2280,9 +432,9 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     if (tid == 0) k_sh.dg_nbase += (unsigned long long)nb;
                     const int hlevels = RFL(b_sh.geom.hist_levels);
                     for (int s0i = 0; RFL(b_sh.nrunning) > 0; s0i += B) {
-                        const int s0 = SR_LEAN_PASS ? kopaque_s(s0i) : s0i;
+                        const int s0 = kopaque_s(s0i);
                         if (s0 + B > hlevels) { if (tid == 0) b_sh.err |= SR_DEV_ERR_BASE_OVERFLOW; break; }
-                        blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1>(RH, s0, pen, nb, cells_acc, row_ld, row_st, s0 == 0);
+                        blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1>(RH, s0, pen, nb, row_ld, row_st, s0 == 0);
                         __syncthreads();
                         if (tid == 0) k_sh.dg_steps += (unsigned long long)b_sh.nrunning * B;
                         if (tid < 64) {                          // one lane per base case: first level of the block that reached the end
@@ -2304,7 +456,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             }
                             const unsigned long long rm = __ballot(running);
                             if (tid == 0) b_sh.nrunning = __popcll(rm);
-                            if (rm != 0ull) blk_setup<TWO, NT, B, E1, E2>(s0 + B, pen, nb, cells_acc);   // tables of the next pass
+                            if (rm != 0ull) blk_setup<TWO, NT, B, E1, E2>(s0 + B, pen, nb);   // tables of the next pass
                             KPRIO_LO();
                         }
                         __syncthreads();
@@ -2325,9 +477,6 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                                                              btbuf + (size_t)tid * SR_BFS_BTCAP, &n);
                         b_sh.bt_n[tid] = n;
                         if (e) atomicOr(&b_sh.err, e);
-#if defined(SR_DBG_PRINT) && SR_DBG_PRINT >= 2
-                        printf("bt job %d score %d n %d err %d first %x last %x\n", tid, b_sh.base_score[tid], n, e, n ? (btbuf + (size_t)tid * SR_BFS_BTCAP)[0] : 0u, n ? (btbuf + (size_t)tid * SR_BFS_BTCAP)[n - 1] : 0u);
-#endif
                         KPRIO_LO();
                     }
                     __syncthreads();
@@ -2409,9 +558,6 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         }
         if (part) atomicAdd(&b_sh.score_acc, part);
         __syncthreads();
-#ifdef SR_DBG_PRINT
-        if (tid == 0) printf("pair %d: cnt %u score %d err %d fwd %d rev %d isrev %d\n", pair, cnt, b_sh.score_acc, b_sh.err, fwd, rev, is_rev);
-#endif
         if (tid == 0) {
             a.is_reverse[pair] = is_rev ? 1 : 0;
             a.score[pair] = b_sh.err ? -1 : b_sh.score_acc;
@@ -2446,23 +592,14 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             }
         }
         t_all += KTICK() - tk0;
-        if (SR_LEAN_PASS) {                                   // (the wave's 64-bit sums live in LDS, not in registers across the pairs)
-            if ((tid & 63) == 0) { k_sh.row_w[0][(tid >> 6) & 15] += row_ld; k_sh.row_w[1][(tid >> 6) & 15] += row_st; }
-        } else { row_ld_acc += row_ld; row_st_acc += row_st; }
+        // (the wave's 64-bit sums live in LDS, not in registers across the pairs)
+        if ((tid & 63) == 0) { k_sh.row_w[0][(tid >> 6) & 15] += row_ld; k_sh.row_w[1][(tid >> 6) & 15] += row_st; }
         row_ld = 0; row_st = 0;
     }
-#ifdef SR_TILE_STAMPS
-    __syncthreads();
-    if ((tid & 63) == 0) {
-        const int w_ = (tid >> 6) & 15;
-        atomicAdd(&a.counters[32], k_sh.st_wait[w_]); atomicAdd(&a.counters[33], k_sh.st_body[w_]);       // (own slots since round 4:
-        atomicAdd(&a.counters[34], k_sh.st_tiles[w_]); atomicAdd(&a.counters[35], k_sh.st_ext[w_]);        //  [25..28] are the control ticks)
-    }
-#endif
-    if (tid < 64 && (cells_acc + k_sh.cells_l[tid])) atomicAdd(&a.counters[0], cells_acc + k_sh.cells_l[tid]);
+    if (tid < 64 && k_sh.cells_l[tid]) atomicAdd(&a.counters[0], k_sh.cells_l[tid]);
     if ((tid & 63) == 0) {                       // row traffic of this wave's tiles, in bytes
         const unsigned long long lane_bytes = 8ull;           // (the tiles count 8-byte units: 4 cells of 2 bytes)
-        if (SR_LEAN_PASS) { row_ld_acc = k_sh.row_w[0][(tid >> 6) & 15]; row_st_acc = k_sh.row_w[1][(tid >> 6) & 15]; }
+        const unsigned long long row_ld_acc = k_sh.row_w[0][(tid >> 6) & 15], row_st_acc = k_sh.row_w[1][(tid >> 6) & 15];
         if (row_ld_acc) atomicAdd(&a.counters[16], row_ld_acc * lane_bytes);
         if (row_st_acc) atomicAdd(&a.counters[17], row_st_acc * lane_bytes);
     }
@@ -2475,9 +612,6 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         atomicAdd(&a.counters[19], k_sh.dg_f); atomicAdd(&a.counters[20], k_sh.dg_c);
         atomicAdd(&a.counters[21], k_sh.dg_e); atomicAdd(&a.counters[22], k_sh.dg_r);
         if (k_sh.dg_redo) atomicAdd(&a.counters[37], k_sh.dg_redo);
-#ifdef SR_TILE_STATS
-        for (int w_ = 0; w_ < 4; w_++) { atomicAdd(&a.counters[32 + w_], k_sh.ts[w_]); atomicAdd(&a.counters[44 + w_], k_sh.ts[4 + w_]); }
-#endif
         if (PROF) {
             if (!a.pre_oriented) atomicAdd(&a.counters[6], t_ori);    // ([6] holds sr_orient_kernel's cells otherwise)
             atomicAdd(&a.counters[7], t_bp);

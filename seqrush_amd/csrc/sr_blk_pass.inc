@@ -1,0 +1,173 @@
+// sr_blk_pass.inc -- blocked kernel (sr_align_blk.inc), part 3: a pass over a block of levels -- reach and tile windows
+// (kreach, kwindow), the pass tables (blk_setup), the tile queue (blk_pass), the I/D recompute pass (blk_recompute).
+// reach() with compile-time gap-extends (the host guarantees pen.e1 == E1, pen.e2 == E2): no runtime division
+template <bool TWO, int E1, int E2>
+__device__ __forceinline__ int kreach(const SrPen &p, int s, int begin) {
+    int r;
+    if (begin == SR_C_M) {
+        r = (s >= p.o1 + E1) ? (s - p.o1) / E1 : 0;
+        if (TWO && s >= p.o2 + E2) r = max(r, (s - p.o2) / E2);
+    } else {
+        r = s / E1;
+        if (TWO) r = max(r, s / E2);
+    }
+    return r;
+}
+
+// Groups [glo, ghi] the tiles of block s0 (levels s0 .. s0+B-1) of aligner b cover -- and store.
+//  * wide (round 1-3, still used by base-case histories and the generic instances): the last level's range + scope + 1
+//    diagonals either side, so that every later reader (levels up to scope + B above, one neighbour diagonal) finds NULL
+//    beyond the range instead of whatever the ring slot held before: 2 (scope + 1) = 54 extra diagonals per aligner and
+//    level for the default penalties -- 9 % of all tile lanes on C2, more the deeper the recursion (narrow segments).
+//  * TIGHT (round 4, ring tiles of the exact instance): the last level's range + the one neighbour diagonal.  What lies
+//    outside is never written and may hold anything; a tile that reads a source block (s0 - B: M[s - o1 - e1], M[s - x], the
+//    chain sources; the one or two blocks M[s - o2 - e2] comes from) masks the lanes outside THAT block's coverage to NULL
+//    (blk_tile16: `in10 / in2a / in2b`; a tile whose 64 lanes lie inside the narrowest source coverage skips the masks),
+//    breakpoint detection tests every cell against its level's range anyway.
+template <bool TWO, int B, int E1, int E2, bool TIGHT>
+__device__ __forceinline__ void kwindow(const SrPen &pen, const BJob &b, int s0, int &glo, int &ghi) {
+    const int Rw = kreach<TWO, E1, E2>(pen, s0 + B - 1, b.begin);
+    const int mg = TIGHT ? 1 : pen.scope + 1;
+    const int wlo = max(-b.plen - 1, -Rw - mg), whi = min(b.tlen + 1, Rw + mg);
+    glo = (wlo + b.shift) >> 2; ghi = (whi + b.shift) >> 2;
+}
+
+// One pass: levels s0 .. s0+B-1 of every active aligner.  Ends with the data of the
+// pass still in flight: the caller's __syncthreads() publishes rows and reductions.
+#define KTICK() (PROF ? __builtin_amdgcn_s_memrealtime() : 0ull)
+// Sections that one wave (or one lane) runs while the workgroup's other waves wait at the barrier are the pair's critical
+// path, and the SIMD they run on is shared with three waves of other workgroups that are usually in their tiles: raised
+// issue priority (s_setprio) lets the lone wave through first; back to 0 before the barrier.
+#define KPRIO_HI() __builtin_amdgcn_s_setprio(3)
+#define KPRIO_LO() __builtin_amdgcn_s_setprio(0)
+// Tables of one pass (levels s0 .. s0+B-1 of every active aligner): wave 0, one lane per aligner.  The first pass of a batch
+// of searches runs it inside blk_pass; later passes get their tables from the wave-0 section that ends the previous pass
+// (control, or the section after breakpoint detection), so a pass costs one barrier and one serial hop less.
+template <bool TWO, int NT, int B, int E1, int E2, bool TIGHT = false>
+__device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs) {
+    const int tid = threadIdx.x;                         // (tid < 64)
+    int nt = 0, glo = 0, ghi = -1, cells = 0;
+    const bool act = tid < njobs && b_sh.job[tid].active;
+    const int pglo = (tid < BJ_MAX) ? k_sh.jglo[tid] : 0, pghi = (tid < BJ_MAX) ? k_sh.jghi[tid] : -1;
+    if (act) {
+        const BJob &b = b_sh.job[tid];
+        int Rw = 0;
+#pragma unroll
+        for (int j = 0; j < B; j++) {
+            Rw = kreach<TWO, E1, E2>(pen, s0 + j, b.begin);
+            const int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
+            k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
+            cells += (khi >= klo) ? khi - klo + 1 : 0;
+        }
+        (void)Rw;
+        kwindow<TWO, B, E1, E2, TIGHT>(pen, b, s0, glo, ghi);
+        nt = (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN;
+    }
+    // (jmerge, jband, jbandown, nband and the second prefix sum are what is left of two round-4 experiments that stayed off,
+    // merged tail tiles and the band-first tile order (profiles/r04_ab.log, DESIGN.md section 7): no tile is merged, the
+    // queue holds no band tile)
+    int incl = nt, hincl = 0;                          // prefix sums: tiles, aligners with a band tile
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64), h = __shfl_up(hincl, o, 64);
+        if (tid >= o) { incl += v; hincl += h; }
+    }
+    if (tid < BJ_MAX) {
+        k_sh.jglo[tid] = glo; k_sh.jghi[tid] = ghi;
+        k_sh.jgplo[tid] = pglo; k_sh.jgphi[tid] = pghi;
+        k_sh.jtstart[tid + 1] = incl;
+        k_sh.jmerge[tid] = 0;
+        k_sh.jband[tid] = INT_MAX / 2;
+#pragma unroll
+        for (int j = 0; j < B; j++) { k_sh.jak[j][tid] = 0; k_sh.jreach[j][tid] = 0; }
+    }
+    if (tid == 0) k_sh.jtstart[0] = 0;
+    if (tid == 63) { k_sh.nband = hincl; k_sh.total_tiles = incl + hincl; k_sh.next_tile = NT / 64; }
+    k_sh.cells_l[tid] += (unsigned long long)cells;      // (tid < 64)
+}
+
+template <typename OT, bool TWO, int NT, int B, int E1, int E2, bool PROF, int X = 0, int OE1 = 0, typename ST = OT, bool RING = false>
+__device__ __forceinline__ void blk_pass(const KRows<OT, ST> &R, int s0, const SrPen &pen, int njobs,
+                                         unsigned &row_ld, unsigned &row_st, const bool setup = true) {
+    const int tid = threadIdx.x;
+    if (setup) {
+        const unsigned long long tsu0 = KTICK();
+        if (tid < 64) blk_setup<TWO, NT, B, E1, E2, RING && KTIGHT_OF(OT, ST, B, X)>(s0, pen, njobs);
+        __syncthreads();
+        if (PROF && threadIdx.x == 0) k_sh.t_setup += KTICK() - tsu0;
+    }
+    const int total = RFL(k_sh.total_tiles);
+    const int slot0 = kslots(R, s0);
+    // Tiles differ in cost (extension loops, edge tiles): every wave takes its first tile by index and the following
+    // ones from a queue, so that the pass ends when the work does and not when the unluckiest wave's share does.
+    const int nband = RFL(k_sh.nband);
+    for (int t = (tid >> 6); t < total;) {
+        int lo, ti;
+        if (t < nband) { lo = RFL(k_sh.jbandown[t]); ti = RFL(k_sh.jband[lo]); }      // the band tiles first
+        else {
+            const int r = t - nband;
+            int hi = njobs; lo = 0;                 // last aligner with jtstart <= r (wave-uniform; jtstart counts the tiles but the band tile)
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (RFL(k_sh.jtstart[mid]) <= r) lo = mid; else hi = mid; }
+            ti = r - RFL(k_sh.jtstart[lo]);
+            ti += (ti >= RFL(k_sh.jband[lo])) ? 1 : 0;
+        }
+        blk_tile_any<OT, TWO, B, E1, E2, false, X, OE1, ST, RING>(R, s0, slot0, pen, lo, ti, lo, row_ld, row_st);
+        int nx = 0;
+        if ((tid & 63) == 0) nx = atomicAdd(&k_sh.next_tile, 1);
+        t = RFL(nx);
+    }
+}
+
+// Segment sa has just entered phase 2: recompute and store the I/D rows of the levels breakpoint detection will
+// read (the scope window below the entry level, up to the end of the current block), block by block from the last
+// block boundary before the window -- its chain sources, the previous block's last e levels, are always stored.
+// Needs the M rows down to (window start - scope): ring depth >= 2 * scope + 2 * B + 2.
+template <typename OT, bool TWO, int NT, int B, int E1, int E2, int X = 0, int OE1 = 0, typename ST = OT>
+__device__ __forceinline__ void blk_recompute(const KRows<OT, ST> &R, const SrPen &pen, int sa, int entry_level, int s0_now,
+                                              unsigned &row_ld, unsigned &row_st) {
+    const int tid = threadIdx.x;
+    const int wlo = max(0, entry_level - pen.scope);
+    for (int blk = (wlo / B) * B; blk <= s0_now; blk += B) {
+        __syncthreads();
+        if (tid < 2) {
+            const BJob &b = b_sh.job[2 * sa + tid];
+            int Rw = 0;
+#pragma unroll
+            for (int j = 0; j < B; j++) {
+                Rw = kreach<TWO, E1, E2>(pen, blk + j, b.begin);
+                k_sh.jklo[j][BJ_MAX + tid] = max(-b.plen, -Rw); k_sh.jkhi[j][BJ_MAX + tid] = min(b.tlen, Rw);
+            }
+            (void)Rw;
+            int glo, ghi;
+            kwindow<TWO, B, E1, E2, KTIGHT_OF(OT, ST, B, X)>(pen, b, blk, glo, ghi);      // (the coverage the block's own pass had)
+            const bool first = blk == (wlo / B) * B;        // U starts from NULL in the first recompute block
+            k_sh.jgplo[BJ_MAX + tid] = first ? 1 : k_sh.jglo[BJ_MAX + tid];
+            k_sh.jgphi[BJ_MAX + tid] = first ? 0 : k_sh.jghi[BJ_MAX + tid];
+            k_sh.jglo[BJ_MAX + tid] = glo; k_sh.jghi[BJ_MAX + tid] = ghi;
+            const int nt = (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN;
+            const int n0 = __shfl(nt, 0, 64), n1 = __shfl(nt, 1, 64);
+            if (tid == 0) { k_sh.rt_n0 = n0; k_sh.rt_total = n0 + n1; }
+        }
+        __syncthreads();
+        const int n0 = RFL(k_sh.rt_n0), total = RFL(k_sh.rt_total);
+        const int slot0 = kslots(R, blk);
+        for (int t = (tid >> 6); t < total; t += NT / 64) {
+            const int side = (t >= n0) ? 1 : 0;
+            blk_tile_any<OT, TWO, B, E1, E2, true, X, OE1, ST, true>(R, blk, slot0, pen, 2 * sa + side, t - (side ? n0 : 0), BJ_MAX + side, row_ld, row_st);
+        }
+    }
+    __syncthreads();
+    if (tid < 2) b_sh.job[2 * sa + tid].pad2 = 1;           // from now on the search stores its I/D rows
+}
+
+// cells of levels (l0, l1] of aligner jid -- work a block computed past the aligner's last level
+__device__ __forceinline__ long long blk_surplus(const SrPen &pen, int jid, int l0, int l1) {
+    const BJob &b = b_sh.job[jid];
+    long long c = 0;
+    for (int l = l0 + 1; l <= l1; l++) {
+        const int Rw = reach(pen, l, b.begin);
+        const int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
+        c += (khi >= klo) ? khi - klo + 1 : 0;
+    }
+    return c;
+}

@@ -123,17 +123,12 @@ struct GroupIn {
 };
 
 // ---- batched window reads of the blocked tiles (sr_align_blk.inc, sr_orient.hip) ----------------------------------
-#ifndef SR_LDS_WRAP
-#define SR_LDS_WRAP 0x1fffcu
-#endif
-#ifndef SR_NULL_NOEXT
-#define SR_NULL_NOEXT 0           // diagnostic builds (scripts/lds_oob): a cell below 0 gains nothing from its windows
-#endif
+#define SR_LDS_WRAP 0x1fffcu      // word-aligned addresses in the first 128 KB of LDS
 // SR_WIN symbols starting at LDS-wide symbol index S (symbol 0 = the low bits of the word at LDS address 0)
 __device__ __forceinline__ uint32_t win_sym(int S) {
     typedef uint32_t __attribute__((ext_vector_type(2), aligned(4))) W2;
     // (the mask aligns the address to a word and wraps it into the first 128 KB: a cell that does not extend may point
-    // anywhere.  Reads beyond the workgroup's allocation return 0 and disturb nothing -- scripts/lds_oob)
+    // anywhere.  Reads beyond the workgroup's allocation return 0 and disturb nothing -- profiles/r03_lds_oob.log)
     const uint32_t addr = ((uint32_t)S >> (SR_WIN_LOG - 2)) & SR_LDS_WRAP;
     const W2 w = *(const W2 __attribute__((address_space(3))) *)(uintptr_t)addr;
     return __builtin_amdgcn_alignbit(w.y, w.x, (uint32_t)S << SR_SYM_LOG);
@@ -141,8 +136,7 @@ __device__ __forceinline__ uint32_t win_sym(int S) {
 // the two words win_sym() takes its window from
 __device__ __forceinline__ void win_words(int S, uint32_t &lo, uint32_t &hi) {
     typedef uint32_t __attribute__((ext_vector_type(2), aligned(4))) W2;
-    // (the mask aligns the address to a word and wraps it into the first 128 KB: a cell that does not extend may point
-    // anywhere.  Reads beyond the workgroup's allocation return 0 and disturb nothing -- scripts/lds_oob)
+    // (the mask aligns the address to a word and wraps it into the first 128 KB, as in win_sym)
     const uint32_t addr = ((uint32_t)S >> (SR_WIN_LOG - 2)) & SR_LDS_WRAP;
     const W2 w = *(const W2 __attribute__((address_space(3))) *)(uintptr_t)addr;
     lo = w.x; hi = w.y;

@@ -38,7 +38,6 @@ static const SrKnob SR_KNOBS[] = {
     {"SR_ALIGN_THREADS", "by pairs per CU", "threads per workgroup: 64 | 128 | 256 | 512 | 1024"},
     {"SR_WG_PER_CU", "4", "workgroups per CU the launch is sized for"},
     {"SR_NWG", "CUs x workgroups per CU", "cap on workgroups (several pairs per workgroup on small inputs)"},
-    {"SR_STATIC_LDS_KB", "23-33 / 28 / 6", "static LDS of the kernel assumed when sizing workgroups per CU (A/B builds with other tables)"},
     {"SR_RING_U16", "1 below 57 k", "0 = 32-bit searches keep 32-bit ring rows"},
     {"SR_LAZY_ID", "1", "0 = searches store their I/D rows from the first level (no recompute pass)"},
     {"SR_HIST_JOBS", "4", "worst-case base cases the per-workgroup history holds (1..16)"},
@@ -704,8 +703,7 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     if (impl == 2 && (uint64_t)np <= (uint64_t)cus) c->nthreads = 1024;
     if (const char *e = knob("SR_ALIGN_THREADS")) {
         const int v = atoi(e);
-        if (v == 128 || v == 256 || v == 512 || (v == 1024 && impl == 2) || (v == 64 && impl == 2 && bits == 2) ||
-            (v == 192 && impl == 2 && kblock == 10 && c->off16 && bits == 2 && pen.two)) c->nthreads = v;   // (192: experiment builds only, -DSR_NT192)
+        if (v == 128 || v == 256 || v == 512 || (v == 1024 && impl == 2) || (v == 64 && impl == 2 && bits == 2)) c->nthreads = v;
     }
     if (c->nthreads == 1024 && !(impl == 2 && kblock == 10 && c->off16 && bits == 2 && pen.two)) c->nthreads = 512;   // (the one 1024-thread build)
     if (impl == 2 && c->nthreads == 128 && kblock == 10 && !(bits == 2 && c->off16)) kblock = 5;   // (no 128-thread 10-level instance there)
@@ -714,7 +712,6 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     // static tables of the kernel (upper estimates; the blocked kernel's scan arrays of the fused unite grow with the
     // workgroup: 23 416 / 26 536 / 32 776 bytes at 256 / 512 / 1024 threads)
     auto static_lds = [&](int nthreads) -> size_t {
-        if (const char *e = knob("SR_STATIC_LDS_KB")) return (size_t)std::max(1, atoi(e)) * 1024;       // (A/B builds with other table sizes)
         return (size_t)(pl.wave_wg ? 6 : impl != 2 ? 28 : nthreads >= 1024 ? 33 : nthreads >= 512 ? 26 : 23) * 1024;
     };
     const size_t lds_per_wg = c->lds_bytes + static_lds(c->nthreads);
@@ -726,7 +723,7 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     const bool u16_ok = kblock == 10 && maxlen <= 57000 && !(ru && atoi(ru) == 0);
     if (impl == 2 && !pl.wave_wg && pl.wg_per_cu <= 2 && !knob("SR_ALIGN_THREADS") && (c->off16 || u16_ok)) c->nthreads = 512;
     pl.wg_per_cu = (int)std::min<size_t>((size_t)pl.wg_per_cu, std::max<size_t>(1, (160 * 1024) / (c->lds_bytes + static_lds(c->nthreads))));
-    // 32-bit searches below 57 k keep their ring as uint16 (offset + 8192): half the row bytes (C5 is bound by them).
+    // 32-bit searches below 57 k keep their ring as 16-bit cells (offset - 24576): half the row bytes (C5 is bound by them).
     // The exact 10-level instance at >= 256 threads has that build; SR_RING_U16=0 keeps 32-bit rows.
     pl.ring_u16 = (impl == 2 && !c->off16 && u16_ok && c->nthreads >= 256) ? 1 : 0;
     pl.rsz = pl.ring_u16 ? 2 : pl.osz;                 // bytes per ring cell (the base-case history keeps osz)

@@ -94,7 +94,7 @@ struct SrAlignArgs {
                                //   (kdepth >= 2 * scope + 2 * block + 2 so that they can be recomputed)
     int profile_ticks;         // impl 2: launch the instrumented instance (SR_PROFILE_TICKS=1)
     int ori_levels;            // impl 2: in-kernel orientation level by level even for the default penalties (SR_ORIENT_LEVELS=1)
-    int ring_u16;              // impl 2, 32-bit searches: the ring's cells are uint16 = offset + 8192 (longest sequence < 57 k)
+    int ring_u16;              // impl 2, 32-bit searches: the ring's cells are 16-bit = offset - 24576 (longest sequence < 57 k)
     int *bmak;                 // impl 2: per workgroup [32 aligners][32 ring levels] max M antidiagonal (breakpoint pruning)
     int test_base_levels;      // impl 2, tests only (SR_TEST_BASE_LEVELS=n): cap on the levels a base case is given at first, so that
                                //   jobs outgrow their region and take the re-queue path
