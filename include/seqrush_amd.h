@@ -257,6 +257,45 @@ int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap);
  * are set are listed under "knobs" in sr_ctx_workspace_report() */
 const char *sr_knobs_doc(void);
 
+/* -------- iterative mode (`seqrush --iterative`, align_and_unite_iterative src/seqrush.rs:867-1132) ---------------
+ * Tree entries ({i<j} picked by the k-NN selection of -x tree:, row-major) are aligned and united first; then the random
+ * entries (the other pairs of the tree: list, in a seeded shuffle, sr_host.cpp "pair list") in chunks of 10, with a
+ * component count after every full chunk; the run stops once 10 checks in a row saw no change (:1034-1122).  Each entry
+ * aligns (i,i) (i,j) (j,i) (j,j).  A -x other than tree: is replaced by tree:3,3,0.1,16 (tree_defaulted).  One context,
+ * no shards.  The union-find holds exactly the processed alignments; the stop point does not depend on the schedule. */
+typedef struct {
+    uint64_t tree_entries;      /* unordered tree pairs (4 alignments each) */
+    uint64_t random_entries;    /* unordered random pairs */
+    uint64_t random_processed;  /* random entries united: 10 per check up to the stop, or all */
+    uint64_t random_aligned;    /* random entries aligned (the last window may hold entries after the stop) */
+    uint64_t checks;            /* component counts taken in phase 2 */
+    uint64_t windows;           /* phase-2 alignment windows */
+    uint64_t post_tree;         /* components after phase 1 */
+    uint64_t final_components;  /* components at the end */
+    int32_t stabilized;         /* 1 = the stop rule fired */
+    int32_t tree_defaulted;     /* 1 = -x was not tree:, tree:3,3,0.1,16 was used */
+    uint32_t tree_k_nearest, tree_k_farthest;   /* the tree spec used */
+    double tree_rand_frac;
+    uint32_t tree_kmer;
+    uint32_t reserved;
+} sr_iter_stats;
+/* sequences + the two lists (k-NN selection on the device); keep_alignments != 0: sr_ctx_iterative_alignments afterwards */
+int sr_ctx_load_iterative(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, int keep_alignments);
+/* both phases to the end (host syncs once per window; a second run starts again from SeqRush::new) */
+int sr_ctx_run_iterative(sr_ctx *c);
+/* stats of the last run + its per-check component counts (up to cap entries; NULL = skip) */
+int sr_ctx_iterative_stats(sr_ctx *c, sr_iter_stats *out, uint64_t *check_counts, uint64_t cap);
+/* the processed alignments of the last run in processing order (--output-alignments); ownership passes to the caller
+ * (sr_alignments_free), so a second call fails until the next run */
+int sr_ctx_iterative_alignments(sr_ctx *c, sr_alignments **out);
+/* host twins (no device): count_components (:341-353) of a SeqRush node array = roots among nodes [0, 2 total_len);
+ * the stop rule over per-check counts (*stop_check = checks consumed when it fired, 0 = never); the two entry lists for a
+ * given n*n k-NN selection (sel[i*n+j] = j picked by i; NULL = none) -- free the four arrays with sr_free */
+int sr_uf_count_components_host(const uint64_t *nodes, uint64_t n, uint64_t total_len, uint64_t *count);
+int sr_iterative_stop_host(const uint64_t *counts, uint64_t nchecks, uint64_t post_tree, uint64_t *stop_check);
+int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, uint32_t **tree_i, uint32_t **tree_j,
+                            uint64_t *tree_count, uint32_t **rand_i, uint32_t **rand_j, uint64_t *rand_count);
+
 /* -------- consumer (A9): graph induction + GFA, host C++ -----------------
  * build_bidirected_graph_with_options (bidirected_builder.rs:17-289) +
  * write_gfa (bidirected_ops.rs:880-925) for --no-sort --no-compact, from

@@ -31,6 +31,8 @@ def main(argv=None):
     ap.add_argument("--skip-groom", action="store_true")
     ap.add_argument("--skip-topo", action="store_true")
     ap.add_argument("--aligner", default="allwave")
+    ap.add_argument("--iterative", action="store_true",
+                    help="tree pairs first, then random pairs in chunks of 10 until 10 component counts in a row are unchanged")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -38,6 +40,10 @@ def main(argv=None):
     ns = ap.parse_args(argv)
     if ns.sort and ns.no_sort:
         print("Error: --sort and --no-sort exclude each other", file=sys.stderr)
+        return 1
+    if ns.iterative and (ns.paf is not None or ns.gpus > 1):
+        # before any rank starts: the stop rule is global and sequential, and -p has no alignment stage to stop
+        print(f"Error: --iterative cannot be combined with {'-p' if ns.paf is not None else '--gpus N > 1'}", file=sys.stderr)
         return 1
     if ns.gpus > 1 and "RANK" not in os.environ:
         # start one process per GPU BEFORE anything here touches the GPU (never exec from a process that has)
@@ -53,7 +59,7 @@ def main(argv=None):
                 output_alignments=ns.output_alignments, no_compact=ns.no_compact, no_sort=ns.no_sort,
                 sort=ns.sort, sort_seed=ns.sort_seed, sgd_iter_max=ns.sgd_iter_max, skip_sgd=ns.skip_sgd,
                 skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
-                aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus)
+                aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

@@ -28,6 +28,8 @@ EXPORTS = [
     "sr_uf_init_host", "sr_uf_unite_host", "sr_uf_merge_labels_host", "sr_uf_canonical_labels_host",
     "sr_build_gfa_from_nodes", "sr_ctx_counters_all", "sr_knobs_doc",
     "sr_sort_params_default", "sr_ctx_build_gfa_sorted", "sr_sort_gfa", "sr_sgd_layout", "sr_sgd_tables", "sr_sort_stats",
+    "sr_ctx_load_iterative", "sr_ctx_run_iterative", "sr_ctx_iterative_stats", "sr_ctx_iterative_alignments",
+    "sr_uf_count_components_host", "sr_iterative_stop_host", "sr_iterative_pair_lists",
 ]
 
 
@@ -60,6 +62,17 @@ class SortParamsC(C.Structure):
         ("eta_max", C.c_double), ("cooling_start", C.c_double), ("space", C.c_uint64), ("space_max", C.c_uint64),
         ("space_quant", C.c_uint64), ("min_term_updates", C.c_uint64), ("terms_per_round", C.c_uint64),
         ("skip_sgd", C.c_int32), ("skip_groom", C.c_int32), ("skip_topo", C.c_int32), ("device", C.c_int32),
+    ]
+
+
+class IterStatsC(C.Structure):
+    """sr_iter_stats (include/seqrush_amd.h, iterative mode)"""
+    _fields_ = [
+        ("tree_entries", C.c_uint64), ("random_entries", C.c_uint64), ("random_processed", C.c_uint64),
+        ("random_aligned", C.c_uint64), ("checks", C.c_uint64), ("windows", C.c_uint64), ("post_tree", C.c_uint64),
+        ("final_components", C.c_uint64), ("stabilized", C.c_int32), ("tree_defaulted", C.c_int32),
+        ("tree_k_nearest", C.c_uint32), ("tree_k_farthest", C.c_uint32), ("tree_rand_frac", C.c_double),
+        ("tree_kmer", C.c_uint32), ("reserved", C.c_uint32),
     ]
 
 
@@ -155,6 +168,15 @@ def load():
     L.sr_sort_stats.argtypes = [PD, C.c_uint32]
     L.sr_pair_list.argtypes = [C.c_uint32, PP, C.POINTER(C.POINTER(C.c_uint32)),
                                C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]
+    L.sr_ctx_load_iterative.argtypes = [vp, PS, PP, i32]
+    L.sr_ctx_run_iterative.argtypes = [vp]
+    L.sr_ctx_iterative_stats.argtypes = [vp, C.POINTER(IterStatsC), C.POINTER(u64), u64]
+    L.sr_ctx_iterative_alignments.argtypes = [vp, C.POINTER(C.POINTER(AlignmentsC))]
+    L.sr_uf_count_components_host.argtypes = [C.POINTER(u64), u64, u64, C.POINTER(u64)]
+    L.sr_iterative_stop_host.argtypes = [C.POINTER(u64), u64, u64, C.POINTER(u64)]
+    PU32 = C.POINTER(C.POINTER(C.c_uint32))
+    L.sr_iterative_pair_lists.argtypes = [C.c_uint32, C.POINTER(C.c_uint8), PP, PU32, PU32, C.POINTER(u64), PU32, PU32,
+                                          C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

@@ -2,6 +2,7 @@
 // (src/main.rs:4-7, Args src/seqrush.rs:17-152, run_seqrush :1839-1853, load_sequences :1801-1837).
 // Everything that computes goes through include/seqrush_amd.h; output is the --no-sort graph or, with --sort, the Ygs
 // layout (sr_ctx_build_gfa_sorted), compacted unless --no-compact.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,10 +51,33 @@ static uint64_t fnv1a(const void *data, size_t n, uint64_t h = 0xcbf29ce48422232
     return h;
 }
 
+// an f64 the way Rust's Display prints it (the reference's messages): shortest round-trip digits, positional, "50" for 50.0
+static std::string rust_f64(double x) {
+    if (std::isnan(x)) return "NaN";
+    if (std::isinf(x)) return x < 0 ? "-inf" : "inf";
+    char buf[64];
+    for (int prec = 1; prec <= 17; prec++) {
+        snprintf(buf, sizeof(buf), "%.*e", prec - 1, x);
+        if (strtod(buf, nullptr) == x) break;
+    }
+    std::string s(buf);
+    const bool neg = s[0] == '-';
+    if (neg) s = s.substr(1);
+    const size_t e = s.find('e');
+    const int point = atoi(s.c_str() + e + 1) + 1;           // digits before the decimal point
+    std::string digits, out;
+    for (size_t i = 0; i < e; i++) if (s[i] != '.') digits += s[i];
+    if (point <= 0) out = "0." + std::string((size_t)-point, '0') + digits;
+    else if ((size_t)point >= digits.size()) out = digits + std::string((size_t)point - digits.size(), '0');
+    else out = digits.substr(0, (size_t)point) + "." + digits.substr((size_t)point);
+    if (out.find('.') != std::string::npos) { while (out.back() == '0') out.pop_back(); if (out.back() == '.') out.pop_back(); }
+    return (neg ? "-" : "") + out;
+}
+
 static void usage() {
     fprintf(stderr, "usage: seqrush_mi355x -s in.fa [-o output.gfa] [-k 0] [-S 0,5,8,2,24,1] [--orientation-scores 0,1,1,1]\n"
                     "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--device N]\n"
-                    "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo]\n"
+                    "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
@@ -63,7 +87,7 @@ int main(int argc, char **argv) {
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
-    bool no_sort = false, no_compact = false, sort = false;
+    bool no_sort = false, no_compact = false, sort = false, iterative = false, verbose = false;
     sr_sort_params sp;
     sr_sort_params_default(&sp);
     // multi-GPU without a collective library in this host: every process aligns one shard (--shard R/N) and writes its
@@ -101,10 +125,17 @@ int main(int argc, char **argv) {
         else if (a == "--shard") { if (sscanf(val("--shard"), "%u/%u", &shard_rank, &shard_count) != 2 || shard_count == 0 || shard_rank >= shard_count) { fprintf(stderr, "error: --shard R/N\n"); return 2; } }
         else if (a == "--labels-out") labels_out = val("--labels-out");
         else if (a == "--labels-in") labels_in.push_back(val("--labels-in"));
-        else if (a == "-v" || a == "--verbose") {}
+        else if (a == "-v" || a == "--verbose") verbose = true;
+        else if (a == "--iterative") iterative = true;
         else { usage(); return 2; }
     }
     if (sequences.empty()) { usage(); return 2; }
+    // the stop rule of --iterative is global and sequential: no shards, no merge of shard labels, no PAF replay
+    if (iterative && (!paf_in.empty() || shard_count > 1 || !labels_out.empty() || !labels_in.empty())) {
+        fprintf(stderr, "Error: --iterative cannot be combined with %s\n",
+                !paf_in.empty() ? "-p" : !labels_in.empty() ? "--labels-in" : "--shard / --labels-out");
+        return 1;
+    }
     if (shard_count > 1 && labels_out.empty()) {
         fprintf(stderr, "Error: --shard %u/%u aligns a part of the pair list only: give --labels-out and merge the parts with --labels-in "
                         "(a graph of one shard would be silently incomplete)\n", shard_rank, shard_count);
@@ -139,7 +170,7 @@ int main(int argc, char **argv) {
         input_hash = fnv1a(cfg.data(), cfg.size(), input_hash);
     }
     printf("Building graph with %zu sequences (total length: %zu)\n", seqs.size(), bases.size());
-    printf("Total sequence pairs: %zu (sparsification: %s)\n", seqs.size() * seqs.size(), sparsify.c_str());
+    if (!iterative) printf("Total sequence pairs: %zu (sparsification: %s)\n", seqs.size() * seqs.size(), sparsify.c_str());
     // one resident context: load (or PAF replay) -> align -> unite -> graph induction, all on the device
     sr_ctx *ctx = nullptr;
     auto die = [&]() { fprintf(stderr, "Error: %s\n", sr_last_error()); if (ctx) sr_ctx_destroy(ctx); return 1; };
@@ -170,10 +201,44 @@ int main(int argc, char **argv) {
     } else if (!paf_in.empty()) {                            // align_and_unite_from_paf (src/seqrush.rs:510-609)
         printf("Reading alignments from PAF file: %s\n", paf_in.c_str());
         if (sr_ctx_load_paf(ctx, &set, &p, paf_in.c_str())) return die();
+    } else if (iterative) {                                  // align_and_unite_iterative (src/seqrush.rs:867-1132)
+        printf("Using iterative alignment with stabilization detection\n");
+        if (p.sparsify_kind != SR_SPARSE_TREE)
+            fprintf(stderr, "Note: Iterative mode works best with tree sampling. Using default tree:3,3,0.1,16\n");
+        if (sr_ctx_load_iterative(ctx, &set, &p, paf_out.empty() ? 0 : 1)) return die();
+        sr_iter_stats st;
+        if (sr_ctx_iterative_stats(ctx, &st, nullptr, 0)) return die();
+        printf("Processing %llu tree pairs (k=%u, k_far=%u) + %llu random pairs (frac=%s)\n", (unsigned long long)st.tree_entries,
+               st.tree_k_nearest, st.tree_k_farthest, (unsigned long long)st.random_entries, rust_f64(st.tree_rand_frac).c_str());
+        if (!paf_out.empty()) printf("Writing alignments to %s\n", paf_out.c_str());
+        printf("\nPhase 1: Processing tree pairs (k-nearest + k-farthest)...\n");
+        if (sr_ctx_run_iterative(ctx) || sr_ctx_sync(ctx) || sr_ctx_iterative_stats(ctx, &st, nullptr, 0)) return die();
+        std::vector<uint64_t> cc(st.checks + 1);
+        if (sr_ctx_iterative_stats(ctx, &st, cc.data(), st.checks)) return die();
+        printf("Phase 1 complete: %llu components after tree pairs\n", (unsigned long long)st.post_tree);
+        printf("\nPhase 2: Processing random pairs with early stopping...\n");
+        uint64_t prev = st.post_tree;
+        for (uint64_t k = 0; k < st.checks; k++) {
+            if (verbose) printf("  After %llu random pairs: %llu components (prev: %llu)\n", (unsigned long long)(k + 1) * 10,
+                                (unsigned long long)cc[k], (unsigned long long)prev);
+            if (st.stabilized && k + 1 == st.checks) {
+                const uint64_t m = (k + 1) * 10, r = st.random_entries;
+                printf("Graph stabilized after %llu random pairs (%llu components)\n", (unsigned long long)m, (unsigned long long)cc[k]);
+                printf("Skipped %llu random pairs (%s%% reduction)\n", (unsigned long long)(r - m), rust_f64((double)(r - m) / (double)r * 100.0).c_str());
+            }
+            prev = cc[k];
+        }
+        printf("\nFinal component count: %llu\n", (unsigned long long)st.final_components);
+        if (!paf_out.empty()) {
+            sr_alignments *al = nullptr;
+            if (sr_ctx_iterative_alignments(ctx, &al)) return die();
+            if (sr_write_paf(al, &set, paf_out.c_str())) { sr_alignments_free(al); return die(); }
+            sr_alignments_free(al);
+        }
     } else {
         if (sr_ctx_load(ctx, &set, &p)) return die();
     }
-    if (!labels_in.empty()) {
+    if (!labels_in.empty() || iterative) {
     } else if (!paf_in.empty() || paf_out.empty()) {
         if (sr_ctx_run(ctx)) return die();                   // align + unite, batch after batch (PAF input: unite only)
     } else {                                                 // --output-alignments (src/seqrush.rs:678-716)

@@ -21,6 +21,7 @@
 #include "sr_internal.h"
 #include "sr_graph.h"
 #include "sr_sort.h"
+#include "sr_iter_rule.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -268,6 +269,16 @@ struct sr_ctx {
     bool from_paf = false;             // loaded by sr_ctx_load_paf: no alignment stage, no sr_alignments
     bool aligned_batch_valid = false;  // the arena holds the CIGARs of the last batch sr_ctx_align ran
     std::string workspace_report;      // sizing of the last load (sr_ctx_workspace_report)
+    // iterative mode (sr_ctx_load_iterative): pairs [0, iter_tree_pairs) are the expanded tree entries, batches
+    // [0, iter_tree_batches) cover them; every later batch is a phase-2 window of whole chunks (4 * CHECK_INTERVAL pairs)
+    bool iter_loaded = false, iter_keep = false, iter_ran = false;
+    uint64_t iter_tree_pairs = 0;
+    uint32_t iter_tree_batches = 0, iter_max_chunks = 0;
+    sr_iter_stats iter_stats{};
+    std::vector<uint64_t> iter_counts;                 // per-check component counts of the last run
+    SrIterState *d_iter_state = nullptr;
+    unsigned long long *d_iter_counts = nullptr;       // [iter_max_chunks] counts of the window's checks, [iter_max_chunks] spare slot
+    sr_alignments *iter_al = nullptr;                  // processed alignments of the last run (keep_alignments)
 };
 
 static int dev_alloc(sr_ctx *c, void **p, size_t bytes) {
@@ -289,6 +300,9 @@ static void free_dev(sr_ctx *c) {
     c->d_okeys = c->d_okeys2 = nullptr; c->d_ovals = nullptr; c->d_otemp = nullptr; c->otemp_bytes = 0;
     c->loaded = false; c->from_paf = false; c->aligned_batch_valid = false;
     for (int k = 0; k < 5; k++) c->ev_used[k] = 0;
+    c->iter_loaded = c->iter_keep = c->iter_ran = false; c->iter_tree_pairs = 0; c->iter_tree_batches = c->iter_max_chunks = 0;
+    c->iter_counts.clear(); c->d_iter_state = nullptr; c->d_iter_counts = nullptr; c->iter_stats = sr_iter_stats{};
+    if (c->iter_al) { sr_alignments_free(c->iter_al); c->iter_al = nullptr; }
 }
 
 // event pair `idx` of kind `kind` (created on first use)
@@ -364,6 +378,12 @@ static inline double unit53(uint64_t h) { return (double)(h >> 11) * (1.0 / 9007
 //   tree:kn,kf,rf,k unordered pair kept iff it is one of the kn nearest or kf farthest neighbours of either end by
 //                   k-mer sketch similarity (sr_sketch.hip), or unit(splitmix64(seed ^ (i*n+j))) < rf
 // Self pairs are always kept unless exclude_self.
+// --iterative (align_and_unite_iterative, src/seqrush.rs:867-1132) splits the unordered pairs of tree:kn,kf,rf,k into
+//   tree entries    {i<j} selected for either end by the k-NN selection, row-major
+//   random entries  the other {i<j} with unit(h) < rf, h = splitmix64(seed ^ (i*n+j)), ordered by h ascending, ties by (i, j):
+//                   a seeded shuffle, so the early checks do not all see pairs of sequence 0
+// (together exactly the unordered pairs of the tree: list above); each entry expands to the ordered alignments (i,i) (i,j)
+// (j,i) (j,j), AllPairIterator over the two-sequence slice with exclude_self = false (:984-991), row-major like `none`.
 static double connectivity_fraction(uint32_t n, double P) {
     if (n <= 2 || P >= 1.0) return 1.0;
     const double c = -std::log(-std::log(P));
@@ -392,6 +412,39 @@ static void enumerate_pairs(uint32_t n, const sr_params &p, const uint8_t *sel, 
                        unit53(splitmix64(p.sparsify_seed ^ ((uint64_t)i * n + j))) < p.tree_rand_frac;
             if (keep) { pq.push_back(q); pt.push_back(t); }
         }
+}
+
+// the two entry lists of --iterative (definition above); sel: n*n bytes of the k-NN selection or NULL (n <= 1)
+static void iterative_lists(uint32_t n, const uint8_t *sel, uint64_t seed, double rf, std::vector<uint32_t> &ti,
+                            std::vector<uint32_t> &tj, std::vector<uint32_t> &ri, std::vector<uint32_t> &rj) {
+    ti.clear(); tj.clear(); ri.clear(); rj.clear();
+    struct R { uint64_t h; uint32_t i, j; };
+    std::vector<R> rnd;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t j = i + 1; j < n; j++) {
+            if (sel && (sel[(uint64_t)i * n + j] || sel[(uint64_t)j * n + i])) { ti.push_back(i); tj.push_back(j); continue; }
+            const uint64_t h = splitmix64(seed ^ ((uint64_t)i * n + j));
+            if (unit53(h) < rf) rnd.push_back({h, i, j});
+        }
+    std::sort(rnd.begin(), rnd.end(), [](const R &a, const R &b) {
+        return a.h != b.h ? a.h < b.h : (a.i != b.i ? a.i < b.i : a.j < b.j); });
+    for (const R &e : rnd) { ri.push_back(e.i); rj.push_back(e.j); }
+}
+
+static uint32_t *copy_out_u32(const std::vector<uint32_t> &v) {
+    uint32_t *o = (uint32_t *)malloc((v.empty() ? 1 : v.size()) * 4);
+    if (o) memcpy(o, v.data(), v.size() * 4);
+    return o;
+}
+
+extern "C" int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, uint32_t **tree_i, uint32_t **tree_j,
+                                       uint64_t *tree_count, uint32_t **rand_i, uint32_t **rand_j, uint64_t *rand_count) {
+    if (!p || !tree_i || !tree_j || !tree_count || !rand_i || !rand_j || !rand_count) return fail(SR_ERR_INVALID, "null argument");
+    std::vector<uint32_t> ti, tj, ri, rj;
+    iterative_lists(n, sel, p->sparsify_seed, p->tree_rand_frac, ti, tj, ri, rj);
+    *tree_i = copy_out_u32(ti); *tree_j = copy_out_u32(tj); *rand_i = copy_out_u32(ri); *rand_j = copy_out_u32(rj);
+    *tree_count = ti.size(); *rand_count = ri.size();
+    return SR_OK;
 }
 
 // Cost-balanced shard: pairs sorted by cost (|q|*|t|; self pairs cost |q|: they end in one
@@ -640,9 +693,24 @@ static int tree_selection(sr_ctx *c, const sr_params *p, const SeqDev &sd, std::
 
 // ordered pair list of this rank + what follows from it: DP cells, worst-case CIGAR reserve per pair, divergence thresholds
 static int build_pair_list(sr_ctx *c, const sr_params *p, const SeqDev &sd, const uint32_t *eq, const uint32_t *et, uint64_t ecount,
-                           bool explicit_pairs, std::vector<int32_t> &max_score, uint64_t *max_reserve) {
+                           bool explicit_pairs, std::vector<int32_t> &max_score, uint64_t *max_reserve, bool iterative = false) {
     const uint32_t n = c->n;
-    if (explicit_pairs) {
+    if (iterative) {                  // --iterative: expanded tree entries, then expanded random entries (explicit list, no shard)
+        std::vector<uint8_t> sel;
+        if (n > 1) { const int r = tree_selection(c, p, sd, sel); if (r) return r; }
+        std::vector<uint32_t> ti, tj, ri, rj;
+        iterative_lists(n, sel.empty() ? nullptr : sel.data(), p->sparsify_seed, p->tree_rand_frac, ti, tj, ri, rj);
+        if (4 * ((uint64_t)ti.size() + ri.size()) > 0xfffffff0ULL) return fail(SR_ERR_UNSUPPORTED, "more than 2^32 pairs in one shard");
+        c->pair_q.clear(); c->pair_t.clear();
+        auto expand = [&](uint32_t i, uint32_t j) {
+            const uint32_t q[4] = {i, i, j, j}, t[4] = {i, j, i, j};
+            for (int k = 0; k < 4; k++) { c->pair_q.push_back(q[k]); c->pair_t.push_back(t[k]); }
+        };
+        for (size_t e = 0; e < ti.size(); e++) expand(ti[e], tj[e]);
+        for (size_t e = 0; e < ri.size(); e++) expand(ri[e], rj[e]);
+        c->iter_tree_pairs = 4 * (uint64_t)ti.size();
+        c->iter_stats.tree_entries = ti.size(); c->iter_stats.random_entries = ri.size();
+    } else if (explicit_pairs) {
         c->pair_q.assign(eq, eq + ecount); c->pair_t.assign(et, et + ecount);
         for (uint64_t i = 0; i < ecount; i++)
             if (eq[i] >= n || et[i] >= n) return fail(SR_ERR_INVALID, "pair index out of range");
@@ -793,7 +861,7 @@ static int plan_workspace(const sr_ctx *c, const SrPen &pen, const SrPen &ori, u
 // memory budget: every buffer counted.  fixed = union-find arrays + per-pair arrays; then the CIGAR arena (worst
 // case |q|+|t|+2 ops per pair; pairs run in batches that reuse it), the orientation rings and the alignment workspaces share
 // what is left
-static int plan_memory(sr_ctx *c, uint32_t np, Plan &pl) {
+static int plan_memory(sr_ctx *c, uint32_t np, Plan &pl, bool iterative = false) {
     size_t total_b = 0;
     HIPCHK(hipMemGetInfo(&pl.free_b, &total_b));
     const uint64_t fixed = 3ULL * c->uf_size * 8 + (uint64_t)np * 40 + (1ULL << 20);
@@ -803,12 +871,39 @@ static int plan_memory(sr_ctx *c, uint32_t np, Plan &pl) {
     {
         uint64_t cap = std::max<uint64_t>((uint64_t)(avail * 0.25) / 4, pl.max_reserve + 1);
         if (const char *e = knob("SR_CIGAR_ARENA_OPS")) cap = std::max<uint64_t>((uint64_t)atoll(e), pl.max_reserve + 1);   // (tests: force batches)
+        if (iterative)                // a phase-2 window holds at least one whole chunk
+            for (uint64_t f = c->iter_tree_pairs; f < np; f += 4 * SR_ITER_CHECK_INTERVAL)
+                cap = std::max<uint64_t>(cap, c->cigar_base[std::min<uint64_t>(np, f + 4 * SR_ITER_CHECK_INTERVAL)] - c->cigar_base[f] + 1);
         pl.arena_ops = std::min(pl.arena_ops, cap);
     }
     if (pl.arena_ops * 4 > avail / 2) return fail(SR_ERR_NOMEM, "not enough device memory for one pair's CIGAR");
     c->batch_first.assign(1, 0);
-    for (uint32_t i = 0; i < np; i++)
+    const uint32_t tp = iterative ? (uint32_t)c->iter_tree_pairs : np;
+    for (uint32_t i = 0; i < tp; i++)
         if (c->cigar_base[i + 1] - c->cigar_base[c->batch_first.back()] + 1 > pl.arena_ops) c->batch_first.push_back(i);
+    if (iterative) {
+        // tree part ends on a batch boundary; then windows of whole chunks: 10 chunks first (the earliest possible stop),
+        // doubling after each window, as many as the arena holds (>= 1)
+        if (tp > 0 && tp < np) c->batch_first.push_back(tp);
+        c->iter_tree_batches = tp == 0 ? 0 : (tp < np ? (uint32_t)c->batch_first.size() - 1 : (uint32_t)c->batch_first.size());
+        const uint32_t CH = 4 * SR_ITER_CHECK_INTERVAL;
+        uint64_t target = SR_ITER_STABILITY_THRESHOLD;
+        c->iter_max_chunks = 0;
+        for (uint32_t f = tp; f < np;) {
+            uint32_t l = f, chunks = 0;
+            while (l < np && (chunks == 0 || chunks < target)) {
+                const uint32_t e = std::min(np, l + CH);
+                if (chunks > 0 && c->cigar_base[e] - c->cigar_base[f] + 1 > pl.arena_ops) break;
+                l = e; chunks++;
+            }
+            c->iter_max_chunks = std::max(c->iter_max_chunks, chunks);
+            if (l < np) c->batch_first.push_back(l);
+            f = l;
+            target = std::min<uint64_t>(2 * target, 1ULL << 32);     // (doubling stops before it could wrap)
+        }
+    } else {
+        c->iter_tree_batches = 0;
+    }
     c->batch_first.push_back(np);
     pl.nbatch = (uint32_t)c->batch_first.size() - 1;
     pl.max_batch_pairs = 0;
@@ -972,7 +1067,7 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
 }
 
 static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const uint32_t *eq, const uint32_t *et,
-                     uint64_t ecount, bool explicit_pairs) {
+                     uint64_t ecount, bool explicit_pairs, bool iterative = false) {
     if (!c || !seqs || !p) return fail(SR_ERR_INVALID, "null argument");
     if (seqs->n == 0) return fail(SR_ERR_INVALID, "no sequences");
     HIPCHK(hipSetDevice(c->device));
@@ -989,11 +1084,11 @@ static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const
     if ((r = upload_sequences(c, seqs, pk, sd))) return r;
     Plan pl;
     std::vector<int32_t> max_score;
-    if ((r = build_pair_list(c, p, sd, eq, et, ecount, explicit_pairs, max_score, &pl.max_reserve))) return r;
+    if ((r = build_pair_list(c, p, sd, eq, et, ecount, explicit_pairs, max_score, &pl.max_reserve, iterative))) return r;
     const uint32_t np = (uint32_t)c->pair_q.size();
     if ((r = plan_kernel(c, pk, pen, ori, maxlen, np, pl))) return r;
     if ((r = plan_workspace(c, pen, ori, maxlen, pl))) return r;
-    if ((r = plan_memory(c, np, pl))) return r;
+    if ((r = plan_memory(c, np, pl, iterative))) return r;
     if ((r = alloc_workspace(c, p, pk, sd, pen, ori, maxlen, max_score, pl))) return r;
     write_report(c, pk, pen, pl);
     if (srk_uf_init(c->d_nodes, c->total_len, c->uf_size, c->stream)) return fail(SR_ERR_HIP, "uf init launch failed");
@@ -1339,8 +1434,8 @@ static int collect_batch(sr_ctx *c, uint32_t b, AlnAcc &acc) {
     return SR_OK;
 }
 
-static sr_alignments *make_alignments(const sr_ctx *c, const AlnAcc &acc) {
-    const size_t np = c->pair_q.size();
+static sr_alignments *make_alignments(const sr_ctx *c, const AlnAcc &acc, size_t count = SIZE_MAX) {
+    const size_t np = std::min(count, c->pair_q.size());
     sr_alignments *a = (sr_alignments *)calloc(1, sizeof(sr_alignments));
     a->n = np;
     const size_t m = np ? np : 1;
@@ -1458,6 +1553,135 @@ extern "C" int sr_align_and_unite(const sr_seqset *seqs, const sr_params *p, uin
     sr_ctx_destroy(c);
     g_err = keep;
     return r;
+}
+
+// ------------------------------------------------------------------ iterative mode (--iterative)
+// align_and_unite_iterative (src/seqrush.rs:867-1132) on one context.  Pair list: the expanded tree entries, then the
+// expanded random entries (sr_host.cpp "pair list"), loaded through load_impl without sharding.  Phase 1 runs the tree
+// batches like sr_ctx_run (fused unite).  Phase 2 runs window after window: the alignment kernel without the fused unite, then
+// per chunk of CHECK_INTERVAL random entries the guarded unite, the root count and the decision (sr_iter.hip), all on the
+// stream; the host reads the decision state and the window's counts after the window and starts the next one only if the
+// run has not stopped.  The union-find then holds exactly the processed alignments, whatever the schedule.
+extern "C" int sr_ctx_load_iterative(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, int keep_alignments) {
+    if (!c || !seqs || !p) return fail(SR_ERR_INVALID, "null argument");
+    if (p->shard_count != 1 || p->shard_rank != 0)
+        return fail(SR_ERR_UNSUPPORTED, "--iterative runs one global sequential stop rule: it cannot be sharded over ranks");
+    sr_params q = *p;
+    const bool defaulted = q.sparsify_kind != SR_SPARSE_TREE;
+    if (defaulted) {                                   // :957-967: any other strategy -> tree:3,3,0.1,16
+        q.sparsify_kind = SR_SPARSE_TREE; q.tree_k_nearest = 3; q.tree_k_farthest = 3; q.tree_rand_frac = 0.1; q.tree_kmer = 16;
+    }
+    int r = load_impl(c, seqs, &q, nullptr, nullptr, 0, true, true);
+    if (r) return r;
+    void *d;
+    if ((r = dev_alloc(c, &d, sizeof(SrIterState)))) return r;
+    c->d_iter_state = (SrIterState *)d;
+    if ((r = dev_alloc(c, &d, ((size_t)c->iter_max_chunks + 1) * 8))) return r;
+    c->d_iter_counts = (unsigned long long *)d;
+    sr_iter_stats &st = c->iter_stats;
+    st.tree_defaulted = defaulted ? 1 : 0;
+    st.tree_k_nearest = q.tree_k_nearest; st.tree_k_farthest = q.tree_k_farthest; st.tree_rand_frac = q.tree_rand_frac; st.tree_kmer = q.tree_kmer;
+    c->iter_keep = keep_alignments != 0;
+    c->iter_loaded = true;
+    return SR_OK;
+}
+
+// components of the context's forest: roots among nodes [0, 2T) into d_iter_counts[slot] (host sync; error flags checked)
+static int iter_count_now(sr_ctx *c, uint32_t slot, uint64_t *out) {
+    HIPCHK(hipMemsetAsync(c->d_iter_counts + slot, 0, 8, c->stream));
+    if (srk_count_roots(c->d_nodes, c->total_len, c->d_iter_counts + slot, nullptr, c->stream)) return fail(SR_ERR_HIP, "count kernel launch failed");
+    int r = sr_ctx_sync(c);
+    if (r) return r;
+    HIPCHK(hipMemcpy(out, c->d_iter_counts + slot, 8, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_run_iterative(sr_ctx *c) {
+    if (!c || !c->loaded || !c->iter_loaded) return fail(SR_ERR_INVALID, "context not loaded with sr_ctx_load_iterative");
+    int r = begin_pass(c, true);
+    if (r) return r;
+    c->ev_used[1] = 0;
+    if (c->iter_ran && (r = sr_ctx_reset_uf(c))) return r;     // a second run starts from SeqRush::new again
+    if (c->iter_al) { sr_alignments_free(c->iter_al); c->iter_al = nullptr; }
+    sr_iter_stats &st = c->iter_stats;
+    st.random_processed = st.random_aligned = st.checks = st.windows = 0; st.stabilized = 0;
+    c->iter_counts.clear();
+    const size_t np = c->pair_q.size();
+    const uint32_t nbatch = (uint32_t)c->batch_first.size() - 1;
+    AlnAcc acc;
+    if (c->iter_keep) { acc.cnt.assign(np + 1, 0); acc.score.assign(np + 1, 0); acc.isrev.assign(np + 1, 0); }
+    // phase 1: every tree entry
+    for (uint32_t b = 0; b < c->iter_tree_batches; b++) {
+        if ((r = enqueue_align_batch(c, b, c->fuse_unite)) || (r = enqueue_unite_batch(c, b, c->fuse_unite))) return r;
+        if (c->iter_keep && ((r = sr_ctx_sync(c)) || (r = collect_batch(c, b, acc)))) return r;
+    }
+    const uint32_t spare = c->iter_max_chunks;
+    uint64_t post_tree = 0;
+    if ((r = iter_count_now(c, spare, &post_tree))) return r;
+    st.post_tree = post_tree;
+    SrIterState hs{};
+    hs.prev = post_tree;
+    HIPCHK(hipMemcpy(c->d_iter_state, &hs, sizeof(hs), hipMemcpyHostToDevice));
+    // phase 2: windows of whole chunks
+    const uint32_t CH = 4 * SR_ITER_CHECK_INTERVAL;
+    const uint64_t tp = c->iter_tree_pairs;
+    std::vector<unsigned long long> cnt(c->iter_max_chunks + 1);
+    for (uint32_t b = c->iter_tree_batches; b < nbatch; b++) {
+        SrUniteArgs u;
+        batch_args(c, b, nullptr, &u);
+        const uint32_t f = c->batch_first[b], npb = u.npairs;
+        if (npb == 0) continue;
+        const uint32_t nchunks = (npb + CH - 1) / CH, check0 = (uint32_t)((f - tp) / CH);
+        HIPCHK(hipMemsetAsync(c->d_iter_counts, 0, (size_t)nchunks * 8, c->stream));
+        if ((r = enqueue_align_batch(c, b, false))) return r;
+        for (uint32_t k = 0; k < nchunks; k++) {
+            SrUniteArgs uc = u;
+            const uint32_t o = k * CH, m = std::min(CH, npb - o);
+            uc.pair_q += o; uc.pair_t += o; uc.npairs = m; uc.is_reverse += o; uc.score += o; uc.max_score += o;
+            uc.cigar_cnt += o; uc.cigar_base += o;
+            if (srk_iter_unite(&uc, (int)m, c->d_iter_state, c->stream)) return fail(SR_ERR_HIP, "iterative unite kernel launch failed");
+            if (m < CH) break;                             // trailing partial chunk: no check (:1088)
+            if (srk_count_roots(c->d_nodes, c->total_len, c->d_iter_counts + k, c->d_iter_state, c->stream) ||
+                srk_iter_decide(c->d_iter_state, c->d_iter_counts, k, check0 + k, c->stream))
+                return fail(SR_ERR_HIP, "iterative count / decide kernel launch failed");
+        }
+        st.windows++;
+        st.random_aligned += npb / 4;
+        if ((r = sr_ctx_sync(c))) return r;
+        HIPCHK(hipMemcpy(&hs, c->d_iter_state, sizeof(hs), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cnt.data(), c->d_iter_counts, (size_t)nchunks * 8, hipMemcpyDeviceToHost));
+        const uint32_t full = npb / CH;
+        const uint32_t done = hs.stopped ? hs.stop_check + 1 - check0 : full;     // checks of this window that ran
+        for (uint32_t k = 0; k < done; k++) c->iter_counts.push_back(cnt[k]);
+        if (c->iter_keep && (r = collect_batch(c, b, acc))) return r;
+        if (hs.stopped) break;
+    }
+    st.checks = c->iter_counts.size();
+    st.stabilized = hs.stopped ? 1 : 0;
+    st.random_processed = hs.stopped ? (uint64_t)(hs.stop_check + 1) * SR_ITER_CHECK_INTERVAL : st.random_entries;
+    uint64_t fin = 0;
+    if ((r = iter_count_now(c, spare, &fin))) return r;
+    st.final_components = fin;
+    if (c->iter_keep) c->iter_al = make_alignments(c, acc, (size_t)(tp + 4 * st.random_processed));
+    c->iter_ran = true;
+    c->aligned_batch_valid = false;
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_iterative_stats(sr_ctx *c, sr_iter_stats *out, uint64_t *check_counts, uint64_t cap) {
+    if (!c || !c->iter_loaded || !out) return fail(SR_ERR_INVALID, "context not loaded with sr_ctx_load_iterative");
+    *out = c->iter_stats;
+    if (check_counts)
+        for (uint64_t i = 0; i < std::min<uint64_t>(cap, c->iter_counts.size()); i++) check_counts[i] = c->iter_counts[i];
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_iterative_alignments(sr_ctx *c, sr_alignments **out) {
+    if (!c || !out) return fail(SR_ERR_INVALID, "null argument");
+    if (!c->iter_al) return fail(SR_ERR_INVALID, "no processed alignments: load with keep_alignments = 1, run, and take them once");
+    *out = c->iter_al;
+    c->iter_al = nullptr;
+    return SR_OK;
 }
 
 // ------------------------------------------------------------------ PAF input (seam 3, `seqrush -p`)
@@ -1703,6 +1927,28 @@ extern "C" int sr_uf_merge_labels_host(uint64_t *nodes, uint64_t n, const uint64
     }
     return SR_OK;
 }
+// count_components (src/seqrush.rs:341-353) of a SeqRush forest: roots among nodes [0, 2 total_len) -- every component with a
+// base holds both strands of it (SeqRush::new) and nodes >= 2T are never united (sr_iter.hip does the same on the device)
+extern "C" int sr_uf_count_components_host(const uint64_t *nodes, uint64_t n, uint64_t total_len, uint64_t *count) {
+    if (!nodes || !count || 2 * total_len > n) return fail(SR_ERR_INVALID, "bad node array");
+    uint64_t c = 0;
+    for (uint64_t x = 0; x < 2 * total_len; x++) c += (nodes[x] & UFH_MASK) == x;
+    *count = c;
+    return SR_OK;
+}
+
+// the stop rule over given per-check counts (sr_iter_rule.h, the decide kernel's rule): *stop_check = number of checks
+// consumed when it fired (the run stops after 10 * *stop_check random entries), 0 = never within nchecks
+extern "C" int sr_iterative_stop_host(const uint64_t *counts, uint64_t nchecks, uint64_t post_tree, uint64_t *stop_check) {
+    if ((!counts && nchecks) || !stop_check) return fail(SR_ERR_INVALID, "null argument");
+    SrIterState s{};
+    s.prev = post_tree;
+    *stop_check = 0;
+    for (uint64_t k = 0; k < nchecks && !s.stopped; k++) sr_iter_step(&s, counts[k], (uint32_t)k);
+    if (s.stopped) *stop_check = (uint64_t)s.stop_check + 1;
+    return SR_OK;
+}
+
 // canonical labels of a node array: the minimum element of each set (what sr_ctx_download_labels returns)
 extern "C" int sr_uf_canonical_labels_host(const uint64_t *nodes, uint64_t n, uint64_t *labels_out) {
     if (!nodes || !labels_out) return fail(SR_ERR_INVALID, "null argument");

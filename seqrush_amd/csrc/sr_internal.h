@@ -173,6 +173,12 @@ int srk_sketch(const uint8_t *bases, const uint64_t *goff, const uint32_t *len, 
 int srk_jaccard(const unsigned long long *sketch, const uint32_t *sk_n, uint32_t n, int s_max, uint32_t *shared, uint32_t *denom,
                 void *stream);
 int srk_knn_select(const uint32_t *shared, const uint32_t *denom, uint32_t n, int kn, int kf, uint8_t *sel, void *stream);
+// sr_iter.hip: phase 2 of the iterative mode (guarded unite, root count over nodes [0, 2 nbases), stop rule; sr_iter_rule.h)
+struct SrIterState;
+int srk_iter_unite(const SrUniteArgs *a, int nwg, const struct SrIterState *st, void *stream);
+int srk_count_roots(const unsigned long long *nodes, uint64_t nbases, unsigned long long *count, const struct SrIterState *st,
+                    void *stream);
+int srk_iter_decide(struct SrIterState *st, const unsigned long long *counts, uint32_t k, uint32_t check, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence as Seq
 import numpy as np
 
 from . import _lib
-from ._lib import ParamsC, SeqSetC, AlignmentsC, SortParamsC, check, SeqRushError
+from ._lib import ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, check, SeqRushError
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -46,6 +46,7 @@ class Args:
     shard_rank: int = 0                     # added: multi-GPU pair shard
     shard_count: int = 1
     gpus: int = 1                           # added: --gpus N, one process per GPU under torch.distributed.run
+    iterative: bool = False                 # --iterative: tree pairs, then random pairs until the components are stable
 
 
 @dataclasses.dataclass
@@ -291,6 +292,32 @@ class Context:
         check(self.L.sr_ctx_pair_results(self._h, sc.ctypes.data_as(C.POINTER(C.c_int32)),
                                          rv.ctypes.data_as(C.POINTER(C.c_uint8)), co.ctypes.data_as(C.POINTER(C.c_uint32))))
         return sc[:n], rv[:n], co[:n]
+
+    def load_iterative(self, seqset: SeqSet, params: Params, keep_alignments: bool = False):
+        """--iterative: sequences + tree entries + random entries (a -x other than tree: becomes tree:3,3,0.1,16)"""
+        self.seqset = seqset
+        check(self.L.sr_ctx_load_iterative(self._h, C.byref(seqset.c), C.byref(params.c), 1 if keep_alignments else 0))
+
+    def run_iterative(self):
+        """phase 1 (every tree entry) and phase 2 (random entries in chunks of 10 until 10 checks saw no change)"""
+        check(self.L.sr_ctx_run_iterative(self._h))
+
+    def iterative_stats(self):
+        """stats of the last iterative run -> dict (sr_iter_stats fields + check_counts: the per-check component counts)"""
+        st = IterStatsC()
+        check(self.L.sr_ctx_iterative_stats(self._h, C.byref(st), None, 0))
+        cc = np.zeros(max(int(st.checks), 1), dtype=np.uint64)
+        check(self.L.sr_ctx_iterative_stats(self._h, C.byref(st), cc.ctypes.data_as(C.POINTER(C.c_uint64)), int(st.checks)))
+        d = {f: getattr(st, f) for f, _ in IterStatsC._fields_ if f != "reserved"}
+        d["stabilized"], d["tree_defaulted"] = bool(d["stabilized"]), bool(d["tree_defaulted"])
+        d["check_counts"] = [int(x) for x in cc[:int(st.checks)]]
+        return d
+
+    def iterative_alignments(self) -> "Alignments":
+        """the processed alignments of the last iterative run, in processing order (load with keep_alignments=True)"""
+        p = C.POINTER(AlignmentsC)()
+        check(self.L.sr_ctx_iterative_alignments(self._h, C.byref(p)))
+        return Alignments(p)
 
     def load_paf(self, seqset: SeqSet, params: Params, paf_path: str):
         """`seqrush -p`: replay the records of a PAF file (then unite()); there is no alignment stage"""
@@ -566,6 +593,8 @@ class SeqRush:
 
     def align_and_unite(self, args: Args):
         """align_and_unite_with_allwave (src/seqrush.rs:611-757) on the device"""
+        if args.iterative and args.paf is not None:
+            raise SeqRushError(-6, "--iterative cannot be combined with -p (there is no alignment stage to stop)")
         if args.paf is not None:                      # align_and_unite_from_paf (src/seqrush.rs:510-609)
             print(f"Reading alignments from PAF file: {args.paf}")
             self.ctx.load_paf(self.seqset, Params.from_args(args), args.paf)
@@ -577,6 +606,8 @@ class SeqRush:
         if args.aligner.lower() != "allwave":
             raise SeqRushError(-6, f"aligner '{args.aligner}' is out of scope; only 'allwave'")
         params = Params.from_args(args)
+        if args.iterative:
+            return self._align_and_unite_iterative(args, params)
         self.ctx.load(self.seqset, params)
         n = len(self.sequences)
         print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
@@ -590,6 +621,34 @@ class SeqRush:
         self.ctx.sync()
         self.labels = self.ctx.download_labels()
         self.ctx.sync()
+
+    def _align_and_unite_iterative(self, args: Args, params: Params):
+        """align_and_unite_iterative (src/seqrush.rs:867-1132) on the device, with the reference's messages"""
+        import sys
+        if args.shard_count != 1:
+            raise SeqRushError(-6, "--iterative cannot be sharded over GPUs (its stop rule is global and sequential)")
+        print("Using iterative alignment with stabilization detection")
+        if params.c.sparsify_kind != SR_SPARSE_TREE:
+            print("Note: Iterative mode works best with tree sampling. Using default tree:3,3,0.1,16", file=sys.stderr)
+        self.ctx.load_iterative(self.seqset, params, keep_alignments=bool(args.output_alignments))
+        st = self.ctx.iterative_stats()
+        print(f"Processing {st['tree_entries']} tree pairs (k={st['tree_k_nearest']}, k_far={st['tree_k_farthest']}) + "
+              f"{st['random_entries']} random pairs (frac={rust_f64(st['tree_rand_frac'])})")
+        if args.output_alignments:
+            print(f"Writing alignments to {args.output_alignments}")
+        print("\nPhase 1: Processing tree pairs (k-nearest + k-farthest)...")
+        self.ctx.run_iterative()
+        self.ctx.sync()
+        st = self.ctx.iterative_stats()
+        for line in iterative_report(st, args.verbose):
+            print(line)
+        if args.output_alignments:
+            al = self.ctx.iterative_alignments()
+            al.write_paf(self.seqset, args.output_alignments)
+            al.close()
+        self.labels = self.ctx.download_labels()
+        self.ctx.sync()
+        self.iterative_stats = st
 
     def build_graph(self, args: Args):
         print(f"Building graph with {len(self.sequences)} sequences "
@@ -693,6 +752,80 @@ def run_seqrush_rank(args: Args):
     dist.barrier()
     dist.destroy_process_group()
     return sr
+
+
+SR_SPARSE_TREE = 4
+
+
+def rust_f64(x: float) -> str:
+    """an f64 the way Rust's Display prints it: shortest round-trip digits, never an exponent, no '.0' on integers"""
+    import decimal
+    r = repr(float(x))
+    if r in ("inf", "-inf", "nan"):
+        return {"inf": "inf", "-inf": "-inf", "nan": "NaN"}[r]
+    s = format(decimal.Decimal(r), "f")
+    if "." in s:
+        s = s.rstrip("0").rstrip(".")
+    return s
+
+
+def iterative_report(st: dict, verbose: bool = False):
+    """the reference's stdout lines after phase 1 (src/seqrush.rs:1024-1131) from iterative_stats(); the per-pair
+    progress lines of its -v phase 1 are not printed"""
+    out = [f"Phase 1 complete: {st['post_tree']} components after tree pairs",
+           "\nPhase 2: Processing random pairs with early stopping..."]
+    prev = st["post_tree"]
+    nchk = len(st["check_counts"])
+    for k, c in enumerate(st["check_counts"]):
+        if verbose:
+            out.append(f"  After {(k + 1) * 10} random pairs: {c} components (prev: {prev})")
+        stop = st["stabilized"] and k == nchk - 1
+        if stop:
+            m, r = (k + 1) * 10, st["random_entries"]
+            out.append(f"Graph stabilized after {m} random pairs ({c} components)")
+            out.append(f"Skipped {r - m} random pairs ({rust_f64((r - m) / r * 100.0)}% reduction)")
+        prev = c
+    out.append(f"\nFinal component count: {st['final_components']}")
+    return out
+
+
+def uf_count_components_host(nodes: np.ndarray, total_len: int) -> int:
+    """count_components (src/seqrush.rs:341-353) of a SeqRush node array on the host: roots among nodes [0, 2T)"""
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
+    out = C.c_uint64()
+    check(_lib.load().sr_uf_count_components_host(nodes.ctypes.data_as(C.POINTER(C.c_uint64)), len(nodes), total_len,
+                                                  C.byref(out)))
+    return int(out.value)
+
+
+def iterative_stop_host(counts, post_tree: int) -> int:
+    """the stop rule over per-check counts -> checks consumed when it fired (0 = it never fired)"""
+    counts = [int(c) for c in counts]
+    arr = np.ascontiguousarray(counts or [0], dtype=np.uint64)
+    out = C.c_uint64()
+    check(_lib.load().sr_iterative_stop_host(arr.ctypes.data_as(C.POINTER(C.c_uint64)), len(counts), post_tree, C.byref(out)))
+    return int(out.value)
+
+
+def iterative_pair_lists(n: int, sel, params: Params):
+    """the two entry lists of --iterative for an n*n k-NN selection (sel[i, j]: j picked by i; None = none)
+    -> (tree [(i, j)], random [(i, j)])"""
+    L = _lib.load()
+    selp = None
+    if sel is not None:
+        sel = np.ascontiguousarray(sel, dtype=np.uint8).reshape(-1)
+        assert len(sel) == n * n
+        selp = sel.ctypes.data_as(C.POINTER(C.c_uint8))
+    P = lambda: C.POINTER(C.c_uint32)()     # noqa: E731
+    ti, tj, ri, rj = P(), P(), P(), P()
+    tc, rc = C.c_uint64(), C.c_uint64()
+    check(L.sr_iterative_pair_lists(n, selp, C.byref(params.c), C.byref(ti), C.byref(tj), C.byref(tc), C.byref(ri), C.byref(rj),
+                                    C.byref(rc)))
+    tree = [(int(ti[k]), int(tj[k])) for k in range(tc.value)]
+    rnd = [(int(ri[k]), int(rj[k])) for k in range(rc.value)]
+    for a in (ti, tj, ri, rj):
+        L.sr_free(C.cast(a, C.c_void_p))
+    return tree, rnd
 
 
 def pair_list(n: int, params: Params):
