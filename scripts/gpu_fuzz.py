@@ -95,3 +95,16 @@ for seed in range(int(sys.argv[3]) if len(sys.argv) > 3 else 80):
             else: os.environ[k] = v
     if seed % 10 == 0: print("r2", seed, L, n, flush=True)
 print("round-2 fuzz done, failures:", bad)
+
+# repeat-rich sets (tests/repeat_inputs.py): homopolymers, microsatellites, satellites, palindromes, two-letter sequences --
+# the inputs whose alignments have co-optimal alternatives, through the same checks as the small sets above
+import test_repeats_gpu as tr
+bad = []
+ROFF = int(sys.argv[5]) if len(sys.argv) > 5 else 12          # (argv[5], argv[6]: seed range of the repeat sets)
+for seed in range(ROFF, int(sys.argv[6]) if len(sys.argv) > 6 else ROFF + 240):
+    try:
+        tr.test_randomised_repeat_sets(None, seed)
+    except Exception as e:
+        bad.append((seed, repr(e)[:200])); print("FAIL repeat", seed, repr(e)[:200], flush=True)
+    if seed % 40 == 0: print("repeat", seed, flush=True)
+print("repeat fuzz done, failures:", bad)
