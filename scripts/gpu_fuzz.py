@@ -108,3 +108,30 @@ for seed in range(ROFF, int(sys.argv[6]) if len(sys.argv) > 6 else ROFF + 240):
         bad.append((seed, repr(e)[:200])); print("FAIL repeat", seed, repr(e)[:200], flush=True)
     if seed % 40 == 0: print("repeat", seed, flush=True)
 print("repeat fuzz done, failures:", bad)
+
+# penalty lattice x alphabet (tests/instance_matrix.py): a lattice set, a symbol width and a family per seed; the report must
+# read what the dispatch restatement says before the result is compared with the oracle
+import instance_matrix as im
+import test_instance_matrix_gpu as tm
+bad = []
+LOFF = int(sys.argv[7]) if len(sys.argv) > 7 else 0           # (argv[7], argv[8]: seed range of the lattice sets)
+names = [k for k, v in im.LATTICE.items() if v[1] != "refused"]
+for seed in range(LOFF, int(sys.argv[8]) if len(sys.argv) > 8 else LOFF + 120):
+    rng = random.Random(12000 + seed)
+    name, bits = rng.choice(names), rng.choice([2, 4, 8])
+    recs = im.lift(im.family(100 + seed, n=rng.randint(3, 5), lo=rng.choice([300, 1200]), hi=rng.choice([1500, 2500, 4000])), bits, seed)
+    knobs = {}
+    if rng.random() < 0.5: knobs["SR_ALIGN_THREADS"] = rng.choice(["128", "256", "512"])
+    if rng.random() < 0.25: knobs["SR_FORCE_INT32"] = "1"
+    if rng.random() < 0.3: knobs["SR_NWG"] = rng.choice(["1", "2"])
+    old = {k: os.environ.get(k) for k in knobs}
+    try:
+        tm.run_and_identify(os.environ.__setitem__, recs, knobs, im.LATTICE[name][0])
+    except Exception as e:
+        bad.append((seed, name, bits, knobs, repr(e)[:300])); print("FAIL lattice", seed, name, bits, knobs, repr(e)[:300], flush=True)
+    finally:
+        for k, v in old.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = v
+    if seed % 20 == 0: print("lattice", seed, name, bits, flush=True)
+print("lattice fuzz done, failures:", bad)

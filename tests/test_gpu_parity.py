@@ -131,10 +131,12 @@ def test_long_homopolymer_11068_vs_11065(gpu):
     ("rc-indel", [(n, s if i % 2 else synth.reverse_complement(s)) for i, (n, s) in enumerate(synth.indel_family(4, 400, 0.03, 0.03, 48))], {}),
     ("affine-1p", synth.indel_family(4, 800, 0.04, 0.02, 49), {"scores": "0,5,8,2"}),
     ("other-2p", synth.indel_family(4, 600, 0.05, 0.03, 50), {"scores": "0,4,6,2,12,1"}),
-    # 10-level exact instance (x = 5, o1 + e1 = 10) with other second pieces: o2 + e2 = 10 (the block depth itself), 13, 31
+    # x = 5, o1 + e1 = 10 with other second pieces: o2 + e2 = 10 (the block depth itself) keeps the 10-level exact instance;
+    # 13 and 31 are no multiples of five (31 is also past its ring) and run the generic 5-level one.  blk<levels>-...: the
+    # test asserts the block depth from the workspace report
     ("blk10-o2e2-10", synth.indel_family(4, 1500, 0.05, 0.03, 5010), {"scores": "0,5,8,2,9,1"}),
-    ("blk10-o2e2-13", synth.indel_family(4, 1500, 0.05, 0.03, 5013), {"scores": "0,5,8,2,12,1"}),
-    ("blk10-o2e2-31", synth.indel_family(3, 2500, 0.06, 0.03, 5031), {"scores": "0,5,8,2,30,1"}),
+    ("blk5-o2e2-13", synth.indel_family(4, 1500, 0.05, 0.03, 5013), {"scores": "0,5,8,2,12,1"}),
+    ("blk5-o2e2-31", synth.indel_family(3, 2500, 0.06, 0.03, 5031), {"scores": "0,5,8,2,30,1"}),
     ("blk5-o2e2-9", synth.indel_family(4, 1500, 0.05, 0.03, 5009), {"scores": "0,5,8,2,8,1"}),
     ("open0", synth.indel_family(3, 400, 0.05, 0.03, 51), {"scores": "0,3,0,1"}),
     ("k8", synth.snp_family(4, 800, 0.06, 52), {"min_match_len": 8}),
@@ -147,7 +149,11 @@ def test_long_homopolymer_11068_vs_11065(gpu):
                     ("s3", (lambda b: b[:60] + b[60:65] * 4 + b[65:])(synth.to_bytes(synth.base_sequence(100, 999))))], {"min_match_len": 1}),
 ], ids=lambda x: x if isinstance(x, str) else None)
 def test_parity_cases(gpu, name, recs, kw):
-    check_parity(recs, **kw)
+    al, labels, cnt = check_parity(recs, **kw)
+    if name.startswith("blk"):
+        ctx = Context(0); ctx.load(SeqSet(recs), Params(**kw))
+        rep = ctx.workspace_report(); ctx.close()
+        assert cnt["align_kernel"] == "sr_align_blk_kernel" and rep["block_levels"] == int(name[3:name.index("-")]), rep
 
 
 def test_c2_subset_parity_8x5kb(gpu):
