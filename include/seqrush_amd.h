@@ -296,6 +296,70 @@ int sr_iterative_stop_host(const uint64_t *counts, uint64_t nchecks, uint64_t po
 int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, uint32_t **tree_i, uint32_t **tree_j,
                             uint64_t *tree_count, uint32_t **rand_i, uint32_t **rand_j, uint64_t *rand_count);
 
+/* -------- inversion patching (`--patch-inversions`; src/inversion_aware_seqrush.rs:118-255, src/cigar_analysis.rs:23-147) ----
+ * After each batch's alignment kernel the device scans every CIGAR for two-sided gaps between match ops (qgap / tgap =
+ * query- / target-only + mismatch columns, both >= m and 2 max <= 3 min; m = min_size or 2 * min_match_len).  Each such gap
+ * becomes a job: the reverse complement of the aligned query's gap segment against the target's, same penalties, orientation
+ * forced (the reference flips the target segment; this library flips the query, where its strand flag lives).  A patch is
+ * accepted when 0 <= patch score < main score / 2 and, with max_divergence, patch score <= max_score_for_divergence(min(qgap,
+ * tgap)); accepted patches are united like any alignment, strand = negated main strand.  Patches are not rescanned.
+ * sr_ctx_enable_inversions: after a load, before a run; NULL = off.  Honoured by sr_ctx_run and sr_ctx_align_all(unite = 1)
+ * (which then sync once per batch to read the job list).  Refused on PAF and iterative contexts (SR_ERR_UNSUPPORTED) and
+ * with a resolved m of 0 (SR_ERR_INVALID).  The patch pass runs on whichever kernel family the penalties select. */
+typedef struct {
+    uint64_t min_size;          /* 0 = 2 * min_match_len */
+    int32_t keep_alignments;    /* != 0: sr_ctx_inversion_alignments afterwards */
+    uint32_t reserved;
+} sr_inv_params;
+typedef struct {
+    uint64_t scanned;           /* alignments scanned (failed ones and those dropped by -d are not) */
+    uint64_t sites;             /* gaps of any kind (divergent, query-only, target-only) */
+    uint64_t candidates;        /* = jobs */
+    uint64_t accepted;
+    uint64_t rejected_score;    /* patch score >= main score / 2 */
+    uint64_t rejected_divergence;   /* passed the score rule, above the -d bound */
+    uint64_t united_bases;      /* bases united from accepted patches */
+    uint64_t patch_batches;     /* alignment kernel launches of the patch pass (0 without candidates) */
+    double scan_ms, patch_align_ms;     /* hipEvents on the context's stream: the scan's kernels (count, offsets, emit) of
+                                           every batch, without the host's reads between them; the patch alignment kernels */
+} sr_inv_stats;
+typedef struct {
+    uint64_t pair;              /* index in sr_ctx_pairs */
+    uint32_t query_idx, target_idx;
+    uint64_t query_start, query_end;    /* forward-strand query range */
+    uint64_t target_start, target_end;
+    int32_t main_score, patch_score;
+    uint8_t is_reverse;         /* the patch's strand: '-' <=> 1 */
+    uint8_t accepted;
+    uint8_t reserved[6];
+} sr_inv_job;
+int sr_ctx_enable_inversions(sr_ctx *c, const sr_inv_params *p);
+int sr_ctx_inversion_stats(sr_ctx *c, sr_inv_stats *out);
+/* the jobs of the last run in pair order, then CIGAR order; *jobs is malloc'ed (sr_free) */
+int sr_ctx_inversion_jobs(sr_ctx *c, sr_inv_job **jobs, uint64_t *count);
+/* the accepted patches of the last run in job order, start / end filled (forward-strand query coordinates, as PAF wants
+ * them); ownership passes to the caller, so a second call fails until the next run */
+int sr_ctx_inversion_alignments(sr_ctx *c, sr_alignments **out);
+/* sr_write_paf that appends to `path` and adds one more tag column (e.g. "sr:Z:inv") to every record; tag NULL = none */
+int sr_append_paf_tagged(const sr_alignments *a, const sr_seqset *seqs, const char *path, const char *tag);
+/* host twins (no device).  ops: one alignment in the sr_alignments encoding.  Sites come back in CIGAR order with the
+ * coordinates of cigar_analysis.rs:80-105 (a one-sided site has an empty range on the other side); free with sr_free */
+#define SR_INV_SITE_DIVERGENT 1
+#define SR_INV_SITE_QUERY_ONLY 2
+#define SR_INV_SITE_TARGET_ONLY 3
+typedef struct {
+    uint64_t query_start, query_end, target_start, target_end;
+    int32_t kind;               /* SR_INV_SITE_* */
+    int32_t candidate;          /* sr_inversion_candidate of its gaps */
+} sr_inv_site;
+int sr_inversion_sites_host(const uint32_t *ops, uint64_t n_ops, uint64_t min_size, sr_inv_site **sites, uint64_t *count);
+int sr_inversion_candidate(uint64_t qgap, uint64_t tgap, uint64_t min_size);    /* 1 / 0; min_size 0: SR_ERR_INVALID */
+int sr_inversion_accept(int32_t patch_score, int32_t main_score);               /* 1 / 0 */
+/* tests: the device scan over `n` alignments given like sr_alignments (cigar_off[n + 1], ops in its encoding): the jobs
+ * as sites with kind SR_INV_SITE_DIVERGENT, and their alignment index in *owner (both sr_free) */
+int sr_inversion_scan_device(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
+                             sr_inv_site **sites, uint64_t **owner, uint64_t *count);
+
 /* -------- consumer (A9): graph induction + GFA, host C++ -----------------
  * build_bidirected_graph_with_options (bidirected_builder.rs:17-289) +
  * write_gfa (bidirected_ops.rs:880-925) for --no-sort --no-compact, from

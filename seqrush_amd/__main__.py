@@ -33,6 +33,9 @@ def main(argv=None):
     ap.add_argument("--aligner", default="allwave")
     ap.add_argument("--iterative", action="store_true",
                     help="tree pairs first, then random pairs in chunks of 10 until 10 component counts in a row are unchanged")
+    ap.add_argument("--patch-inversions", action="store_true",
+                    help="realign large two-sided CIGAR gaps with the query segment reverse-complemented and unite the good ones")
+    ap.add_argument("--inversion-min-size", type=int, default=0, help="gap threshold of --patch-inversions (0 = 2 * -k)")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -44,6 +47,13 @@ def main(argv=None):
     if ns.iterative and (ns.paf is not None or ns.gpus > 1):
         # before any rank starts: the stop rule is global and sequential, and -p has no alignment stage to stop
         print(f"Error: --iterative cannot be combined with {'-p' if ns.paf is not None else '--gpus N > 1'}", file=sys.stderr)
+        return 1
+    if ns.patch_inversions and (ns.iterative or ns.paf is not None):
+        print(f"Error: --patch-inversions cannot be combined with {'--iterative' if ns.iterative else '-p'}", file=sys.stderr)
+        return 1
+    if ns.patch_inversions and (ns.inversion_min_size or 2 * ns.min_match_length) <= 0:
+        print("Error: --patch-inversions needs -k or --inversion-min-size (a threshold of 0 would call every complementary "
+              "SNP an inversion)", file=sys.stderr)
         return 1
     if ns.gpus > 1 and "RANK" not in os.environ:
         # start one process per GPU BEFORE anything here touches the GPU (never exec from a process that has)
@@ -59,7 +69,8 @@ def main(argv=None):
                 output_alignments=ns.output_alignments, no_compact=ns.no_compact, no_sort=ns.no_sort,
                 sort=ns.sort, sort_seed=ns.sort_seed, sgd_iter_max=ns.sgd_iter_max, skip_sgd=ns.skip_sgd,
                 skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
-                aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative)
+                aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative,
+                patch_inversions=ns.patch_inversions, inversion_min_size=ns.inversion_min_size)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

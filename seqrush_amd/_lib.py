@@ -30,6 +30,9 @@ EXPORTS = [
     "sr_sort_params_default", "sr_ctx_build_gfa_sorted", "sr_sort_gfa", "sr_sgd_layout", "sr_sgd_tables", "sr_sort_stats",
     "sr_ctx_load_iterative", "sr_ctx_run_iterative", "sr_ctx_iterative_stats", "sr_ctx_iterative_alignments",
     "sr_uf_count_components_host", "sr_iterative_stop_host", "sr_iterative_pair_lists",
+    "sr_ctx_enable_inversions", "sr_ctx_inversion_stats", "sr_ctx_inversion_jobs", "sr_ctx_inversion_alignments",
+    "sr_append_paf_tagged", "sr_inversion_sites_host", "sr_inversion_candidate", "sr_inversion_accept",
+    "sr_inversion_scan_device",
 ]
 
 
@@ -74,6 +77,29 @@ class IterStatsC(C.Structure):
         ("tree_k_nearest", C.c_uint32), ("tree_k_farthest", C.c_uint32), ("tree_rand_frac", C.c_double),
         ("tree_kmer", C.c_uint32), ("reserved", C.c_uint32),
     ]
+
+
+class InvParamsC(C.Structure):
+    """sr_inv_params (include/seqrush_amd.h, inversion patching)"""
+    _fields_ = [("min_size", C.c_uint64), ("keep_alignments", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class InvStatsC(C.Structure):
+    _fields_ = [("scanned", C.c_uint64), ("sites", C.c_uint64), ("candidates", C.c_uint64), ("accepted", C.c_uint64),
+                ("rejected_score", C.c_uint64), ("rejected_divergence", C.c_uint64), ("united_bases", C.c_uint64),
+                ("patch_batches", C.c_uint64), ("scan_ms", C.c_double), ("patch_align_ms", C.c_double)]
+
+
+class InvJobC(C.Structure):
+    _fields_ = [("pair", C.c_uint64), ("query_idx", C.c_uint32), ("target_idx", C.c_uint32),
+                ("query_start", C.c_uint64), ("query_end", C.c_uint64), ("target_start", C.c_uint64),
+                ("target_end", C.c_uint64), ("main_score", C.c_int32), ("patch_score", C.c_int32),
+                ("is_reverse", C.c_uint8), ("accepted", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+class InvSiteC(C.Structure):
+    _fields_ = [("query_start", C.c_uint64), ("query_end", C.c_uint64), ("target_start", C.c_uint64),
+                ("target_end", C.c_uint64), ("kind", C.c_int32), ("candidate", C.c_int32)]
 
 
 class AlignmentsC(C.Structure):
@@ -177,6 +203,16 @@ def load():
     PU32 = C.POINTER(C.POINTER(C.c_uint32))
     L.sr_iterative_pair_lists.argtypes = [C.c_uint32, C.POINTER(C.c_uint8), PP, PU32, PU32, C.POINTER(u64), PU32, PU32,
                                           C.POINTER(u64)]
+    L.sr_ctx_enable_inversions.argtypes = [vp, C.POINTER(InvParamsC)]
+    L.sr_ctx_inversion_stats.argtypes = [vp, C.POINTER(InvStatsC)]
+    L.sr_ctx_inversion_jobs.argtypes = [vp, C.POINTER(C.POINTER(InvJobC)), C.POINTER(u64)]
+    L.sr_ctx_inversion_alignments.argtypes = [vp, C.POINTER(C.POINTER(AlignmentsC))]
+    L.sr_append_paf_tagged.argtypes = [C.POINTER(AlignmentsC), PS, C.c_char_p, C.c_char_p]
+    L.sr_inversion_sites_host.argtypes = [C.POINTER(C.c_uint32), u64, u64, C.POINTER(C.POINTER(InvSiteC)), C.POINTER(u64)]
+    L.sr_inversion_candidate.argtypes = [u64, u64, u64]
+    L.sr_inversion_accept.argtypes = [C.c_int32, C.c_int32]
+    L.sr_inversion_scan_device.argtypes = [i32, C.POINTER(C.c_uint32), C.POINTER(u64), u64, u64,
+                                           C.POINTER(C.POINTER(InvSiteC)), C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

@@ -78,6 +78,7 @@ static void usage() {
     fprintf(stderr, "usage: seqrush_mi355x -s in.fa [-o output.gfa] [-k 0] [-S 0,5,8,2,24,1] [--orientation-scores 0,1,1,1]\n"
                     "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--device N]\n"
                     "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
+                    "       [--patch-inversions [--inversion-min-size N]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
@@ -87,7 +88,8 @@ int main(int argc, char **argv) {
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
-    bool no_sort = false, no_compact = false, sort = false, iterative = false, verbose = false;
+    bool no_sort = false, no_compact = false, sort = false, iterative = false, verbose = false, patch_inv = false;
+    unsigned long long inv_min = 0;
     sr_sort_params sp;
     sr_sort_params_default(&sp);
     // multi-GPU without a collective library in this host: every process aligns one shard (--shard R/N) and writes its
@@ -127,6 +129,13 @@ int main(int argc, char **argv) {
         else if (a == "--labels-in") labels_in.push_back(val("--labels-in"));
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--iterative") iterative = true;
+        else if (a == "--patch-inversions") patch_inv = true;
+        else if (a == "--inversion-min-size") {
+            const char *v = val("--inversion-min-size");
+            char *end = nullptr;
+            inv_min = strtoull(v, &end, 10);
+            if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: --inversion-min-size needs a non-negative integer, got '%s'\n", v); return 1; }
+        }
         else { usage(); return 2; }
     }
     if (sequences.empty()) { usage(); return 2; }
@@ -134,6 +143,15 @@ int main(int argc, char **argv) {
     if (iterative && (!paf_in.empty() || shard_count > 1 || !labels_out.empty() || !labels_in.empty())) {
         fprintf(stderr, "Error: --iterative cannot be combined with %s\n",
                 !paf_in.empty() ? "-p" : !labels_in.empty() ? "--labels-in" : "--shard / --labels-out");
+        return 1;
+    }
+    // --patch-inversions scans the alignments this run makes: nothing to scan with -p, --iterative or a merge run
+    if (patch_inv && (iterative || !paf_in.empty() || !labels_in.empty())) {
+        fprintf(stderr, "Error: --patch-inversions cannot be combined with %s\n", iterative ? "--iterative" : !paf_in.empty() ? "-p" : "--labels-in");
+        return 1;
+    }
+    if (patch_inv && (inv_min ? inv_min : 2ULL * (unsigned long long)(k > 0 ? k : 0)) == 0) {
+        fprintf(stderr, "Error: --patch-inversions needs -k or --inversion-min-size (a threshold of 0 would call every complementary SNP an inversion)\n");
         return 1;
     }
     if (shard_count > 1 && labels_out.empty()) {
@@ -237,6 +255,10 @@ int main(int argc, char **argv) {
         }
     } else {
         if (sr_ctx_load(ctx, &set, &p)) return die();
+        if (patch_inv) {
+            sr_inv_params ip{inv_min, paf_out.empty() ? 0 : 1, 0};
+            if (sr_ctx_enable_inversions(ctx, &ip)) return die();
+        }
     }
     if (!labels_in.empty() || iterative) {
     } else if (!paf_in.empty() || paf_out.empty()) {
@@ -247,8 +269,19 @@ int main(int argc, char **argv) {
         printf("Writing alignments to %s\n", paf_out.c_str());
         if (sr_write_paf(al, &set, paf_out.c_str())) { sr_alignments_free(al); return die(); }
         sr_alignments_free(al);
+        sr_inv_stats ist;
+        if (patch_inv && !sr_ctx_inversion_stats(ctx, &ist) && ist.candidates > 0) {     // accepted patches after the main records
+            if (sr_ctx_inversion_alignments(ctx, &al)) return die();
+            if (sr_append_paf_tagged(al, &set, paf_out.c_str(), "sr:Z:inv")) { sr_alignments_free(al); return die(); }
+            sr_alignments_free(al);
+        }
     }
     if (sr_ctx_sync(ctx)) return die();
+    if (patch_inv) {
+        sr_inv_stats ist;
+        if (sr_ctx_inversion_stats(ctx, &ist)) return die();
+        printf("Patched inversions: %llu of %llu candidate gaps\n", (unsigned long long)ist.accepted, (unsigned long long)ist.candidates);
+    }
     if (!labels_out.empty()) {                               // shard run: the forest's canonical labels, no graph
         const uint64_t ufn = sr_ctx_uf_size(ctx);
         std::vector<uint64_t> lab(ufn);

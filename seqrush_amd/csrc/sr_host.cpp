@@ -22,6 +22,7 @@
 #include "sr_graph.h"
 #include "sr_sort.h"
 #include "sr_iter_rule.h"
+#include "sr_inv_rule.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -279,6 +280,19 @@ struct sr_ctx {
     SrIterState *d_iter_state = nullptr;
     unsigned long long *d_iter_counts = nullptr;       // [iter_max_chunks] counts of the window's checks, [iter_max_chunks] spare slot
     sr_alignments *iter_al = nullptr;                  // processed alignments of the last run (keep_alignments)
+    // inversion patching (sr_ctx_enable_inversions): the scan's buffers, the jobs and results of the last run
+    bool inv_on = false, inv_keep = false;
+    uint64_t inv_m = 0;                                // resolved threshold
+    uint32_t *d_inv_count = nullptr, *d_inv_off = nullptr;      // [largest batch], [largest batch + 1]
+    unsigned long long *d_inv_stats = nullptr;         // [4]
+    SrInvJob *d_inv_jobs = nullptr;
+    uint64_t inv_job_cap = 0;
+    std::vector<SrInvJob> inv_raw;                     // job records of the run so far, pair order then CIGAR order
+    std::vector<sr_inv_job> inv_jobs;
+    sr_inv_stats inv_stats{};
+    sr_alignments *inv_al = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> inv_ev;      // one event pair per scanned batch
+    int inv_ev_used = 0;
 };
 
 static int dev_alloc(sr_ctx *c, void **p, size_t bytes) {
@@ -303,6 +317,10 @@ static void free_dev(sr_ctx *c) {
     c->iter_loaded = c->iter_keep = c->iter_ran = false; c->iter_tree_pairs = 0; c->iter_tree_batches = c->iter_max_chunks = 0;
     c->iter_counts.clear(); c->d_iter_state = nullptr; c->d_iter_counts = nullptr; c->iter_stats = sr_iter_stats{};
     if (c->iter_al) { sr_alignments_free(c->iter_al); c->iter_al = nullptr; }
+    c->inv_on = c->inv_keep = false; c->inv_m = 0; c->d_inv_count = c->d_inv_off = nullptr; c->d_inv_stats = nullptr;
+    c->d_inv_jobs = nullptr; c->inv_job_cap = 0; c->inv_raw.clear(); c->inv_jobs.clear(); c->inv_stats = sr_inv_stats{};
+    c->inv_ev_used = 0;
+    if (c->inv_al) { sr_alignments_free(c->inv_al); c->inv_al = nullptr; }
 }
 
 // event pair `idx` of kind `kind` (created on first use)
@@ -337,6 +355,7 @@ extern "C" void sr_ctx_destroy(sr_ctx *c) {
     free_dev(c);
     for (int k = 0; k < 5; k++)
         for (auto &e : c->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (auto &e : c->inv_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -924,8 +943,12 @@ static int plan_memory(sr_ctx *c, uint32_t np, Plan &pl, bool iterative = false)
 }
 
 // per-pair device arrays, workspaces, kernel arguments
+// forced_strand (the patch pass of --patch-inversions): every query is loaded in the orientation it is to be aligned in and
+// no orientation search may run: no orientation kernel and none of its buffers; the blocked kernel takes strand 0 as an
+// input (pre_oriented), the level-per-pass kernel -- which always scores both copies and lets the forward one win ties -- is
+// given the forward copy as its reverse-complement copy too, so the two searches are the same and forward is chosen
 static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, const SeqDev &sd, const SrPen &pen, const SrPen &ori,
-                           uint64_t maxlen, const std::vector<int32_t> &max_score, Plan &pl) {
+                           uint64_t maxlen, const std::vector<int32_t> &max_score, Plan &pl, bool forced_strand = false) {
     int r;
     void *d;
     const uint32_t np = (uint32_t)c->pair_q.size(), nbatch = pl.nbatch;
@@ -980,7 +1003,7 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     // CU by LDS -- 9 % slower than orientation inside the alignment kernel's workgroup).  SR_PREORIENT=1 / 0 forces.
     const char *po = knob("SR_PREORIENT");
     const bool pre_auto = (uint64_t)np >= 4ULL * (uint64_t)pl.cus && (size_t)pl.max_words * 12 <= 20 * 1024;
-    if (impl == 2 && (po ? atoi(po) != 0 : pre_auto) && (size_t)pl.max_words * 12 <= 60 * 1024) {
+    if (!forced_strand && impl == 2 && (po ? atoi(po) != 0 : pre_auto) && (size_t)pl.max_words * 12 <= 60 * 1024) {
         const int orow = (int)((2 * ((2 * maxlen + 32) & ~3ULL) + 512 + 7) & ~7ULL);
         const uint64_t oring_wg = ((uint64_t)(ori.scope + 1) * 3 + 1) * (uint64_t)orow + 256;
         int onwg = (int)std::min<uint64_t>(pl.max_batch_pairs, (uint64_t)pl.cus * 16);
@@ -1015,7 +1038,13 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     HIPCHK(hipMemsetAsync(c->d_error, 0, sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(a.cigar_cnt, 0, ((size_t)np + 1) * 4, c->stream));
     HIPCHK(hipMemsetAsync(a.score, 0xff, ((size_t)np + 1) * 4, c->stream));
+    if (forced_strand) {
+        HIPCHK(hipMemsetAsync(a.is_reverse, 0, (size_t)np + 1, c->stream));
+        HIPCHK(hipMemsetAsync(a.ori_fwd, 0, ((size_t)np + 1) * 4, c->stream));
+        HIPCHK(hipMemsetAsync(a.ori_rev, 0, ((size_t)np + 1) * 4, c->stream));
+    }
     a.seqwords = sd.words; a.word_off_fwd = sd.woff[0]; a.word_off_rc = sd.woff[1]; a.word_off_rev = sd.woff[2]; a.word_off_cmp = sd.woff[3];
+    if (forced_strand) { if (impl == 2) a.pre_oriented = 1; else a.word_off_rc = a.word_off_fwd; }
     a.symbits = pk.sm.bits; a.order = c->d_order; a.seqlen = sd.len;
     a.max_words = pl.max_words; a.pair_q = d_pq; a.pair_t = d_pt; a.npairs = np;
     a.queue_head = c->d_queue; a.pen = pen; a.ori = ori; a.mem_mode = p->memory_mode;
@@ -1076,7 +1105,7 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
 }
 
 static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const uint32_t *eq, const uint32_t *et,
-                     uint64_t ecount, bool explicit_pairs, bool iterative = false) {
+                     uint64_t ecount, bool explicit_pairs, bool iterative = false, bool forced_strand = false) {
     if (!c || !seqs || !p) return fail(SR_ERR_INVALID, "null argument");
     if (seqs->n == 0) return fail(SR_ERR_INVALID, "no sequences");
     HIPCHK(hipSetDevice(c->device));
@@ -1098,7 +1127,7 @@ static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const
     if ((r = plan_kernel(c, pk, pen, ori, maxlen, np, pl))) return r;
     if ((r = plan_workspace(c, pen, ori, maxlen, pl))) return r;
     if ((r = plan_memory(c, np, pl, iterative))) return r;
-    if ((r = alloc_workspace(c, p, pk, sd, pen, ori, maxlen, max_score, pl))) return r;
+    if ((r = alloc_workspace(c, p, pk, sd, pen, ori, maxlen, max_score, pl, forced_strand))) return r;
     write_report(c, pk, pen, pl);
     if (srk_uf_init(c->d_nodes, c->total_len, c->uf_size, c->stream)) return fail(SR_ERR_HIP, "uf init launch failed");
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1232,7 +1261,12 @@ extern "C" int sr_ctx_unite(sr_ctx *c) {
     return enqueue_unite_batch(c, 0);
 }
 
-// alignment + match-run extraction + unite of the whole pair list, batch after batch (no host sync)
+static int inv_begin_run(sr_ctx *c);
+static int inv_scan_batch(sr_ctx *c, uint32_t b);
+static int inv_patch_pass(sr_ctx *c);
+
+// alignment + match-run extraction + unite of the whole pair list, batch after batch (no host sync, unless inversion
+// patching is on: then the scan's job list is read after every batch and the patch pass follows the last one)
 extern "C" int sr_ctx_run(sr_ctx *c) {
     if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");
     int r = begin_pass(c, !c->from_paf);
@@ -1240,11 +1274,14 @@ extern "C" int sr_ctx_run(sr_ctx *c) {
     c->ev_used[1] = 0;
     const uint32_t nbatch = (uint32_t)c->batch_first.size() - 1;
     const bool fuse = c->fuse_unite && !c->from_paf;
+    if (c->inv_on && (r = inv_begin_run(c))) return r;
     for (uint32_t b = 0; b < nbatch; b++) {
         if (!c->from_paf && (r = enqueue_align_batch(c, b, fuse))) return r;
         if ((r = enqueue_unite_batch(c, b, fuse))) return r;
+        if (c->inv_on && (r = inv_scan_batch(c, b))) return r;
     }
     c->aligned_batch_valid = nbatch == 1 && !c->from_paf;
+    if (c->inv_on && (r = inv_patch_pass(c))) return r;
     return SR_OK;
 }
 
@@ -1443,8 +1480,14 @@ static int collect_batch(sr_ctx *c, uint32_t b, AlnAcc &acc) {
     return SR_OK;
 }
 
+static sr_alignments *make_alignments_of(const std::vector<uint32_t> &pair_q, const std::vector<uint32_t> &pair_t,
+                                         const std::vector<uint32_t> &len, const AlnAcc &acc, size_t count = SIZE_MAX);
 static sr_alignments *make_alignments(const sr_ctx *c, const AlnAcc &acc, size_t count = SIZE_MAX) {
-    const size_t np = std::min(count, c->pair_q.size());
+    return make_alignments_of(c->pair_q, c->pair_t, c->len, acc, count);
+}
+static sr_alignments *make_alignments_of(const std::vector<uint32_t> &pair_q, const std::vector<uint32_t> &pair_t,
+                                         const std::vector<uint32_t> &len, const AlnAcc &acc, size_t count) {
+    const size_t np = std::min(count, pair_q.size());
     sr_alignments *a = (sr_alignments *)calloc(1, sizeof(sr_alignments));
     a->n = np;
     const size_t m = np ? np : 1;
@@ -1457,10 +1500,10 @@ static sr_alignments *make_alignments(const sr_ctx *c, const AlnAcc &acc, size_t
     memcpy(a->cigar_ops, acc.ops.data(), acc.ops.size() * 4);
     uint64_t w = 0;
     for (size_t i = 0; i < np; i++) {
-        a->query_idx[i] = c->pair_q[i]; a->target_idx[i] = c->pair_t[i];
+        a->query_idx[i] = pair_q[i]; a->target_idx[i] = pair_t[i];
         a->is_reverse[i] = acc.isrev[i]; a->score[i] = acc.score[i];
-        a->query_start[i] = 0; a->query_end[i] = c->len[c->pair_q[i]];     // allwave aligns full sequences (seqrush.rs:743-753)
-        a->target_start[i] = 0; a->target_end[i] = c->len[c->pair_t[i]];
+        a->query_start[i] = 0; a->query_end[i] = len[pair_q[i]];     // allwave aligns full sequences (seqrush.rs:743-753)
+        a->target_start[i] = 0; a->target_end[i] = len[pair_t[i]];
         a->cigar_off[i] = w;
         w += acc.cnt[i];
     }
@@ -1519,13 +1562,17 @@ static int align_all_impl(sr_ctx *c, bool unite, sr_alignments **out) {
     AlnAcc acc;
     acc.cnt.assign(np + 1, 0); acc.score.assign(np + 1, 0); acc.isrev.assign(np + 1, 0);
     const uint32_t nbatch = (uint32_t)c->batch_first.size() - 1;
+    const bool inv = unite && c->inv_on;
+    if (inv && (r = inv_begin_run(c))) return r;
     for (uint32_t b = 0; b < nbatch; b++) {
         if ((r = enqueue_align_batch(c, b))) return r;
         if (unite && (r = enqueue_unite_batch(c, b))) return r;
+        if (inv && (r = inv_scan_batch(c, b))) return r;
         if ((r = sr_ctx_sync(c))) return r;
         if ((r = collect_batch(c, b, acc))) return r;
     }
     c->aligned_batch_valid = nbatch == 1;
+    if (inv && (r = inv_patch_pass(c))) return r;
     *out = make_alignments(c, acc);
     return SR_OK;
 }
@@ -1690,6 +1737,356 @@ extern "C" int sr_ctx_iterative_alignments(sr_ctx *c, sr_alignments **out) {
     if (!c->iter_al) return fail(SR_ERR_INVALID, "no processed alignments: load with keep_alignments = 1, run, and take them once");
     *out = c->iter_al;
     c->iter_al = nullptr;
+    return SR_OK;
+}
+
+// ------------------------------------------------------------------ inversion patching (--patch-inversions)
+// Rule and coordinates: sr_inv_rule.h.  Chain: after every batch's alignment kernel (and its unite, fused or not) the scan
+// (sr_inv.hip) counts the candidates of each CIGAR in the arena, turns the counts into offsets and emits the job records;
+// the host reads the total and the records (20 bytes each) before the arena is reused.  After the last batch the patch pass
+// copies the raw sequence bytes back from the device (total_len bytes, once per run: the context keeps no host copy), cuts
+// the jobs' segments out of them -- the query's already reverse-complemented where the patch is on '-' -- and loads them as a
+// set of their own through the same pack-and-upload path (an inner context on the same device and stream, load flag
+// forced_strand: pair j = (segment 2j, segment 2j + 1), aligned as loaded, no orientation search on either kernel family),
+// runs the alignment kernel over it in batches under the usual arena rule and, per batch, sr_unite_kernel over the
+// patch CIGARs with the ORIGINAL sequence indices, the patches' starts and the folded score bound, into this context's forest.
+static uint64_t inv_resolve_threshold(uint64_t min_size, uint64_t k) { return min_size ? min_size : 2 * k; }
+
+extern "C" int sr_inversion_candidate(uint64_t qgap, uint64_t tgap, uint64_t min_size) {
+    if (min_size == 0) return fail(SR_ERR_INVALID, "inversion threshold 0: every complementary SNP would be an inversion (give -k or a minimum size)");
+    return sr_inv_is_candidate(qgap, tgap, min_size);
+}
+extern "C" int sr_inversion_accept(int32_t patch_score, int32_t main_score) { return sr_inv_accept_score(patch_score, main_score); }
+
+// cigar_analysis.rs:23-128 over run-length ops in the sr_alignments encoding (2 'I' = query only, 3 'D' = target only)
+extern "C" int sr_inversion_sites_host(const uint32_t *ops, uint64_t n_ops, uint64_t min_size, sr_inv_site **sites, uint64_t *count) {
+    if ((!ops && n_ops) || !sites || !count) return fail(SR_ERR_INVALID, "null argument");
+    if (min_size == 0) return fail(SR_ERR_INVALID, "inversion threshold 0: every complementary SNP would be an inversion (give -k or a minimum size)");
+    std::vector<sr_inv_site> out;
+    uint64_t q = 0, t = 0;
+    for (uint64_t i = 0; i < n_ops; i++) {
+        const uint32_t op = ops[i] & 3u; const uint64_t len = ops[i] >> 4;
+        if (op == 0) {
+            uint64_t qg = 0, tg = 0;
+            for (uint64_t j = i + 1; j < n_ops && (ops[j] & 3u) != 0; j++) {
+                const uint32_t o2 = ops[j] & 3u; const uint64_t l2 = ops[j] >> 4;
+                if (o2 == 1) { qg += l2; tg += l2; } else if (o2 == 2) qg += l2; else tg += l2;
+            }
+            const int kind = sr_inv_site_kind(qg, tg, min_size);
+            if (kind != SR_INV_NONE) {
+                sr_inv_site s;
+                s.query_start = q + len; s.target_start = t + len;
+                s.query_end = s.query_start + (kind == SR_INV_TARGET_ONLY ? 0 : qg);
+                s.target_end = s.target_start + (kind == SR_INV_QUERY_ONLY ? 0 : tg);
+                s.kind = kind; s.candidate = sr_inv_is_candidate(qg, tg, min_size);
+                out.push_back(s);
+            }
+            q += len; t += len;
+        } else if (op == 1) { q += len; t += len; }
+        else if (op == 2) q += len;
+        else t += len;
+    }
+    *count = out.size();
+    *sites = (sr_inv_site *)malloc((out.empty() ? 1 : out.size()) * sizeof(sr_inv_site));
+    if (!*sites) return fail(SR_ERR_NOMEM, "out of memory");
+    memcpy(*sites, out.data(), out.size() * sizeof(sr_inv_site));
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_enable_inversions(sr_ctx *c, const sr_inv_params *p) {
+    if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");
+    if (!p) { c->inv_on = false; return SR_OK; }
+    if (c->from_paf) return fail(SR_ERR_UNSUPPORTED, "inversion patching needs the alignment stage: it cannot be combined with PAF input");
+    if (c->iter_loaded) return fail(SR_ERR_UNSUPPORTED, "inversion patching cannot be combined with the iterative mode");
+    const uint64_t m = inv_resolve_threshold(p->min_size, c->prm.min_match_len);
+    if (m == 0) return fail(SR_ERR_INVALID, "inversion threshold 0: every complementary SNP would be an inversion (give -k or a minimum size)");
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_inv_count) {
+        uint32_t maxb = 1;
+        for (size_t b = 0; b + 1 < c->batch_first.size(); b++) maxb = std::max(maxb, c->batch_first[b + 1] - c->batch_first[b]);
+        int r;
+        void *d;
+        if ((r = dev_alloc(c, &d, (size_t)maxb * 4))) return r; c->d_inv_count = (uint32_t *)d;
+        if ((r = dev_alloc(c, &d, ((size_t)maxb + 1) * 4))) return r; c->d_inv_off = (uint32_t *)d;
+        if ((r = dev_alloc(c, &d, 4 * sizeof(unsigned long long)))) return r; c->d_inv_stats = (unsigned long long *)d;
+    }
+    c->inv_m = m; c->inv_keep = p->keep_alignments != 0; c->inv_on = true;
+    return SR_OK;
+}
+
+static int inv_begin_run(sr_ctx *c) {
+    c->inv_raw.clear(); c->inv_jobs.clear(); c->inv_stats = sr_inv_stats{}; c->inv_ev_used = 0;
+    if (c->inv_al) { sr_alignments_free(c->inv_al); c->inv_al = nullptr; }
+    HIPCHK(hipMemsetAsync(c->d_inv_stats, 0, 4 * sizeof(unsigned long long), c->stream));
+    return SR_OK;
+}
+
+// count, offsets, (host reads the total,) emit, (host reads the records) for one batch whose CIGARs are in the arena
+// ev: two event pairs (or NULL): [0] around count + offsets, [1] around emit -- kernels only, not the host round trips
+static int inv_scan_launch(hipStream_t stream, SrInvScanArgs &s, uint32_t *d_off, std::vector<void *> *allocs, SrInvJob **d_jobs,
+                           uint64_t *job_cap, std::vector<SrInvJob> &out, std::pair<hipEvent_t, hipEvent_t> *ev = nullptr,
+                           int *ev_used = nullptr) {
+    if (s.npairs == 0) return SR_OK;
+    if (ev) HIPCHK(hipEventRecord(ev[0].first, stream));
+    if (srk_inv_scan(&s, 0, stream) || srk_inv_offsets(s.count, s.npairs, d_off, stream)) return fail(SR_ERR_HIP, "inversion scan kernel launch failed");
+    if (ev) { HIPCHK(hipEventRecord(ev[0].second, stream)); *ev_used = 1; }
+    uint32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + s.npairs, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (total == 0) return SR_OK;
+    if (total > *job_cap) {
+        const uint64_t cap = std::max<uint64_t>(total, 2 * *job_cap);
+        void *d = nullptr;
+        if (hipMalloc(&d, cap * sizeof(SrInvJob)) != hipSuccess) return fail(SR_ERR_NOMEM, "not enough device memory for the inversion job list");
+        if (*d_jobs) {                                     // (the stream is idle: the smaller buffer's records were copied out)
+            auto it = std::find(allocs->begin(), allocs->end(), (void *)*d_jobs);
+            if (it != allocs->end()) allocs->erase(it);
+            (void)hipFree(*d_jobs);
+        }
+        allocs->push_back(d);
+        *d_jobs = (SrInvJob *)d; *job_cap = cap;
+    }
+    s.offset = d_off; s.jobs = *d_jobs; s.job_cap = *job_cap;
+    if (ev) HIPCHK(hipEventRecord(ev[1].first, stream));
+    if (srk_inv_scan(&s, 1, stream)) return fail(SR_ERR_HIP, "inversion scan kernel launch failed");
+    if (ev) { HIPCHK(hipEventRecord(ev[1].second, stream)); *ev_used = 2; }
+    const size_t at = out.size();
+    out.resize(at + total);
+    HIPCHK(hipMemcpyAsync(out.data() + at, *d_jobs, (size_t)total * sizeof(SrInvJob), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return SR_OK;
+}
+
+static int inv_scan_batch(sr_ctx *c, uint32_t b) {
+    SrUniteArgs u;
+    batch_args(c, b, nullptr, &u);
+    while ((int)c->inv_ev.size() < c->inv_ev_used + 2) {
+        hipEvent_t x = nullptr, y = nullptr;
+        HIPCHK(hipEventCreate(&x)); HIPCHK(hipEventCreate(&y));
+        c->inv_ev.push_back({x, y});
+    }
+    SrInvScanArgs s{};
+    s.cigar_ops = u.cigar_ops; s.cigar_base = u.cigar_base; s.cigar_cnt = u.cigar_cnt; s.score = u.score; s.max_score = u.max_score;
+    s.npairs = u.npairs; s.pair0 = c->batch_first[b]; s.min_size = c->inv_m; s.count = c->d_inv_count; s.stats = c->d_inv_stats;
+    int used = 0;
+    const int r = inv_scan_launch(c->stream, s, c->d_inv_off, &c->dev_allocs, &c->d_inv_jobs, &c->inv_job_cap, c->inv_raw,
+                                  c->inv_ev.data() + c->inv_ev_used, &used);
+    if (r) return r;
+    c->inv_ev_used += used;
+    return SR_OK;
+}
+
+static int inv_patch_pass(sr_ctx *c) {
+    int r;
+    if ((r = sr_ctx_sync(c))) return r;
+    sr_inv_stats &st = c->inv_stats;
+    unsigned long long ds[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(ds, c->d_inv_stats, sizeof(ds), hipMemcpyDeviceToHost));
+    st.scanned = ds[0]; st.sites = ds[1]; st.candidates = ds[2];
+    for (int i = 0; i < c->inv_ev_used; i++) {
+        float t = 0;
+        HIPCHK(hipEventSynchronize(c->inv_ev[i].second));
+        HIPCHK(hipEventElapsedTime(&t, c->inv_ev[i].first, c->inv_ev[i].second));
+        st.scan_ms += t;
+    }
+    const size_t nj = c->inv_raw.size();
+    if ((uint64_t)nj != st.candidates) return fail(SR_ERR_DEVICE_FAULT, "inversion scan: the emitted job records do not match the counted candidates");
+    if (nj == 0) return SR_OK;                             // nothing to patch: no launch, the forest is the plain run's
+    if (nj > 0x7ffffff0ULL) return fail(SR_ERR_UNSUPPORTED, "more than 2^31 inversion candidates");
+    const size_t np = c->pair_q.size();
+    std::vector<int32_t> score(np);
+    std::vector<uint8_t> isrev(np), bases(c->total_len);
+    HIPCHK(hipMemcpy(score.data(), c->aa.score, np * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(isrev.data(), c->aa.is_reverse, np, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(bases.data(), c->d_bases, c->total_len, hipMemcpyDeviceToHost));
+    // segment set: 2 j = the pattern (the query's forward segment, reverse-complemented for a '-' patch -- the same bytes as
+    // the reverse complement of the ALIGNED query's gap), 2 j + 1 = the target's segment; patch strand = negated main strand
+    std::vector<uint8_t> seg;
+    std::vector<uint64_t> soff(1, 0);
+    std::vector<uint32_t> eq(nj), et(nj), opq(nj), opt(nj), qs(nj), ts(nj);
+    std::vector<uint8_t> strand(nj);
+    std::vector<int32_t> bound(nj);
+    c->inv_jobs.assign(nj, sr_inv_job{});
+    for (size_t j = 0; j < nj; j++) {
+        const SrInvJob &w = c->inv_raw[j];
+        if (w.pair >= np) return fail(SR_ERR_DEVICE_FAULT, "inversion scan: job record with a pair index out of range");
+        const uint32_t q = c->pair_q[w.pair], t = c->pair_t[w.pair];
+        const uint64_t lq = c->len[q], lt = c->len[t];
+        if ((uint64_t)w.qa + w.qgap > lq || (uint64_t)w.ta + w.tgap > lt || w.qgap == 0 || w.tgap == 0)
+            return fail(SR_ERR_DEVICE_FAULT, "inversion scan: job record outside its sequences");
+        const bool main_rev = isrev[w.pair] != 0;
+        const uint64_t fq = main_rev ? lq - w.qa - w.qgap : w.qa;
+        if (main_rev) seg.insert(seg.end(), bases.begin() + (c->goff[q] + fq), bases.begin() + (c->goff[q] + fq + w.qgap));
+        else for (uint64_t k = 0; k < w.qgap; k++) seg.push_back(comp_base(bases[c->goff[q] + fq + w.qgap - 1 - k]));
+        soff.push_back(seg.size());
+        seg.insert(seg.end(), bases.begin() + (c->goff[t] + w.ta), bases.begin() + (c->goff[t] + w.ta + w.tgap));
+        soff.push_back(seg.size());
+        eq[j] = (uint32_t)(2 * j); et[j] = (uint32_t)(2 * j + 1); opq[j] = q; opt[j] = t;
+        strand[j] = main_rev ? 0 : 1;
+        qs[j] = (uint32_t)(lq - w.qa - w.qgap);            // first query position in the patch's own space (sr_inv_rule.h)
+        ts[j] = w.ta;
+        int32_t bd = sr_inv_score_bound(score[w.pair]);
+        if (c->prm.max_divergence >= 0.0)
+            bd = std::min(bd, max_score_for_divergence(c->prm, std::min<uint64_t>(w.qgap, w.tgap), c->prm.max_divergence));
+        bound[j] = bd;
+        sr_inv_job &o = c->inv_jobs[j];
+        o.pair = w.pair; o.query_idx = q; o.target_idx = t; o.query_start = fq; o.query_end = fq + w.qgap;
+        o.target_start = w.ta; o.target_end = (uint64_t)w.ta + w.tgap; o.main_score = score[w.pair]; o.patch_score = -1;
+        o.is_reverse = strand[j]; o.accepted = 0;
+    }
+    sr_seqset ss{(uint32_t)(2 * nj), seg.data(), soff.data(), nullptr};
+    sr_params pp = c->prm;
+    pp.sparsify_kind = SR_SPARSE_NONE; pp.shard_rank = 0; pp.shard_count = 1; pp.max_divergence = -1.0;
+    sr_ctx *in = new sr_ctx();
+    in->device = c->device; in->stream = c->stream; in->own_stream = false;
+    struct Guard { sr_ctx *p; ~Guard() { std::string keep = g_err; sr_ctx_destroy(p); g_err = keep; } } guard{in};
+    if ((r = load_impl(in, &ss, &pp, eq.data(), et.data(), nj, true, false, true))) return r;      // forced_strand
+    uint32_t *d_opq, *d_opt, *d_qs, *d_ts; int32_t *d_bound; uint8_t *d_strand;
+    void *d;
+#define INV_UP(dst, T, v)                                                                     \
+    do {                                                                                      \
+        if ((r = dev_alloc(in, &d, (v).size() * sizeof(T)))) return r;                        \
+        HIPCHK(hipMemcpyAsync(d, (v).data(), (v).size() * sizeof(T), hipMemcpyHostToDevice, c->stream)); \
+        dst = (T *)d;                                                                         \
+    } while (0)
+    INV_UP(d_opq, uint32_t, opq); INV_UP(d_opt, uint32_t, opt); INV_UP(d_qs, uint32_t, qs); INV_UP(d_ts, uint32_t, ts);
+    INV_UP(d_bound, int32_t, bound); INV_UP(d_strand, uint8_t, strand);
+#undef INV_UP
+    HIPCHK(hipStreamSynchronize(c->stream));
+    AlnAcc acc;
+    if (c->inv_keep) { acc.cnt.assign(nj + 1, 0); acc.score.assign(nj + 1, 0); acc.isrev.assign(nj + 1, 0); }
+    const uint32_t nbatch = (uint32_t)in->batch_first.size() - 1;
+    in->ev_used[0] = in->ev_used[4] = 0;
+    for (uint32_t b = 0; b < nbatch; b++) {
+        if ((r = enqueue_align_batch(in, b, false))) return r;
+        SrUniteArgs u;
+        batch_args(in, b, nullptr, &u);
+        const uint32_t f = in->batch_first[b];
+        u.pair_q = d_opq + f; u.pair_t = d_opt + f; u.seqlen = c->ua.seqlen; u.seq_goff = c->ua.seq_goff;
+        u.q_start = d_qs + f; u.t_start = d_ts + f; u.max_score = d_bound + f; u.is_reverse = d_strand + f;
+        u.nodes = c->d_nodes; u.uf_size = c->uf_size; u.counters = in->d_counters; u.error_flag = c->d_error;
+        if (u.npairs > 0 && srk_unite(&u, (int)std::min<uint64_t>(u.npairs, 4096), c->stream))
+            return fail(SR_ERR_HIP, "unite kernel launch failed");
+        if (c->inv_keep && ((r = sr_ctx_sync(in)) || (r = collect_batch(in, b, acc)))) return r;
+    }
+    if ((r = sr_ctx_sync(in)) || (r = sr_ctx_sync(c))) return r;
+    std::vector<int32_t> ps(nj);
+    HIPCHK(hipMemcpy(ps.data(), in->aa.score, nj * 4, hipMemcpyDeviceToHost));
+    unsigned long long cnt[8];
+    HIPCHK(hipMemcpy(cnt, in->d_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+    st.united_bases = cnt[4]; st.patch_batches = nbatch;
+    { float ms = 0; if (sr_ctx_kernel_ms(in, 0, &ms) == SR_OK) st.patch_align_ms = ms; }
+    for (size_t j = 0; j < nj; j++) {
+        sr_inv_job &o = c->inv_jobs[j];
+        o.patch_score = ps[j];
+        if (!sr_inv_accept_score(ps[j], o.main_score)) st.rejected_score++;
+        else if (ps[j] > bound[j]) st.rejected_divergence++;
+        else { o.accepted = 1; st.accepted++; }
+    }
+    if (c->inv_keep) {                                     // the accepted patches as sr_alignments, PAF coordinates
+        AlnAcc ka;
+        std::vector<size_t> keep;
+        size_t w = 0;
+        for (size_t j = 0; j < nj; j++) {
+            if (c->inv_jobs[j].accepted) {
+                keep.push_back(j); ka.cnt.push_back(acc.cnt[j]); ka.score.push_back(acc.score[j]); ka.isrev.push_back(acc.isrev[j]);
+                ka.ops.insert(ka.ops.end(), acc.ops.begin() + w, acc.ops.begin() + w + acc.cnt[j]);
+            }
+            w += acc.cnt[j];
+        }
+        ka.cnt.push_back(0); ka.score.push_back(0); ka.isrev.push_back(0);
+        std::vector<uint32_t> kq, kt;
+        for (size_t j : keep) { kq.push_back(opq[j]); kt.push_back(opt[j]); }
+        sr_alignments *al = make_alignments_of(kq, kt, c->len, ka);
+        for (size_t i = 0; i < keep.size(); i++) {
+            const sr_inv_job &o = c->inv_jobs[keep[i]];
+            al->query_start[i] = o.query_start; al->query_end[i] = o.query_end;
+            al->target_start[i] = o.target_start; al->target_end[i] = o.target_end;
+            al->is_reverse[i] = o.is_reverse;
+        }
+        c->inv_al = al;
+    }
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_inversion_stats(sr_ctx *c, sr_inv_stats *out) {
+    if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
+    *out = c->inv_stats;
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_inversion_jobs(sr_ctx *c, sr_inv_job **jobs, uint64_t *count) {
+    if (!c || !c->loaded || !jobs || !count) return fail(SR_ERR_INVALID, "context not loaded");
+    const size_t n = c->inv_jobs.size();
+    *jobs = (sr_inv_job *)malloc((n ? n : 1) * sizeof(sr_inv_job));
+    if (!*jobs) return fail(SR_ERR_NOMEM, "out of memory");
+    memcpy(*jobs, c->inv_jobs.data(), n * sizeof(sr_inv_job));
+    *count = n;
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_inversion_alignments(sr_ctx *c, sr_alignments **out) {
+    if (!c || !out) return fail(SR_ERR_INVALID, "null argument");
+    if (!c->inv_al) return fail(SR_ERR_INVALID, "no patch alignments: enable with keep_alignments = 1, run, and take them once (none are kept when no job ran)");
+    *out = c->inv_al;
+    c->inv_al = nullptr;
+    return SR_OK;
+}
+
+// tests: the scan kernels over alignments given on the host
+extern "C" int sr_inversion_scan_device(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
+                                        sr_inv_site **sites, uint64_t **owner, uint64_t *count) {
+    if (!cigar_off || !sites || !owner || !count || (!ops && n && cigar_off[n])) return fail(SR_ERR_INVALID, "null argument");
+    if (min_size == 0) return fail(SR_ERR_INVALID, "inversion threshold 0");
+    if (n == 0 || n > 0x7fffffffULL) return fail(SR_ERR_INVALID, "bad alignment count");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SR_ERR_NO_DEVICE, "no HIP device available (seqrush_amd has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(SR_ERR_INVALID, "device ordinal out of range");
+    HIPCHK(hipSetDevice(device));
+    const uint64_t nops = cigar_off[n];
+    std::vector<uint32_t> raw(nops ? nops : 1), cnt(n);
+    for (uint64_t i = 0; i < nops; i++) {                  // reference alphabet -> raw device alphabet (I <-> D)
+        const uint32_t op = ops[i] & 3u;
+        raw[i] = (ops[i] & ~15u) | (op == 0 ? SR_OP_M : op == 1 ? SR_OP_X : op == 2 ? SR_OP_D : SR_OP_I);
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        if (cigar_off[i + 1] < cigar_off[i] || cigar_off[i + 1] - cigar_off[i] > 0xffffffffULL) return fail(SR_ERR_INVALID, "bad cigar_off");
+        cnt[i] = (uint32_t)(cigar_off[i + 1] - cigar_off[i]);
+    }
+    struct Tmp { std::vector<void *> v; ~Tmp() { for (void *q : v) (void)hipFree(q); } } tmp;
+    auto up = [&](const void *src, size_t bytes) -> void * {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+        tmp.v.push_back(q);
+        if (src && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return q;
+    };
+    SrInvScanArgs s{};
+    s.cigar_ops = (const uint32_t *)up(raw.data(), raw.size() * 4);
+    s.cigar_base = (const uint64_t *)up(cigar_off, (n + 1) * 8);
+    s.cigar_cnt = (const uint32_t *)up(cnt.data(), n * 4);
+    s.count = (uint32_t *)up(nullptr, n * 4);
+    uint32_t *d_off = (uint32_t *)up(nullptr, (n + 1) * 4);
+    s.stats = (unsigned long long *)up(nullptr, 32);
+    if (!s.cigar_ops || !s.cigar_base || !s.cigar_cnt || !s.count || !d_off || !s.stats) return fail(SR_ERR_NOMEM, "device allocation failed");
+    HIPCHK(hipMemset(s.stats, 0, 32));
+    s.npairs = (uint32_t)n; s.pair0 = 0; s.min_size = min_size;
+    std::vector<SrInvJob> jobs;
+    SrInvJob *d_jobs = nullptr;
+    uint64_t cap = 0;
+    const int r = inv_scan_launch(nullptr, s, d_off, &tmp.v, &d_jobs, &cap, jobs);
+    if (r) return r;
+    *count = jobs.size();
+    *sites = (sr_inv_site *)malloc((jobs.empty() ? 1 : jobs.size()) * sizeof(sr_inv_site));
+    *owner = (uint64_t *)malloc((jobs.empty() ? 1 : jobs.size()) * 8);
+    if (!*sites || !*owner) return fail(SR_ERR_NOMEM, "out of memory");
+    for (size_t j = 0; j < jobs.size(); j++) {
+        sr_inv_site &o = (*sites)[j];
+        o.query_start = jobs[j].qa; o.query_end = (uint64_t)jobs[j].qa + jobs[j].qgap;
+        o.target_start = jobs[j].ta; o.target_end = (uint64_t)jobs[j].ta + jobs[j].tgap;
+        o.kind = SR_INV_DIVERGENT; o.candidate = 1;
+        (*owner)[j] = jobs[j].pair;
+    }
     return SR_OK;
 }
 
@@ -1973,9 +2370,16 @@ extern "C" int sr_uf_canonical_labels_host(const uint64_t *nodes, uint64_t n, ui
 }
 
 // ------------------------------------------------------------------ PAF (seam 3)
+static int write_paf_impl(const sr_alignments *a, const sr_seqset *seqs, const char *path, const char *mode, const char *tag);
 extern "C" int sr_write_paf(const sr_alignments *a, const sr_seqset *seqs, const char *path) {
+    return write_paf_impl(a, seqs, path, "w", nullptr);
+}
+extern "C" int sr_append_paf_tagged(const sr_alignments *a, const sr_seqset *seqs, const char *path, const char *tag) {
+    return write_paf_impl(a, seqs, path, "a", tag);
+}
+static int write_paf_impl(const sr_alignments *a, const sr_seqset *seqs, const char *path, const char *mode, const char *tag) {
     if (!a || !seqs || !path || !seqs->names) return fail(SR_ERR_INVALID, "null argument");
-    FILE *f = fopen(path, "w");
+    FILE *f = fopen(path, mode);
     if (!f) return fail(SR_ERR_IO, std::string("cannot open ") + path);
     std::vector<char> buf;
     for (uint64_t i = 0; i < a->n; i++) {
@@ -1990,13 +2394,13 @@ extern "C" int sr_write_paf(const sr_alignments *a, const sr_seqset *seqs, const
         buf.resize(need + 1);
         sr_alignment_cigar(a, i, buf.data(), need + 1);
         // 12 mandatory PAF columns + cg:Z: (parsed by seqrush.rs:536-559)
-        fprintf(f, "%s\t%llu\t%llu\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tAS:i:%d\tcg:Z:%s\n",
+        fprintf(f, "%s\t%llu\t%llu\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tAS:i:%d\tcg:Z:%s%s%s\n",
                 seqs->names[q], (unsigned long long)(seqs->offsets[q + 1] - seqs->offsets[q]),
                 (unsigned long long)a->query_start[i], (unsigned long long)a->query_end[i],
                 a->is_reverse[i] ? '-' : '+', seqs->names[t],
                 (unsigned long long)(seqs->offsets[t + 1] - seqs->offsets[t]),
                 (unsigned long long)a->target_start[i], (unsigned long long)a->target_end[i],
-                (unsigned long long)matches, (unsigned long long)alen, a->score[i], buf.data());
+                (unsigned long long)matches, (unsigned long long)alen, a->score[i], buf.data(), tag ? "\t" : "", tag ? tag : "");
     }
     fclose(f);
     return SR_OK;

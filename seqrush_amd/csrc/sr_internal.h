@@ -136,9 +136,29 @@ struct SrUniteArgs {
     int *error_flag;
 };
 
+// sr_inv.hip: CIGAR scan of --patch-inversions over one batch (sr_inv_rule.h)
+struct SrInvJob;
+struct SrInvScanArgs {
+    const uint32_t *cigar_ops;
+    const uint64_t *cigar_base;     // [npairs] relative to cigar_ops
+    const uint32_t *cigar_cnt;      // [npairs]
+    const int32_t *score;           // [npairs] main score (< 0: failed, not scanned); NULL = scan every alignment
+    const int32_t *max_score;       // [npairs] divergence bound of the main pass (score above it: not scanned) or NULL
+    uint32_t npairs;
+    uint32_t pair0;                 // index of the batch's first pair in the context's list (job records carry pair0 + i)
+    unsigned long long min_size;    // threshold m >= 1
+    uint32_t *count;                // [npairs] pass 0 out: candidates per alignment
+    const uint32_t *offset;         // [npairs + 1] pass 1 in: exclusive offsets of count
+    struct SrInvJob *jobs;          // pass 1 out
+    uint64_t job_cap;               // records `jobs` holds
+    unsigned long long *stats;      // pass 0: [0] alignments scanned, [1] sites of any kind, [2] candidates
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+int srk_inv_scan(const struct SrInvScanArgs *a, int emit, void *stream);
+int srk_inv_offsets(const uint32_t *count, uint32_t n, uint32_t *off, void *stream);
 // launchers implemented in sr_device.hip (hipStream_t passed as void*)
 int srk_align(const SrAlignArgs *a, int nwg, size_t lds_bytes, int off16, int nthreads, void *stream);   // by a->impl, a->symbits
 int srk_unite(const SrUniteArgs *a, int nwg, void *stream);

@@ -13,7 +13,8 @@ from typing import List, Optional, Sequence as Seq
 import numpy as np
 
 from . import _lib
-from ._lib import ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, check, SeqRushError
+from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, check,
+                   SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -47,6 +48,8 @@ class Args:
     shard_count: int = 1
     gpus: int = 1                           # added: --gpus N, one process per GPU under torch.distributed.run
     iterative: bool = False                 # --iterative: tree pairs, then random pairs until the components are stable
+    patch_inversions: bool = False          # added: --patch-inversions, realign large two-sided CIGAR gaps on the other strand
+    inversion_min_size: int = 0             # added: --inversion-min-size N (0 = 2 * min_match_length)
 
 
 @dataclasses.dataclass
@@ -221,6 +224,10 @@ class Alignments:
     def write_paf(self, seqset: SeqSet, path: str):
         check(_lib.load().sr_write_paf(self._p, C.byref(seqset.c), path.encode()))
 
+    def append_paf(self, seqset: SeqSet, path: str, tag: Optional[str] = None):
+        """append the records to `path`, each with one more tag column (e.g. "sr:Z:inv")"""
+        check(_lib.load().sr_append_paf_tagged(self._p, C.byref(seqset.c), path.encode(), tag.encode() if tag else None))
+
     def close(self):
         if self._p:
             _lib.load().sr_alignments_free(self._p)
@@ -317,6 +324,34 @@ class Context:
         """the processed alignments of the last iterative run, in processing order (load with keep_alignments=True)"""
         p = C.POINTER(AlignmentsC)()
         check(self.L.sr_ctx_iterative_alignments(self._h, C.byref(p)))
+        return Alignments(p)
+
+    def enable_inversions(self, min_size: int = 0, keep_alignments: bool = False, on: bool = True):
+        """--patch-inversions for the next run() / align_all(unite=True) of the loaded context (min_size 0 = 2 * -k)"""
+        if not on:
+            check(self.L.sr_ctx_enable_inversions(self._h, None))
+            return
+        ip = InvParamsC(int(min_size), 1 if keep_alignments else 0, 0)
+        check(self.L.sr_ctx_enable_inversions(self._h, C.byref(ip)))
+
+    def inversion_stats(self):
+        """sr_inv_stats of the last run -> dict"""
+        st = InvStatsC()
+        check(self.L.sr_ctx_inversion_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in InvStatsC._fields_}
+
+    def inversion_jobs(self):
+        """the jobs of the last run (pair order, then CIGAR order) -> list of dicts of the sr_inv_job fields"""
+        p = C.POINTER(InvJobC)(); cnt = C.c_uint64()
+        check(self.L.sr_ctx_inversion_jobs(self._h, C.byref(p), C.byref(cnt)))
+        out = [{f: int(getattr(p[i], f)) for f, _ in InvJobC._fields_ if f != "reserved"} for i in range(cnt.value)]
+        self.L.sr_free(C.cast(p, C.c_void_p))
+        return out
+
+    def inversion_alignments(self) -> "Alignments":
+        """the accepted patches of the last run (enable with keep_alignments=True), forward-strand query coordinates"""
+        p = C.POINTER(AlignmentsC)()
+        check(self.L.sr_ctx_inversion_alignments(self._h, C.byref(p)))
         return Alignments(p)
 
     def load_paf(self, seqset: SeqSet, params: Params, paf_path: str):
@@ -595,6 +630,11 @@ class SeqRush:
         """align_and_unite_with_allwave (src/seqrush.rs:611-757) on the device"""
         if args.iterative and args.paf is not None:
             raise SeqRushError(-6, "--iterative cannot be combined with -p (there is no alignment stage to stop)")
+        if args.patch_inversions and (args.iterative or args.paf is not None):
+            raise SeqRushError(-6, f"--patch-inversions cannot be combined with {'--iterative' if args.iterative else '-p'}")
+        if args.patch_inversions and (args.inversion_min_size or 2 * args.min_match_length) == 0:
+            raise SeqRushError(-1, "--patch-inversions needs -k or --inversion-min-size: a threshold of 0 would call every "
+                                   "complementary SNP an inversion")
         if args.paf is not None:                      # align_and_unite_from_paf (src/seqrush.rs:510-609)
             print(f"Reading alignments from PAF file: {args.paf}")
             self.ctx.load_paf(self.seqset, Params.from_args(args), args.paf)
@@ -611,14 +651,21 @@ class SeqRush:
         self.ctx.load(self.seqset, params)
         n = len(self.sequences)
         print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
+        if args.patch_inversions:
+            self.ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments))
         if args.output_alignments:
             al = self.ctx.align_all(unite=True)         # batches: align, copy the CIGARs out, unite
             print(f"Writing alignments to {args.output_alignments}")
             al.write_paf(self.seqset, args.output_alignments)
             al.close()
+            append_inversion_paf(self.ctx, self.seqset, args.output_alignments, args.patch_inversions)
         else:
             self.ctx.run()
         self.ctx.sync()
+        if args.patch_inversions:
+            st = self.ctx.inversion_stats()
+            self.inversion_stats = st
+            print(f"Patched inversions: {st['accepted']} of {st['candidates']} candidate gaps")
         self.labels = self.ctx.download_labels()
         self.ctx.sync()
 
@@ -715,13 +762,22 @@ def run_seqrush_rank(args: Args):
         if rank == 0:
             n = len(sequences)
             print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
+        if args.patch_inversions:               # a job stays on the rank that owns its pair and lands in that rank's forest
+            ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments))
         if args.output_alignments:
             al = ctx.align_all(unite=True)
             al.write_paf(sr.seqset, f"{args.output_alignments}.rank{rank}")
             al.close()
+            append_inversion_paf(ctx, sr.seqset, f"{args.output_alignments}.rank{rank}", args.patch_inversions)
         else:
             ctx.run()
     ctx.sync()
+    if args.patch_inversions and args.paf is None:
+        st = ctx.inversion_stats()
+        tot = torch.tensor([st["accepted"], st["candidates"]], dtype=torch.int64, device="cpu" if single_dev else "cuda")
+        dist.all_reduce(tot)
+        if rank == 0:
+            print(f"Patched inversions: {int(tot[0])} of {int(tot[1])} candidate gaps")
     ufn = ctx.uf_size
     u32 = ufn < (1 << 32)
     ldt = torch.int32 if u32 else torch.int64
@@ -755,6 +811,63 @@ def run_seqrush_rank(args: Args):
 
 
 SR_SPARSE_TREE = 4
+
+
+def append_inversion_paf(ctx: Context, seqset: SeqSet, path: str, on: bool = True):
+    """--output-alignments with --patch-inversions: the accepted patches after the main records, tagged sr:Z:inv"""
+    if not on or ctx.inversion_stats()["candidates"] == 0:
+        return
+    al = ctx.inversion_alignments()
+    al.append_paf(seqset, path, "sr:Z:inv")
+    al.close()
+
+
+def _ops_array(ops):
+    a = np.ascontiguousarray(ops, dtype=np.uint32)
+    return a, a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _sites(p, n):
+    return [dict(query_start=int(p[i].query_start), query_end=int(p[i].query_end), target_start=int(p[i].target_start),
+                 target_end=int(p[i].target_end), kind=int(p[i].kind), candidate=bool(p[i].candidate)) for i in range(n)]
+
+
+def inversion_sites_host(ops, min_size: int):
+    """the gaps of one alignment (ops in the sr_alignments encoding, (len << 4) | 0 '=' 1 X 2 I 3 D) -> list of dicts;
+    kind 1 divergent, 2 query-only, 3 target-only (src/cigar_analysis.rs:23-128)"""
+    L = _lib.load()
+    a, ap = _ops_array(ops)
+    p = C.POINTER(InvSiteC)(); cnt = C.c_uint64()
+    check(L.sr_inversion_sites_host(ap, len(a), int(min_size), C.byref(p), C.byref(cnt)))
+    out = _sites(p, cnt.value)
+    L.sr_free(C.cast(p, C.c_void_p))
+    return out
+
+
+def inversion_candidate(qgap: int, tgap: int, min_size: int) -> bool:
+    r = _lib.load().sr_inversion_candidate(int(qgap), int(tgap), int(min_size))
+    if r < 0:
+        check(r)
+    return r == 1
+
+
+def inversion_accept(patch_score: int, main_score: int) -> bool:
+    return _lib.load().sr_inversion_accept(int(patch_score), int(main_score)) == 1
+
+
+def inversion_scan_device(cigars, min_size: int, device: int = 0):
+    """tests: the device scan over a list of op arrays -> [(alignment index, site dict)] in job order"""
+    L = _lib.load()
+    off = np.zeros(len(cigars) + 1, dtype=np.uint64)
+    np.cumsum([len(c) for c in cigars], out=off[1:])
+    a, ap = _ops_array(np.concatenate([np.asarray(c, dtype=np.uint32) for c in cigars]) if len(cigars) else [])
+    p = C.POINTER(InvSiteC)(); ow = C.POINTER(C.c_uint64)(); cnt = C.c_uint64()
+    check(L.sr_inversion_scan_device(device, ap, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(cigars), int(min_size),
+                                     C.byref(p), C.byref(ow), C.byref(cnt)))
+    sites = _sites(p, cnt.value)
+    out = [(int(ow[i]), sites[i]) for i in range(cnt.value)]
+    L.sr_free(C.cast(p, C.c_void_p)); L.sr_free(C.cast(ow, C.c_void_p))
+    return out
 
 
 def rust_f64(x: float) -> str:
