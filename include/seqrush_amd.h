@@ -305,18 +305,25 @@ int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, 
  * tgap)); accepted patches are united like any alignment, strand = negated main strand.  Patches are not rescanned.
  * sr_ctx_enable_inversions: after a load, before a run; NULL = off.  Honoured by sr_ctx_run and sr_ctx_align_all(unite = 1)
  * (which then sync once per batch to read the job list).  Refused on PAF and iterative contexts (SR_ERR_UNSUPPORTED) and
- * with a resolved m of 0 (SR_ERR_INVALID).  The patch pass runs on whichever kernel family the penalties select. */
+ * with a resolved m of 0 (SR_ERR_INVALID).  The patch pass runs on whichever kernel family the penalties select.
+ * Joined mode (`--inversion-join J`, join_below = J >= 1; 0 = off, everything above as it is): only match ops of at least J
+ * columns (anchors) open and close gaps; the columns of shorter ones (islands) count towards qgap and tgap like mismatches, so
+ * an inversion whose gap the main alignment split around a few chance matches is one gap again.  Each job carries its site
+ * cost: what the main alignment paid for the gap's ops under the run's penalties (X: len x; an I or D run: min(o1 + len e1,
+ * o2 + len e2); island: 0).  A patch is then accepted when 0 <= patch score < site cost / 2 (in place of main score / 2,
+ * which joined SNP clusters pass), and under the -d bound as above.  J > m is SR_ERR_INVALID; J <= min_match_len is the
+ * sensible range. */
 typedef struct {
     uint64_t min_size;          /* 0 = 2 * min_match_len */
     int32_t keep_alignments;    /* != 0: sr_ctx_inversion_alignments afterwards */
-    uint32_t reserved;
+    uint32_t join_below;        /* J of the joined mode; 0 = off */
 } sr_inv_params;
 typedef struct {
     uint64_t scanned;           /* alignments scanned (failed ones and those dropped by -d are not) */
     uint64_t sites;             /* gaps of any kind (divergent, query-only, target-only) */
     uint64_t candidates;        /* = jobs */
     uint64_t accepted;
-    uint64_t rejected_score;    /* patch score >= main score / 2 */
+    uint64_t rejected_score;    /* patch score >= main score / 2 (joined mode: >= site cost / 2) */
     uint64_t rejected_divergence;   /* passed the score rule, above the -d bound */
     uint64_t united_bases;      /* bases united from accepted patches */
     uint64_t patch_batches;     /* alignment kernel launches of the patch pass (0 without candidates) */
@@ -331,10 +338,16 @@ typedef struct {
     int32_t main_score, patch_score;
     uint8_t is_reverse;         /* the patch's strand: '-' <=> 1 */
     uint8_t accepted;
-    uint8_t reserved[6];
+    uint8_t reserved[2];
+    int32_t site_cost;          /* joined mode: what the main alignment paid for this gap; 0 when off */
 } sr_inv_job;
 int sr_ctx_enable_inversions(sr_ctx *c, const sr_inv_params *p);
 int sr_ctx_inversion_stats(sr_ctx *c, sr_inv_stats *out);
+/* joined mode, last run: [0] islands inside the candidate gaps, [1] jobs rejected by the site-cost rule, [2] host
+ * microseconds of the patch pass on a host clock, from the download of the bases through the segment set and the load of
+ * the segment set (index, packing, uploads, planning, allocation) to just before that load's first kernel; the uploads of
+ * the jobs' starts and bounds after it are outside (any run with jobs, joined or not), [3] reserved */
+int sr_ctx_inversion_join_stats(sr_ctx *c, uint64_t out[4]);
 /* the jobs of the last run in pair order, then CIGAR order; *jobs is malloc'ed (sr_free) */
 int sr_ctx_inversion_jobs(sr_ctx *c, sr_inv_job **jobs, uint64_t *count);
 /* the accepted patches of the last run in job order, start / end filled (forward-strand query coordinates, as PAF wants
@@ -355,10 +368,21 @@ typedef struct {
 int sr_inversion_sites_host(const uint32_t *ops, uint64_t n_ops, uint64_t min_size, sr_inv_site **sites, uint64_t *count);
 int sr_inversion_candidate(uint64_t qgap, uint64_t tgap, uint64_t min_size);    /* 1 / 0; min_size 0: SR_ERR_INVALID */
 int sr_inversion_accept(int32_t patch_score, int32_t main_score);               /* 1 / 0 */
+/* the joined rule: sites with join_below = J (1 <= J <= min_size, else SR_ERR_INVALID) and, in *cost, each site's cost under
+ * the penalties of `pen` (only its score fields are read); both sr_free */
+int sr_inversion_sites_host_join(const uint32_t *ops, uint64_t n_ops, uint64_t min_size, uint32_t join_below, const sr_params *pen,
+                                 sr_inv_site **sites, int32_t **cost, uint64_t *count);
+int sr_inversion_accept_site(int32_t patch_score, int32_t site_cost);           /* 1 / 0 */
 /* tests: the device scan over `n` alignments given like sr_alignments (cigar_off[n + 1], ops in its encoding): the jobs
  * as sites with kind SR_INV_SITE_DIVERGENT, and their alignment index in *owner (both sr_free) */
 int sr_inversion_scan_device(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
                              sr_inv_site **sites, uint64_t **owner, uint64_t *count);
+/* tests: the joined instances of the device scan.  score / max_score: per alignment or NULL (an alignment with score < 0 or
+ * score > max_score is not scanned); *cost: the jobs' site costs (sr_free); stats (or NULL): alignments scanned, sites,
+ * candidates, islands inside candidates */
+int sr_inversion_scan_device_join(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
+                                  uint32_t join_below, const sr_params *pen, const int32_t *score, const int32_t *max_score,
+                                  sr_inv_site **sites, uint64_t **owner, int32_t **cost, uint64_t *count, uint64_t stats[4]);
 
 /* -------- consumer (A9): graph induction + GFA, host C++ -----------------
  * build_bidirected_graph_with_options (bidirected_builder.rs:17-289) +

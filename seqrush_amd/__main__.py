@@ -5,7 +5,7 @@ import os
 import subprocess
 import sys
 
-from .seqrush import Args, run_seqrush, run_seqrush_rank
+from .seqrush import Args, run_seqrush, run_seqrush_rank, check_inversion_join
 from ._lib import SeqRushError
 
 
@@ -36,6 +36,9 @@ def main(argv=None):
     ap.add_argument("--patch-inversions", action="store_true",
                     help="realign large two-sided CIGAR gaps with the query segment reverse-complemented and unite the good ones")
     ap.add_argument("--inversion-min-size", type=int, default=0, help="gap threshold of --patch-inversions (0 = 2 * -k)")
+    ap.add_argument("--inversion-join", type=int, default=0,
+                    help="with --patch-inversions: join gaps across match islands shorter than N and accept a patch against "
+                         "what the main alignment paid for the gap (0 = off; N <= -k is the sensible range)")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -55,6 +58,11 @@ def main(argv=None):
         print("Error: --patch-inversions needs -k or --inversion-min-size (a threshold of 0 would call every complementary "
               "SNP an inversion)", file=sys.stderr)
         return 1
+    try:
+        check_inversion_join(ns)
+    except SeqRushError as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 1
     if ns.gpus > 1 and "RANK" not in os.environ:
         # start one process per GPU BEFORE anything here touches the GPU (never exec from a process that has)
         port = os.environ.get("MASTER_PORT", str(29400 + os.getpid() % 2000))
@@ -70,7 +78,8 @@ def main(argv=None):
                 sort=ns.sort, sort_seed=ns.sort_seed, sgd_iter_max=ns.sgd_iter_max, skip_sgd=ns.skip_sgd,
                 skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
                 aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative,
-                patch_inversions=ns.patch_inversions, inversion_min_size=ns.inversion_min_size)
+                patch_inversions=ns.patch_inversions, inversion_min_size=ns.inversion_min_size,
+                inversion_join=ns.inversion_join)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

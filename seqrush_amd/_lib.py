@@ -33,6 +33,7 @@ EXPORTS = [
     "sr_ctx_enable_inversions", "sr_ctx_inversion_stats", "sr_ctx_inversion_jobs", "sr_ctx_inversion_alignments",
     "sr_append_paf_tagged", "sr_inversion_sites_host", "sr_inversion_candidate", "sr_inversion_accept",
     "sr_inversion_scan_device",
+    "sr_ctx_inversion_join_stats", "sr_inversion_sites_host_join", "sr_inversion_accept_site", "sr_inversion_scan_device_join",
 ]
 
 
@@ -81,7 +82,7 @@ class IterStatsC(C.Structure):
 
 class InvParamsC(C.Structure):
     """sr_inv_params (include/seqrush_amd.h, inversion patching)"""
-    _fields_ = [("min_size", C.c_uint64), ("keep_alignments", C.c_int32), ("reserved", C.c_uint32)]
+    _fields_ = [("min_size", C.c_uint64), ("keep_alignments", C.c_int32), ("join_below", C.c_uint32)]
 
 
 class InvStatsC(C.Structure):
@@ -94,7 +95,7 @@ class InvJobC(C.Structure):
     _fields_ = [("pair", C.c_uint64), ("query_idx", C.c_uint32), ("target_idx", C.c_uint32),
                 ("query_start", C.c_uint64), ("query_end", C.c_uint64), ("target_start", C.c_uint64),
                 ("target_end", C.c_uint64), ("main_score", C.c_int32), ("patch_score", C.c_int32),
-                ("is_reverse", C.c_uint8), ("accepted", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+                ("is_reverse", C.c_uint8), ("accepted", C.c_uint8), ("reserved", C.c_uint8 * 2), ("site_cost", C.c_int32)]
 
 
 class InvSiteC(C.Structure):
@@ -213,6 +214,14 @@ def load():
     L.sr_inversion_accept.argtypes = [C.c_int32, C.c_int32]
     L.sr_inversion_scan_device.argtypes = [i32, C.POINTER(C.c_uint32), C.POINTER(u64), u64, u64,
                                            C.POINTER(C.POINTER(InvSiteC)), C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
+    PI32 = C.POINTER(C.c_int32)
+    L.sr_ctx_inversion_join_stats.argtypes = [vp, C.POINTER(u64)]
+    L.sr_inversion_sites_host_join.argtypes = [C.POINTER(C.c_uint32), u64, u64, C.c_uint32, PP, C.POINTER(C.POINTER(InvSiteC)),
+                                               C.POINTER(PI32), C.POINTER(u64)]
+    L.sr_inversion_accept_site.argtypes = [C.c_int32, C.c_int32]
+    L.sr_inversion_scan_device_join.argtypes = [i32, C.POINTER(C.c_uint32), C.POINTER(u64), u64, u64, C.c_uint32, PP, PI32, PI32,
+                                                C.POINTER(C.POINTER(InvSiteC)), C.POINTER(C.POINTER(u64)), C.POINTER(PI32),
+                                                C.POINTER(u64), C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

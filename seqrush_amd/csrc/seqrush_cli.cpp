@@ -78,7 +78,7 @@ static void usage() {
     fprintf(stderr, "usage: seqrush_mi355x -s in.fa [-o output.gfa] [-k 0] [-S 0,5,8,2,24,1] [--orientation-scores 0,1,1,1]\n"
                     "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--device N]\n"
                     "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
-                    "       [--patch-inversions [--inversion-min-size N]]\n"
+                    "       [--patch-inversions [--inversion-min-size N] [--inversion-join N]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
@@ -89,7 +89,8 @@ int main(int argc, char **argv) {
     double max_div = -1.0;
     int device = 0;
     bool no_sort = false, no_compact = false, sort = false, iterative = false, verbose = false, patch_inv = false;
-    unsigned long long inv_min = 0;
+    unsigned long long inv_min = 0, inv_join = 0;
+    bool inv_join_given = false;
     sr_sort_params sp;
     sr_sort_params_default(&sp);
     // multi-GPU without a collective library in this host: every process aligns one shard (--shard R/N) and writes its
@@ -136,6 +137,13 @@ int main(int argc, char **argv) {
             inv_min = strtoull(v, &end, 10);
             if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: --inversion-min-size needs a non-negative integer, got '%s'\n", v); return 1; }
         }
+        else if (a == "--inversion-join") {
+            const char *v = val("--inversion-join");
+            char *end = nullptr;
+            inv_join = strtoull(v, &end, 10);
+            if (*v < '0' || *v > '9' || *end != 0 || inv_join > 0xffffffffULL) { fprintf(stderr, "Error: --inversion-join needs a non-negative integer, got '%s'\n", v); return 1; }
+            inv_join_given = inv_join != 0;
+        }
         else { usage(); return 2; }
     }
     if (sequences.empty()) { usage(); return 2; }
@@ -152,6 +160,15 @@ int main(int argc, char **argv) {
     }
     if (patch_inv && (inv_min ? inv_min : 2ULL * (unsigned long long)(k > 0 ? k : 0)) == 0) {
         fprintf(stderr, "Error: --patch-inversions needs -k or --inversion-min-size (a threshold of 0 would call every complementary SNP an inversion)\n");
+        return 1;
+    }
+    if (inv_join_given && !patch_inv) {
+        fprintf(stderr, "Error: --inversion-join is an option of --patch-inversions: give both\n");
+        return 1;
+    }
+    if (inv_join_given && inv_join > (inv_min ? inv_min : 2ULL * (unsigned long long)(k > 0 ? k : 0))) {
+        fprintf(stderr, "Error: --inversion-join %llu is above the gap threshold of --patch-inversions (%llu): an island would be a candidate by itself\n",
+                inv_join, inv_min ? inv_min : 2ULL * (unsigned long long)(k > 0 ? k : 0));
         return 1;
     }
     if (shard_count > 1 && labels_out.empty()) {
@@ -256,7 +273,7 @@ int main(int argc, char **argv) {
     } else {
         if (sr_ctx_load(ctx, &set, &p)) return die();
         if (patch_inv) {
-            sr_inv_params ip{inv_min, paf_out.empty() ? 0 : 1, 0};
+            sr_inv_params ip{inv_min, paf_out.empty() ? 0 : 1, (uint32_t)inv_join};
             if (sr_ctx_enable_inversions(ctx, &ip)) return die();
         }
     }
@@ -281,6 +298,12 @@ int main(int argc, char **argv) {
         sr_inv_stats ist;
         if (sr_ctx_inversion_stats(ctx, &ist)) return die();
         printf("Patched inversions: %llu of %llu candidate gaps\n", (unsigned long long)ist.accepted, (unsigned long long)ist.candidates);
+        if (verbose && inv_join) {
+            uint64_t js[4];
+            if (sr_ctx_inversion_join_stats(ctx, js)) return die();
+            printf("Inversion join: %llu match islands absorbed into candidate gaps, %llu jobs rejected by site cost\n",
+                   (unsigned long long)js[0], (unsigned long long)js[1]);
+        }
     }
     if (!labels_out.empty()) {                               // shard run: the forest's canonical labels, no graph
         const uint64_t ufn = sr_ctx_uf_size(ctx);

@@ -292,6 +292,13 @@ struct sr_ctx {
     sr_inv_stats inv_stats{};
     sr_alignments *inv_al = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> inv_ev;      // one event pair per scanned batch
+    // joined mode (--inversion-join): J, its 24-byte records and sr_ctx_inversion_join_stats
+    uint32_t inv_join = 0;
+    SrInvJobJ *d_inv_jobs_j = nullptr;
+    uint64_t inv_job_cap_j = 0;
+    std::vector<SrInvJobJ> inv_raw_j;
+    uint64_t inv_join_stats[4] = {0, 0, 0, 0};
+    std::chrono::steady_clock::time_point t_first_kernel;      // host clock just before a load's first kernel (inv_patch_pass)
     int inv_ev_used = 0;
 };
 
@@ -319,6 +326,8 @@ static void free_dev(sr_ctx *c) {
     if (c->iter_al) { sr_alignments_free(c->iter_al); c->iter_al = nullptr; }
     c->inv_on = c->inv_keep = false; c->inv_m = 0; c->d_inv_count = c->d_inv_off = nullptr; c->d_inv_stats = nullptr;
     c->d_inv_jobs = nullptr; c->inv_job_cap = 0; c->inv_raw.clear(); c->inv_jobs.clear(); c->inv_stats = sr_inv_stats{};
+    c->inv_join = 0; c->d_inv_jobs_j = nullptr; c->inv_job_cap_j = 0; c->inv_raw_j.clear();
+    for (uint64_t &v : c->inv_join_stats) v = 0;
     c->inv_ev_used = 0;
     if (c->inv_al) { sr_alignments_free(c->inv_al); c->inv_al = nullptr; }
 }
@@ -1129,6 +1138,7 @@ static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const
     if ((r = plan_memory(c, np, pl, iterative))) return r;
     if ((r = alloc_workspace(c, p, pk, sd, pen, ori, maxlen, max_score, pl, forced_strand))) return r;
     write_report(c, pk, pen, pl);
+    c->t_first_kernel = std::chrono::steady_clock::now();
     if (srk_uf_init(c->d_nodes, c->total_len, c->uf_size, c->stream)) return fail(SR_ERR_HIP, "uf init launch failed");
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loaded = true;
@@ -1793,6 +1803,64 @@ extern "C" int sr_inversion_sites_host(const uint32_t *ops, uint64_t n_ops, uint
     return SR_OK;
 }
 
+static int inv_pen_of(const sr_params *p, SrInvPen *out) {
+    if (!p) return fail(SR_ERR_INVALID, "null argument");
+    SrPen pen;
+    const int r = make_pen(*p, false, &pen);
+    if (r) return r;
+    *out = SrInvPen{pen.x, pen.o1, pen.e1, pen.o2, pen.e2, pen.two};
+    return SR_OK;
+}
+
+extern "C" int sr_inversion_accept_site(int32_t patch_score, int32_t site_cost) { return sr_inv_accept_site(patch_score, site_cost); }
+
+// the joined rule (sr_inv_rule.h) over run-length ops in the sr_alignments encoding; cost[i] = site cost of sites[i]
+extern "C" int sr_inversion_sites_host_join(const uint32_t *ops, uint64_t n_ops, uint64_t min_size, uint32_t join_below, const sr_params *pen,
+                                            sr_inv_site **sites, int32_t **cost, uint64_t *count) {
+    if ((!ops && n_ops) || !sites || !cost || !count) return fail(SR_ERR_INVALID, "null argument");
+    if (min_size == 0) return fail(SR_ERR_INVALID, "inversion threshold 0: every complementary SNP would be an inversion (give -k or a minimum size)");
+    if (join_below == 0) return fail(SR_ERR_INVALID, "inversion join length 0: the joined rule needs J >= 1");
+    if (join_below > min_size) return fail(SR_ERR_INVALID, "inversion join length above the gap threshold: an island would be a candidate by itself");
+    SrInvPen ip;
+    int r;
+    if ((r = inv_pen_of(pen, &ip))) return r;
+    std::vector<sr_inv_site> out;
+    std::vector<int32_t> oc;
+    uint64_t q = 0, t = 0, qa = 0, ta = 0, qg = 0, tg = 0, sc = 0;
+    bool open = false;
+    auto close = [&]() {
+        const int kind = sr_inv_site_kind(qg, tg, min_size);
+        if (kind == SR_INV_NONE) return;
+        sr_inv_site s;
+        s.query_start = qa; s.target_start = ta;
+        s.query_end = qa + (kind == SR_INV_TARGET_ONLY ? 0 : qg);
+        s.target_end = ta + (kind == SR_INV_QUERY_ONLY ? 0 : tg);
+        s.kind = kind; s.candidate = sr_inv_is_candidate(qg, tg, min_size);
+        out.push_back(s); oc.push_back((int32_t)(uint32_t)sc);
+    };
+    for (uint64_t i = 0; i < n_ops; i++) {
+        const uint32_t op = ops[i] & 3u, len = ops[i] >> 4;
+        if (sr_inv_is_anchor(op, len, join_below)) {
+            if (open) close();
+            q += len; t += len;
+            open = true; qa = q; ta = t; qg = tg = sc = 0;
+            continue;
+        }
+        if (op == 0 || op == 1) { q += len; t += len; qg += len; tg += len; }
+        else if (op == 2) { q += len; qg += len; }
+        else { t += len; tg += len; }
+        sc += sr_inv_op_cost(op, len, ip);
+    }
+    if (open) close();
+    *count = out.size();
+    *sites = (sr_inv_site *)malloc((out.empty() ? 1 : out.size()) * sizeof(sr_inv_site));
+    *cost = (int32_t *)malloc((out.empty() ? 1 : out.size()) * sizeof(int32_t));
+    if (!*sites || !*cost) return fail(SR_ERR_NOMEM, "out of memory");
+    memcpy(*sites, out.data(), out.size() * sizeof(sr_inv_site));
+    memcpy(*cost, oc.data(), oc.size() * sizeof(int32_t));
+    return SR_OK;
+}
+
 extern "C" int sr_ctx_enable_inversions(sr_ctx *c, const sr_inv_params *p) {
     if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");
     if (!p) { c->inv_on = false; return SR_OK; }
@@ -1800,6 +1868,7 @@ extern "C" int sr_ctx_enable_inversions(sr_ctx *c, const sr_inv_params *p) {
     if (c->iter_loaded) return fail(SR_ERR_UNSUPPORTED, "inversion patching cannot be combined with the iterative mode");
     const uint64_t m = inv_resolve_threshold(p->min_size, c->prm.min_match_len);
     if (m == 0) return fail(SR_ERR_INVALID, "inversion threshold 0: every complementary SNP would be an inversion (give -k or a minimum size)");
+    if (p->join_below > m) return fail(SR_ERR_INVALID, "inversion join length above the gap threshold: an island would be a candidate by itself");
     HIPCHK(hipSetDevice(c->device));
     if (!c->d_inv_count) {
         uint32_t maxb = 1;
@@ -1810,12 +1879,14 @@ extern "C" int sr_ctx_enable_inversions(sr_ctx *c, const sr_inv_params *p) {
         if ((r = dev_alloc(c, &d, ((size_t)maxb + 1) * 4))) return r; c->d_inv_off = (uint32_t *)d;
         if ((r = dev_alloc(c, &d, 4 * sizeof(unsigned long long)))) return r; c->d_inv_stats = (unsigned long long *)d;
     }
-    c->inv_m = m; c->inv_keep = p->keep_alignments != 0; c->inv_on = true;
+    c->inv_m = m; c->inv_keep = p->keep_alignments != 0; c->inv_on = true; c->inv_join = p->join_below;
     return SR_OK;
 }
 
 static int inv_begin_run(sr_ctx *c) {
     c->inv_raw.clear(); c->inv_jobs.clear(); c->inv_stats = sr_inv_stats{}; c->inv_ev_used = 0;
+    c->inv_raw_j.clear();
+    for (uint64_t &v : c->inv_join_stats) v = 0;
     if (c->inv_al) { sr_alignments_free(c->inv_al); c->inv_al = nullptr; }
     HIPCHK(hipMemsetAsync(c->d_inv_stats, 0, 4 * sizeof(unsigned long long), c->stream));
     return SR_OK;
@@ -1823,8 +1894,12 @@ static int inv_begin_run(sr_ctx *c) {
 
 // count, offsets, (host reads the total,) emit, (host reads the records) for one batch whose CIGARs are in the arena
 // ev: two event pairs (or NULL): [0] around count + offsets, [1] around emit -- kernels only, not the host round trips
-static int inv_scan_launch(hipStream_t stream, SrInvScanArgs &s, uint32_t *d_off, std::vector<void *> *allocs, SrInvJob **d_jobs,
-                           uint64_t *job_cap, std::vector<SrInvJob> &out, std::pair<hipEvent_t, hipEvent_t> *ev = nullptr,
+// J: SrInvJob (plain instances) or SrInvJobJ (joined instances, s.join_below >= 1)
+static void inv_set_jobs(SrInvScanArgs &s, SrInvJob *j) { s.jobs = j; }
+static void inv_set_jobs(SrInvScanArgs &s, SrInvJobJ *j) { s.jobs_j = j; }
+template <class J>
+static int inv_scan_launch(hipStream_t stream, SrInvScanArgs &s, uint32_t *d_off, std::vector<void *> *allocs, J **d_jobs,
+                           uint64_t *job_cap, std::vector<J> &out, std::pair<hipEvent_t, hipEvent_t> *ev = nullptr,
                            int *ev_used = nullptr) {
     if (s.npairs == 0) return SR_OK;
     if (ev) HIPCHK(hipEventRecord(ev[0].first, stream));
@@ -1837,22 +1912,22 @@ static int inv_scan_launch(hipStream_t stream, SrInvScanArgs &s, uint32_t *d_off
     if (total > *job_cap) {
         const uint64_t cap = std::max<uint64_t>(total, 2 * *job_cap);
         void *d = nullptr;
-        if (hipMalloc(&d, cap * sizeof(SrInvJob)) != hipSuccess) return fail(SR_ERR_NOMEM, "not enough device memory for the inversion job list");
+        if (hipMalloc(&d, cap * sizeof(J)) != hipSuccess) return fail(SR_ERR_NOMEM, "not enough device memory for the inversion job list");
         if (*d_jobs) {                                     // (the stream is idle: the smaller buffer's records were copied out)
             auto it = std::find(allocs->begin(), allocs->end(), (void *)*d_jobs);
             if (it != allocs->end()) allocs->erase(it);
             (void)hipFree(*d_jobs);
         }
         allocs->push_back(d);
-        *d_jobs = (SrInvJob *)d; *job_cap = cap;
+        *d_jobs = (J *)d; *job_cap = cap;
     }
-    s.offset = d_off; s.jobs = *d_jobs; s.job_cap = *job_cap;
+    s.offset = d_off; inv_set_jobs(s, *d_jobs); s.job_cap = *job_cap;
     if (ev) HIPCHK(hipEventRecord(ev[1].first, stream));
     if (srk_inv_scan(&s, 1, stream)) return fail(SR_ERR_HIP, "inversion scan kernel launch failed");
     if (ev) { HIPCHK(hipEventRecord(ev[1].second, stream)); *ev_used = 2; }
     const size_t at = out.size();
     out.resize(at + total);
-    HIPCHK(hipMemcpyAsync(out.data() + at, *d_jobs, (size_t)total * sizeof(SrInvJob), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out.data() + at, *d_jobs, (size_t)total * sizeof(J), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     return SR_OK;
 }
@@ -1868,15 +1943,28 @@ static int inv_scan_batch(sr_ctx *c, uint32_t b) {
     SrInvScanArgs s{};
     s.cigar_ops = u.cigar_ops; s.cigar_base = u.cigar_base; s.cigar_cnt = u.cigar_cnt; s.score = u.score; s.max_score = u.max_score;
     s.npairs = u.npairs; s.pair0 = c->batch_first[b]; s.min_size = c->inv_m; s.count = c->d_inv_count; s.stats = c->d_inv_stats;
-    int used = 0;
-    const int r = inv_scan_launch(c->stream, s, c->d_inv_off, &c->dev_allocs, &c->d_inv_jobs, &c->inv_job_cap, c->inv_raw,
-                                  c->inv_ev.data() + c->inv_ev_used, &used);
+    int used = 0, r;
+    if (c->inv_join) {
+        s.join_below = c->inv_join;
+        const SrPen &pn = c->aa.pen;
+        const int32_t pv[6] = {pn.x, pn.o1, pn.e1, pn.o2, pn.e2, pn.two};
+        memcpy(s.pen, pv, sizeof(pv));
+        r = inv_scan_launch(c->stream, s, c->d_inv_off, &c->dev_allocs, &c->d_inv_jobs_j, &c->inv_job_cap_j, c->inv_raw_j,
+                            c->inv_ev.data() + c->inv_ev_used, &used);
+    } else
+        r = inv_scan_launch(c->stream, s, c->d_inv_off, &c->dev_allocs, &c->d_inv_jobs, &c->inv_job_cap, c->inv_raw,
+                            c->inv_ev.data() + c->inv_ev_used, &used);
     if (r) return r;
     c->inv_ev_used += used;
     return SR_OK;
 }
 
-static int inv_patch_pass(sr_ctx *c) {
+static inline int32_t inv_job_cost(const SrInvJob &) { return 0; }            // the plain record carries no cost
+static inline int32_t inv_job_cost(const SrInvJobJ &w) { return w.cost; }
+
+// J: the record type of the run's scan instances; raw: the run's records
+template <class J>
+static int inv_patch_pass_of(sr_ctx *c, const std::vector<J> &raw) {
     int r;
     if ((r = sr_ctx_sync(c))) return r;
     sr_inv_stats &st = c->inv_stats;
@@ -1889,7 +1977,9 @@ static int inv_patch_pass(sr_ctx *c) {
         HIPCHK(hipEventElapsedTime(&t, c->inv_ev[i].first, c->inv_ev[i].second));
         st.scan_ms += t;
     }
-    const size_t nj = c->inv_raw.size();
+    const bool join = c->inv_join != 0;
+    if (join) c->inv_join_stats[0] = ds[3];
+    const size_t nj = raw.size();
     if ((uint64_t)nj != st.candidates) return fail(SR_ERR_DEVICE_FAULT, "inversion scan: the emitted job records do not match the counted candidates");
     if (nj == 0) return SR_OK;                             // nothing to patch: no launch, the forest is the plain run's
     if (nj > 0x7ffffff0ULL) return fail(SR_ERR_UNSUPPORTED, "more than 2^31 inversion candidates");
@@ -1898,6 +1988,9 @@ static int inv_patch_pass(sr_ctx *c) {
     std::vector<uint8_t> isrev(np), bases(c->total_len);
     HIPCHK(hipMemcpy(score.data(), c->aa.score, np * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(isrev.data(), c->aa.is_reverse, np, hipMemcpyDeviceToHost));
+    // host clock (sr_ctx_inversion_join_stats[2]): from here -- the download of the bases, the segment set, the inner load's
+    // index, packing, uploads, planning and allocation -- to just before the inner load's first kernel (its union-find init)
+    const auto host_t0 = std::chrono::steady_clock::now();
     HIPCHK(hipMemcpy(bases.data(), c->d_bases, c->total_len, hipMemcpyDeviceToHost));
     // segment set: 2 j = the pattern (the query's forward segment, reverse-complemented for a '-' patch -- the same bytes as
     // the reverse complement of the ALIGNED query's gap), 2 j + 1 = the target's segment; patch strand = negated main strand
@@ -1907,8 +2000,15 @@ static int inv_patch_pass(sr_ctx *c) {
     std::vector<uint8_t> strand(nj);
     std::vector<int32_t> bound(nj);
     c->inv_jobs.assign(nj, sr_inv_job{});
+    {
+        uint64_t seg_bytes = 0;
+        for (const J &w : raw) seg_bytes += (uint64_t)w.qgap + w.tgap;
+        seg.reserve(seg_bytes);
+        soff.reserve(2 * nj + 1);
+    }
     for (size_t j = 0; j < nj; j++) {
-        const SrInvJob &w = c->inv_raw[j];
+        const J &w = raw[j];
+        const int32_t cost = inv_job_cost(w);
         if (w.pair >= np) return fail(SR_ERR_DEVICE_FAULT, "inversion scan: job record with a pair index out of range");
         const uint32_t q = c->pair_q[w.pair], t = c->pair_t[w.pair];
         const uint64_t lq = c->len[q], lt = c->len[t];
@@ -1917,7 +2017,13 @@ static int inv_patch_pass(sr_ctx *c) {
         const bool main_rev = isrev[w.pair] != 0;
         const uint64_t fq = main_rev ? lq - w.qa - w.qgap : w.qa;
         if (main_rev) seg.insert(seg.end(), bases.begin() + (c->goff[q] + fq), bases.begin() + (c->goff[q] + fq + w.qgap));
-        else for (uint64_t k = 0; k < w.qgap; k++) seg.push_back(comp_base(bases[c->goff[q] + fq + w.qgap - 1 - k]));
+        else {                                             // reverse complement, written in place
+            const size_t at = seg.size();
+            seg.resize(at + w.qgap);
+            const uint8_t *src = bases.data() + c->goff[q] + fq + w.qgap - 1;
+            uint8_t *dst = seg.data() + at;
+            for (uint32_t k = 0; k < w.qgap; k++) dst[k] = comp_base(src[-(ptrdiff_t)k]);
+        }
         soff.push_back(seg.size());
         seg.insert(seg.end(), bases.begin() + (c->goff[t] + w.ta), bases.begin() + (c->goff[t] + w.ta + w.tgap));
         soff.push_back(seg.size());
@@ -1925,14 +2031,16 @@ static int inv_patch_pass(sr_ctx *c) {
         strand[j] = main_rev ? 0 : 1;
         qs[j] = (uint32_t)(lq - w.qa - w.qgap);            // first query position in the patch's own space (sr_inv_rule.h)
         ts[j] = w.ta;
-        int32_t bd = sr_inv_score_bound(score[w.pair]);
+        if (join && (cost < 0 || cost > score[w.pair]))
+            return fail(SR_ERR_DEVICE_FAULT, "inversion scan: a site cost outside [0, main score]");
+        int32_t bd = join ? sr_inv_site_bound(cost) : sr_inv_score_bound(score[w.pair]);
         if (c->prm.max_divergence >= 0.0)
             bd = std::min(bd, max_score_for_divergence(c->prm, std::min<uint64_t>(w.qgap, w.tgap), c->prm.max_divergence));
         bound[j] = bd;
         sr_inv_job &o = c->inv_jobs[j];
         o.pair = w.pair; o.query_idx = q; o.target_idx = t; o.query_start = fq; o.query_end = fq + w.qgap;
         o.target_start = w.ta; o.target_end = (uint64_t)w.ta + w.tgap; o.main_score = score[w.pair]; o.patch_score = -1;
-        o.is_reverse = strand[j]; o.accepted = 0;
+        o.is_reverse = strand[j]; o.accepted = 0; o.site_cost = join ? cost : 0;
     }
     sr_seqset ss{(uint32_t)(2 * nj), seg.data(), soff.data(), nullptr};
     sr_params pp = c->prm;
@@ -1941,6 +2049,7 @@ static int inv_patch_pass(sr_ctx *c) {
     in->device = c->device; in->stream = c->stream; in->own_stream = false;
     struct Guard { sr_ctx *p; ~Guard() { std::string keep = g_err; sr_ctx_destroy(p); g_err = keep; } } guard{in};
     if ((r = load_impl(in, &ss, &pp, eq.data(), et.data(), nj, true, false, true))) return r;      // forced_strand
+    c->inv_join_stats[2] = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(in->t_first_kernel - host_t0).count();
     uint32_t *d_opq, *d_opt, *d_qs, *d_ts; int32_t *d_bound; uint8_t *d_strand;
     void *d;
 #define INV_UP(dst, T, v)                                                                     \
@@ -1979,7 +2088,10 @@ static int inv_patch_pass(sr_ctx *c) {
     for (size_t j = 0; j < nj; j++) {
         sr_inv_job &o = c->inv_jobs[j];
         o.patch_score = ps[j];
-        if (!sr_inv_accept_score(ps[j], o.main_score)) st.rejected_score++;
+        if (join ? !sr_inv_accept_site(ps[j], o.site_cost) : !sr_inv_accept_score(ps[j], o.main_score)) {
+            st.rejected_score++;
+            if (join) c->inv_join_stats[1]++;
+        }
         else if (ps[j] > bound[j]) st.rejected_divergence++;
         else { o.accepted = 1; st.accepted++; }
     }
@@ -2009,9 +2121,19 @@ static int inv_patch_pass(sr_ctx *c) {
     return SR_OK;
 }
 
+static int inv_patch_pass(sr_ctx *c) {
+    return c->inv_join ? inv_patch_pass_of(c, c->inv_raw_j) : inv_patch_pass_of(c, c->inv_raw);
+}
+
 extern "C" int sr_ctx_inversion_stats(sr_ctx *c, sr_inv_stats *out) {
     if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
     *out = c->inv_stats;
+    return SR_OK;
+}
+
+extern "C" int sr_ctx_inversion_join_stats(sr_ctx *c, uint64_t out[4]) {
+    if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
+    memcpy(out, c->inv_join_stats, sizeof(c->inv_join_stats));
     return SR_OK;
 }
 
@@ -2034,9 +2156,11 @@ extern "C" int sr_ctx_inversion_alignments(sr_ctx *c, sr_alignments **out) {
 }
 
 // tests: the scan kernels over alignments given on the host
-extern "C" int sr_inversion_scan_device(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
-                                        sr_inv_site **sites, uint64_t **owner, uint64_t *count) {
-    if (!cigar_off || !sites || !owner || !count || (!ops && n && cigar_off[n])) return fail(SR_ERR_INVALID, "null argument");
+template <class J>
+static int inv_scan_device_impl(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
+                                uint32_t join_below, const SrInvPen *pen, const int32_t *score, const int32_t *max_score,
+                                std::vector<J> &jobs, uint64_t stats_out[4]) {
+    if (!cigar_off || (!ops && n && cigar_off[n])) return fail(SR_ERR_INVALID, "null argument");
     if (min_size == 0) return fail(SR_ERR_INVALID, "inversion threshold 0");
     if (n == 0 || n > 0x7fffffffULL) return fail(SR_ERR_INVALID, "bad alignment count");
     int ndev = 0;
@@ -2071,11 +2195,27 @@ extern "C" int sr_inversion_scan_device(int device, const uint32_t *ops, const u
     if (!s.cigar_ops || !s.cigar_base || !s.cigar_cnt || !s.count || !d_off || !s.stats) return fail(SR_ERR_NOMEM, "device allocation failed");
     HIPCHK(hipMemset(s.stats, 0, 32));
     s.npairs = (uint32_t)n; s.pair0 = 0; s.min_size = min_size;
-    std::vector<SrInvJob> jobs;
-    SrInvJob *d_jobs = nullptr;
+    if (score && !(s.score = (const int32_t *)up(score, n * 4))) return fail(SR_ERR_NOMEM, "device allocation failed");
+    if (max_score && !(s.max_score = (const int32_t *)up(max_score, n * 4))) return fail(SR_ERR_NOMEM, "device allocation failed");
+    if (pen) {
+        s.join_below = join_below;
+        const int32_t pv[6] = {pen->x, pen->o1, pen->e1, pen->o2, pen->e2, pen->two};
+        memcpy(s.pen, pv, sizeof(pv));
+    }
+    J *d_jobs = nullptr;
     uint64_t cap = 0;
     const int r = inv_scan_launch(nullptr, s, d_off, &tmp.v, &d_jobs, &cap, jobs);
     if (r) return r;
+    if (stats_out) {
+        unsigned long long ds[4];
+        HIPCHK(hipMemcpy(ds, s.stats, sizeof(ds), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 4; i++) stats_out[i] = ds[i];
+    }
+    return SR_OK;
+}
+
+template <class J>
+static int inv_sites_of_jobs(const std::vector<J> &jobs, sr_inv_site **sites, uint64_t **owner, uint64_t *count) {
     *count = jobs.size();
     *sites = (sr_inv_site *)malloc((jobs.empty() ? 1 : jobs.size()) * sizeof(sr_inv_site));
     *owner = (uint64_t *)malloc((jobs.empty() ? 1 : jobs.size()) * 8);
@@ -2087,6 +2227,32 @@ extern "C" int sr_inversion_scan_device(int device, const uint32_t *ops, const u
         o.kind = SR_INV_DIVERGENT; o.candidate = 1;
         (*owner)[j] = jobs[j].pair;
     }
+    return SR_OK;
+}
+
+extern "C" int sr_inversion_scan_device(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
+                                        sr_inv_site **sites, uint64_t **owner, uint64_t *count) {
+    if (!sites || !owner || !count) return fail(SR_ERR_INVALID, "null argument");
+    std::vector<SrInvJob> jobs;
+    const int r = inv_scan_device_impl(device, ops, cigar_off, n, min_size, 0, nullptr, nullptr, nullptr, jobs, nullptr);
+    return r ? r : inv_sites_of_jobs(jobs, sites, owner, count);
+}
+
+extern "C" int sr_inversion_scan_device_join(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
+                                             uint32_t join_below, const sr_params *pen, const int32_t *score, const int32_t *max_score,
+                                             sr_inv_site **sites, uint64_t **owner, int32_t **cost, uint64_t *count, uint64_t stats[4]) {
+    if (!sites || !owner || !cost || !count) return fail(SR_ERR_INVALID, "null argument");
+    if (join_below == 0) return fail(SR_ERR_INVALID, "inversion join length 0: the joined rule needs J >= 1");
+    if (join_below > min_size) return fail(SR_ERR_INVALID, "inversion join length above the gap threshold: an island would be a candidate by itself");
+    SrInvPen ip;
+    int r;
+    if ((r = inv_pen_of(pen, &ip))) return r;
+    std::vector<SrInvJobJ> jobs;
+    if ((r = inv_scan_device_impl(device, ops, cigar_off, n, min_size, join_below, &ip, score, max_score, jobs, stats))) return r;
+    if ((r = inv_sites_of_jobs(jobs, sites, owner, count))) return r;
+    *cost = (int32_t *)malloc((jobs.empty() ? 1 : jobs.size()) * sizeof(int32_t));
+    if (!*cost) return fail(SR_ERR_NOMEM, "out of memory");
+    for (size_t j = 0; j < jobs.size(); j++) (*cost)[j] = jobs[j].cost;
     return SR_OK;
 }
 

@@ -138,6 +138,7 @@ struct SrUniteArgs {
 
 // sr_inv.hip: CIGAR scan of --patch-inversions over one batch (sr_inv_rule.h)
 struct SrInvJob;
+struct SrInvJobJ;
 struct SrInvScanArgs {
     const uint32_t *cigar_ops;
     const uint64_t *cigar_base;     // [npairs] relative to cigar_ops
@@ -152,6 +153,11 @@ struct SrInvScanArgs {
     struct SrInvJob *jobs;          // pass 1 out
     uint64_t job_cap;               // records `jobs` holds
     unsigned long long *stats;      // pass 0: [0] alignments scanned, [1] sites of any kind, [2] candidates
+                                    // [3] joined instance: islands inside candidates
+    // joined instance (--inversion-join): selected by join_below >= 1
+    uint32_t join_below;            // J: match ops shorter than this are islands; 0 = the plain instances
+    struct SrInvJobJ *jobs_j;       // pass 1 out in place of `jobs`
+    int32_t pen[6];                 // the run's penalties for the site cost: x, o1, e1, o2, e2, two (SrInvPen)
 };
 
 #ifdef __cplusplus

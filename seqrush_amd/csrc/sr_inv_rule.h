@@ -19,6 +19,18 @@
 //              len_q - qa - qgap on '-' patches and the forward start on '+' patches -- the same number.
 //   accept     0 <= inv_score < main_score / 2, integer halving (:191); with -d also inv_score <= max_score_for_divergence(
 //              min(qgap, tgap), d) (:304-309).  Both fold into one per-job upper bound for the unite kernel's score filter.
+// Joined mode (--inversion-join J, J >= 1; own rule, not the reference's): rc(s) against s nearly always matches a few bases
+// near the centre, and that island is a match op that splits a real inversion's gap into two one-sided sites.  So:
+//   anchor     a match op with len >= J.  Only anchors open and close sites; "match op" above reads "anchor".
+//   island     a match op with len < J.  Its columns count towards qgap AND tgap, like X columns.
+//   site cost  what the main alignment paid for the site's ops under the run's penalties: X len x; an I or D run
+//              min(o1 + len e1, o2 + len e2) (single-piece: o1 + len e1); island 0.  The CIGAR is run-length, so every gap
+//              run is one op and the sum over a whole CIGAR is the alignment's score; a site's cost is at most that.
+//   accept     0 <= inv_score < site_cost / 2, integer halving, in place of the main-score test: joined SNP clusters pass
+//              main / 2 (the whole alignment's score is large next to any one cluster) and fail against what the
+//              alignment paid for that very gap.  The -d bound is as above.
+//   J = 1      every match op is an anchor: the plain rule's sites, the joined accept test.  J > m is refused: an island of
+//              m columns would be a candidate by itself.
 #pragma once
 #include <stdint.h>
 
@@ -32,6 +44,12 @@ enum { SR_INV_NONE = 0, SR_INV_DIVERGENT = 1, SR_INV_QUERY_ONLY = 2, SR_INV_TARG
 
 // one job of the patch pass, as the scan emits it (20 bytes): pair index in the context's list, alignment coordinates
 struct SrInvJob { uint32_t pair, qa, qgap, ta, tgap; };
+
+// the joined scan's record (24 bytes): the same, and what the main alignment paid for the site
+struct SrInvJobJ { uint32_t pair, qa, qgap, ta, tgap; int32_t cost; };
+
+// penalties as the joined scan needs them (SrPen's fields; two = 0: single-piece)
+struct SrInvPen { int32_t x, o1, e1, o2, e2, two; };
 
 SR_INV_HD inline int sr_inv_site_kind(unsigned long long qgap, unsigned long long tgap, unsigned long long m) {
     if (qgap >= m && tgap >= m) return SR_INV_DIVERGENT;
@@ -51,4 +69,24 @@ SR_INV_HD inline int32_t sr_inv_score_bound(int32_t main_score) { return main_sc
 
 SR_INV_HD inline int sr_inv_accept_score(int32_t inv_score, int32_t main_score) {
     return inv_score >= 0 && inv_score <= sr_inv_score_bound(main_score) ? 1 : 0;
+}
+
+// ---- joined mode
+// op: 0 match, 1 mismatch, anything else a gap run (either side); join_below = J.  An island costs 0.
+SR_INV_HD inline int sr_inv_is_anchor(uint32_t op, uint32_t len, uint32_t join_below) { return op == 0 && len >= join_below ? 1 : 0; }
+
+SR_INV_HD inline uint32_t sr_inv_op_cost(uint32_t op, uint32_t len, const SrInvPen &p) {
+    if (op == 0) return 0;
+    if (op == 1) return len * (uint32_t)p.x;
+    const uint32_t c1 = (uint32_t)p.o1 + len * (uint32_t)p.e1;
+    if (!p.two) return c1;
+    const uint32_t c2 = (uint32_t)p.o2 + len * (uint32_t)p.e2;
+    return c1 < c2 ? c1 : c2;
+}
+
+// largest patch score the site-cost rule accepts (< 0: none)
+SR_INV_HD inline int32_t sr_inv_site_bound(int32_t site_cost) { return site_cost < 0 ? -1 : site_cost / 2 - 1; }
+
+SR_INV_HD inline int sr_inv_accept_site(int32_t inv_score, int32_t site_cost) {
+    return inv_score >= 0 && inv_score <= sr_inv_site_bound(site_cost) ? 1 : 0;
 }

@@ -50,6 +50,7 @@ class Args:
     iterative: bool = False                 # --iterative: tree pairs, then random pairs until the components are stable
     patch_inversions: bool = False          # added: --patch-inversions, realign large two-sided CIGAR gaps on the other strand
     inversion_min_size: int = 0             # added: --inversion-min-size N (0 = 2 * min_match_length)
+    inversion_join: int = 0                 # added: --inversion-join J: join gaps across match islands shorter than J (0 = off)
 
 
 @dataclasses.dataclass
@@ -326,12 +327,15 @@ class Context:
         check(self.L.sr_ctx_iterative_alignments(self._h, C.byref(p)))
         return Alignments(p)
 
-    def enable_inversions(self, min_size: int = 0, keep_alignments: bool = False, on: bool = True):
-        """--patch-inversions for the next run() / align_all(unite=True) of the loaded context (min_size 0 = 2 * -k)"""
+    def enable_inversions(self, min_size: int = 0, keep_alignments: bool = False, on: bool = True, join_below: int = 0):
+        """--patch-inversions for the next run() / align_all(unite=True) of the loaded context (min_size 0 = 2 * -k);
+        join_below = J of --inversion-join (0 = the plain rule)"""
         if not on:
             check(self.L.sr_ctx_enable_inversions(self._h, None))
             return
-        ip = InvParamsC(int(min_size), 1 if keep_alignments else 0, 0)
+        if not 0 <= int(join_below) < 2 ** 32:
+            raise SeqRushError(-1, f"inversion join length out of range: {join_below}")
+        ip = InvParamsC(int(min_size), 1 if keep_alignments else 0, int(join_below))
         check(self.L.sr_ctx_enable_inversions(self._h, C.byref(ip)))
 
     def inversion_stats(self):
@@ -339,6 +343,12 @@ class Context:
         st = InvStatsC()
         check(self.L.sr_ctx_inversion_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in InvStatsC._fields_}
+
+    def inversion_join_stats(self):
+        """sr_ctx_inversion_join_stats of the last run -> dict"""
+        out = (C.c_uint64 * 4)()
+        check(self.L.sr_ctx_inversion_join_stats(self._h, out))
+        return dict(islands_absorbed=int(out[0]), rejected_site_cost=int(out[1]), host_us=int(out[2]))
 
     def inversion_jobs(self):
         """the jobs of the last run (pair order, then CIGAR order) -> list of dicts of the sr_inv_job fields"""
@@ -635,6 +645,7 @@ class SeqRush:
         if args.patch_inversions and (args.inversion_min_size or 2 * args.min_match_length) == 0:
             raise SeqRushError(-1, "--patch-inversions needs -k or --inversion-min-size: a threshold of 0 would call every "
                                    "complementary SNP an inversion")
+        check_inversion_join(args)
         if args.paf is not None:                      # align_and_unite_from_paf (src/seqrush.rs:510-609)
             print(f"Reading alignments from PAF file: {args.paf}")
             self.ctx.load_paf(self.seqset, Params.from_args(args), args.paf)
@@ -652,7 +663,8 @@ class SeqRush:
         n = len(self.sequences)
         print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
         if args.patch_inversions:
-            self.ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments))
+            self.ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments),
+                                       join_below=args.inversion_join)
         if args.output_alignments:
             al = self.ctx.align_all(unite=True)         # batches: align, copy the CIGARs out, unite
             print(f"Writing alignments to {args.output_alignments}")
@@ -666,6 +678,10 @@ class SeqRush:
             st = self.ctx.inversion_stats()
             self.inversion_stats = st
             print(f"Patched inversions: {st['accepted']} of {st['candidates']} candidate gaps")
+            if args.verbose and args.inversion_join:
+                js = self.ctx.inversion_join_stats()
+                self.inversion_join_stats = js
+                print(inversion_join_report(js))
         self.labels = self.ctx.download_labels()
         self.ctx.sync()
 
@@ -763,7 +779,8 @@ def run_seqrush_rank(args: Args):
             n = len(sequences)
             print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
         if args.patch_inversions:               # a job stays on the rank that owns its pair and lands in that rank's forest
-            ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments))
+            ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments),
+                                  join_below=args.inversion_join)
         if args.output_alignments:
             al = ctx.align_all(unite=True)
             al.write_paf(sr.seqset, f"{args.output_alignments}.rank{rank}")
@@ -774,10 +791,14 @@ def run_seqrush_rank(args: Args):
     ctx.sync()
     if args.patch_inversions and args.paf is None:
         st = ctx.inversion_stats()
-        tot = torch.tensor([st["accepted"], st["candidates"]], dtype=torch.int64, device="cpu" if single_dev else "cuda")
+        js = ctx.inversion_join_stats()
+        tot = torch.tensor([st["accepted"], st["candidates"], js["islands_absorbed"], js["rejected_site_cost"], js["host_us"]],
+                           dtype=torch.int64, device="cpu" if single_dev else "cuda")
         dist.all_reduce(tot)
         if rank == 0:
             print(f"Patched inversions: {int(tot[0])} of {int(tot[1])} candidate gaps")
+            if args.verbose and args.inversion_join:
+                print(inversion_join_report(dict(islands_absorbed=int(tot[2]), rejected_site_cost=int(tot[3]), host_us=int(tot[4]))))
     ufn = ctx.uf_size
     u32 = ufn < (1 << 32)
     ldt = torch.int32 if u32 else torch.int64
@@ -811,6 +832,23 @@ def run_seqrush_rank(args: Args):
 
 
 SR_SPARSE_TREE = 4
+
+
+def check_inversion_join(args: "Args"):
+    """the refusals of --inversion-join that need no device"""
+    if args.inversion_join < 0:
+        raise SeqRushError(-1, f"--inversion-join needs a non-negative integer, got {args.inversion_join}")
+    if args.inversion_join and not args.patch_inversions:
+        raise SeqRushError(-1, "--inversion-join is an option of --patch-inversions: give both")
+    if args.inversion_join and args.inversion_join > (args.inversion_min_size or 2 * args.min_match_length):
+        raise SeqRushError(-1, f"--inversion-join {args.inversion_join} is above the gap threshold of --patch-inversions "
+                               f"({args.inversion_min_size or 2 * args.min_match_length}): an island would be a candidate by itself")
+
+
+def inversion_join_report(js: dict) -> str:
+    """the -v line of --inversion-join"""
+    return (f"Inversion join: {js['islands_absorbed']} match islands absorbed into candidate gaps, "
+            f"{js['rejected_site_cost']} jobs rejected by site cost")
 
 
 def append_inversion_paf(ctx: Context, seqset: SeqSet, path: str, on: bool = True):
@@ -849,6 +887,47 @@ def inversion_candidate(qgap: int, tgap: int, min_size: int) -> bool:
     if r < 0:
         check(r)
     return r == 1
+
+
+def inversion_sites_host_join(ops, min_size: int, join_below: int, scores: str = "0,5,8,2,24,1"):
+    """the joined rule over one alignment -> (list of site dicts, list of site costs)"""
+    L = _lib.load()
+    a, ap = _ops_array(ops)
+    prm = Params(scores=scores)
+    p = C.POINTER(InvSiteC)(); pc = C.POINTER(C.c_int32)(); cnt = C.c_uint64()
+    check(L.sr_inversion_sites_host_join(ap, len(a), int(min_size), int(join_below), C.byref(prm.c), C.byref(p), C.byref(pc),
+                                         C.byref(cnt)))
+    out = _sites(p, cnt.value), [int(pc[i]) for i in range(cnt.value)]
+    L.sr_free(C.cast(p, C.c_void_p)); L.sr_free(C.cast(pc, C.c_void_p))
+    return out
+
+
+def inversion_accept_site(patch_score: int, site_cost: int) -> bool:
+    return _lib.load().sr_inversion_accept_site(int(patch_score), int(site_cost)) == 1
+
+
+def inversion_scan_device_join(cigars, min_size: int, join_below: int, scores: str = "0,5,8,2,24,1", score=None, max_score=None,
+                               device: int = 0):
+    """tests: the joined device scan over a list of op arrays -> ([(alignment index, site dict, site cost)] in job order,
+    dict(scanned, sites, candidates, islands))"""
+    L = _lib.load()
+    off = np.zeros(len(cigars) + 1, dtype=np.uint64)
+    np.cumsum([len(c) for c in cigars], out=off[1:])
+    a, ap = _ops_array(np.concatenate([np.asarray(c, dtype=np.uint32) for c in cigars]) if len(cigars) else [])
+    prm = Params(scores=scores)
+    i32p = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.int32)      # noqa: E731
+    sc, mx = i32p(score), i32p(max_score)
+    ptr = lambda v: None if v is None else v.ctypes.data_as(C.POINTER(C.c_int32))        # noqa: E731
+    p = C.POINTER(InvSiteC)(); ow = C.POINTER(C.c_uint64)(); pc = C.POINTER(C.c_int32)(); cnt = C.c_uint64()
+    st = (C.c_uint64 * 4)()
+    check(L.sr_inversion_scan_device_join(device, ap, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(cigars), int(min_size),
+                                          int(join_below), C.byref(prm.c), ptr(sc), ptr(mx), C.byref(p), C.byref(ow), C.byref(pc),
+                                          C.byref(cnt), st))
+    sites = _sites(p, cnt.value)
+    out = [(int(ow[i]), sites[i], int(pc[i])) for i in range(cnt.value)]
+    for q in (p, ow, pc):
+        L.sr_free(C.cast(q, C.c_void_p))
+    return out, dict(scanned=int(st[0]), sites=int(st[1]), candidates=int(st[2]), islands=int(st[3]))
 
 
 def inversion_accept(patch_score: int, main_score: int) -> bool:
