@@ -135,3 +135,17 @@ for seed in range(LOFF, int(sys.argv[8]) if len(sys.argv) > 8 else LOFF + 120):
             else: os.environ[k] = v
     if seed % 20 == 0: print("lattice", seed, name, bits, flush=True)
 print("lattice fuzz done, failures:", bad)
+
+# built partitions (tests/partition_inputs.py): a seeded random partition of 2..4096 bases over ACGT or the mixed alphabet,
+# one to three label arrays merged through the 64- or the 32-bit kernel and induced, with and without compaction, against
+# the host twins -- no alignment in the loop
+import test_partitions_gpu as tp
+bad = []
+POFF = int(sys.argv[9]) if len(sys.argv) > 9 else 8            # (argv[9], argv[10]: seed range of the partitions)
+for seed in range(POFF, int(sys.argv[10]) if len(sys.argv) > 10 else POFF + 400):
+    try:
+        tp.check_random_partition(seed)
+    except Exception as e:
+        bad.append((seed, repr(e)[:200])); print("FAIL partition", seed, repr(e)[:200], flush=True)
+    if seed % 50 == 0: print("partition", seed, flush=True)
+print("partition fuzz done, failures:", bad)

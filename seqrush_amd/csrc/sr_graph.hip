@@ -12,7 +12,8 @@
 //     first orientation and first-seen order kept (src/bidirected_ops.rs:813-825): open-addressing hash
 //     table keyed by min((from,to), (to^1,from^1)) holding the smallest position, then flag + scan + emit.
 // The host (sr_ctx_build_gfa) formats the GFA text from the compact arrays; the text is byte-identical to
-// sr_build_gfa() on the downloaded labels (tests/test_gpu_parity.py::test_graph_induction_on_device).
+// sr_build_gfa() on the downloaded labels (tests/test_gpu_parity.py::test_graph_induction_on_device on aligned families,
+// tests/test_partitions_gpu.py::test_induction on built partitions at the tile, scan-level and grid-cap sizes).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include "sr_internal.h"

@@ -13,6 +13,7 @@ import seqrush_amd as sa
 from seqrush_amd import synth, _lib
 from seqrush_amd.seqrush import SeqSet, Params, Context, build_gfa
 from conftest import canon_gfa, usable_cpus
+from partition_inputs import oracle_paf_replay
 
 pytestmark = pytest.mark.gpu
 
@@ -291,30 +292,6 @@ def test_fused_entry_points_and_paf(gpu, tmp_path):
         cg = [x for x in f[12:] if x.startswith("cg:Z:")][0][5:]
         assert o2.process_alignment(cg, names.index(f[0]), names.index(f[5]), 0, f[4] == "-", int(f[2]), int(f[3]), int(f[7]), int(f[8])) >= 0
     assert np.array_equal(o2.canonical_labels(), labels)
-
-
-def oracle_paf_replay(recs, paf_text, k=0):
-    """align_and_unite_from_paf (src/seqrush.rs:510-609) on the oracle: same record rules"""
-    o = ob.OracleSeqRush(records=recs)
-    idx = {}
-    for i, (name, _) in enumerate(recs):
-        idx[name] = i                                   # HashMap collect: a later duplicate wins
-    for ln in paf_text.split("\n"):
-        if ln == "":
-            continue
-        f = ln.split("\t")
-        if len(f) < 12:
-            continue
-        cg = ""
-        for x in f[12:]:
-            if x.startswith("cg:Z:"):
-                cg = x[5:]
-                break
-        if f[0] not in idx or f[5] not in idx:
-            continue
-        assert o.process_alignment(cg, idx[f[0]], idx[f[5]], k, f[4] == "-", int(f[2]), int(f[3]),
-                                   int(f[7]), int(f[8])) >= 0
-    return o.canonical_labels()
 
 
 def gpu_paf_labels(recs, paf_path, **kw):
