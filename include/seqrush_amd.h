@@ -295,6 +295,9 @@ int sr_uf_count_components_host(const uint64_t *nodes, uint64_t n, uint64_t tota
 int sr_iterative_stop_host(const uint64_t *counts, uint64_t nchecks, uint64_t post_tree, uint64_t *stop_check);
 int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, uint32_t **tree_i, uint32_t **tree_j,
                             uint64_t *tree_count, uint32_t **rand_i, uint32_t **rand_j, uint64_t *rand_count);
+/* host twin of the blocked alignment kernel's base-case cone: a level with `levels_left` levels to its job's last one
+ * computes the diagonals within this many of the end diagonal tlen - plen (< 0: none) */
+int sr_base_cone_reach(int e1, int e2, int two, int levels_left);
 
 /* -------- inversion patching (`--patch-inversions`; src/inversion_aware_seqrush.rs:118-255, src/cigar_analysis.rs:23-147) ----
  * After each batch's alignment kernel the device scans every CIGAR for two-sided gaps between match ops (qgap / tgap =

@@ -29,7 +29,7 @@ EXPORTS = [
     "sr_build_gfa_from_nodes", "sr_ctx_counters_all", "sr_knobs_doc",
     "sr_sort_params_default", "sr_ctx_build_gfa_sorted", "sr_sort_gfa", "sr_sgd_layout", "sr_sgd_tables", "sr_sort_stats",
     "sr_ctx_load_iterative", "sr_ctx_run_iterative", "sr_ctx_iterative_stats", "sr_ctx_iterative_alignments",
-    "sr_uf_count_components_host", "sr_iterative_stop_host", "sr_iterative_pair_lists",
+    "sr_uf_count_components_host", "sr_iterative_stop_host", "sr_iterative_pair_lists", "sr_base_cone_reach",
     "sr_ctx_enable_inversions", "sr_ctx_inversion_stats", "sr_ctx_inversion_jobs", "sr_ctx_inversion_alignments",
     "sr_append_paf_tagged", "sr_inversion_sites_host", "sr_inversion_candidate", "sr_inversion_accept",
     "sr_inversion_scan_device",
@@ -201,6 +201,7 @@ def load():
     L.sr_ctx_iterative_alignments.argtypes = [vp, C.POINTER(C.POINTER(AlignmentsC))]
     L.sr_uf_count_components_host.argtypes = [C.POINTER(u64), u64, u64, C.POINTER(u64)]
     L.sr_iterative_stop_host.argtypes = [C.POINTER(u64), u64, u64, C.POINTER(u64)]
+    L.sr_base_cone_reach.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     PU32 = C.POINTER(C.POINTER(C.c_uint32))
     L.sr_iterative_pair_lists.argtypes = [C.c_uint32, C.POINTER(C.c_uint8), PP, PU32, PU32, C.POINTER(u64), PU32, PU32,
                                           C.POINTER(u64)]

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
     RH.base = bhist; RH.cM = 0; RH.cst2 = 0; RH.sstr = 0; RH.chs = 256u; RH.depth = 0x3fff; RH.depth2 = 0x3fff; RH.urow = 0; RH.perjob = true; RH.extent = (unsigned)a.bhist_wg_stride;
     RH.nuloff = (unsigned)a.hist_cap; RH.trash = RH.nuloff + hw;
     if (tid < 64) k_sh.cells_l[tid] = 0ull;
-    if (tid < 32) k_sh.row_w[tid >> 4][tid & 15] = 0ull;
+    if (tid < 64) k_sh.row_w[tid >> 4][tid & 15] = 0ull;
     {   // NULL rows
         for (int r = 0; r < SR_NULL_ROWS; r++)
             for (int i = tid; i < a.brow; i += NT) rput(RR, RR.nuloff + (unsigned)r * 256u, (unsigned)i, NULLV);
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
 #ifdef SR_BOUNDS
             k_sh.bnd_flag = 0; k_sh.bnd_off = k_sh.bnd_ext = k_sh.bnd_what = 0; k_sh.lds_seq_bytes = 16u * a.max_words + 16u;
 #endif
-            k_sh.dg_steps = k_sh.dg_nbase = k_sh.dg_nbp = k_sh.dg_npass = 0;
+            k_sh.dg_steps = k_sh.dg_nbase = k_sh.dg_nbp = k_sh.dg_npass = 0; k_sh.base_tiles = k_sh.base_cells = 0;
             b_sh.geom.brow = a.brow; b_sh.geom.ring_scope = a.ring_scope; b_sh.geom.ring_hot = a.ring_hot;
             b_sh.geom.bbase_jobs = a.bbase_jobs; b_sh.geom.hist_w = a.hist_w; b_sh.geom.hist_levels = a.hist_levels;
             b_sh.geom.urow = urow;
@@ -380,6 +380,9 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         }
         // ---------------- leaves in order: trivial ones are emitted directly, base cases in batches
         const unsigned long long tc0 = KTICK();
+        // (row traffic so far was the ring's: from here to the end of the pair the tiles run on the base-case histories)
+        if ((tid & 63) == 0) { k_sh.row_w[0][(tid >> 6) & 15] += row_ld; k_sh.row_w[1][(tid >> 6) & 15] += row_st; }
+        row_ld = 0; row_st = 0;
         {
             const int n_cur = RFL(b_sh.list_n);
             if (tid == 0) b_sh.emit_pos = 0;
@@ -434,7 +437,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     for (int s0i = 0; RFL(b_sh.nrunning) > 0; s0i += B) {
                         const int s0 = kopaque_s(s0i);
                         if (s0 + B > hlevels) { if (tid == 0) b_sh.err |= SR_DEV_ERR_BASE_OVERFLOW; break; }
-                        blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1>(RH, s0, pen, nb, row_ld, row_st, s0 == 0);
+                        blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1, OT, false, true>(RH, s0, pen, nb, row_ld, row_st, s0 == 0);
                         __syncthreads();
                         if (tid == 0) k_sh.dg_steps += (unsigned long long)b_sh.nrunning * B;
                         if (tid < 64) {                          // one lane per base case: first level of the block that reached the end
@@ -456,7 +459,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             }
                             const unsigned long long rm = __ballot(running);
                             if (tid == 0) b_sh.nrunning = __popcll(rm);
-                            if (rm != 0ull) blk_setup<TWO, NT, B, E1, E2>(s0 + B, pen, nb);   // tables of the next pass
+                            if (rm != 0ull) blk_setup<TWO, NT, B, E1, E2, false, true>(s0 + B, pen, nb);   // tables of the next pass (cone-clipped)
                             KPRIO_LO();
                         }
                         __syncthreads();
@@ -593,7 +596,10 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         }
         t_all += KTICK() - tk0;
         // (the wave's 64-bit sums live in LDS, not in registers across the pairs)
-        if ((tid & 63) == 0) { k_sh.row_w[0][(tid >> 6) & 15] += row_ld; k_sh.row_w[1][(tid >> 6) & 15] += row_st; }
+        if ((tid & 63) == 0) {
+            k_sh.row_w[0][(tid >> 6) & 15] += row_ld; k_sh.row_w[1][(tid >> 6) & 15] += row_st;
+            k_sh.row_w[2][(tid >> 6) & 15] += row_ld; k_sh.row_w[3][(tid >> 6) & 15] += row_st;      // (the histories' share)
+        }
         row_ld = 0; row_st = 0;
     }
     if (tid < 64 && k_sh.cells_l[tid]) atomicAdd(&a.counters[0], k_sh.cells_l[tid]);
@@ -602,6 +608,11 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         const unsigned long long row_ld_acc = k_sh.row_w[0][(tid >> 6) & 15], row_st_acc = k_sh.row_w[1][(tid >> 6) & 15];
         if (row_ld_acc) atomicAdd(&a.counters[16], row_ld_acc * lane_bytes);
         if (row_st_acc) atomicAdd(&a.counters[17], row_st_acc * lane_bytes);
+        // of these, the base-case histories (the ring's share is the difference), the base cases' tiles and level-diagonals as
+        // executed: the experiment slots [44..47]
+        const unsigned long long hist_ld_acc = k_sh.row_w[2][(tid >> 6) & 15], hist_st_acc = k_sh.row_w[3][(tid >> 6) & 15];
+        if (hist_ld_acc) atomicAdd(&a.counters[44], hist_ld_acc * lane_bytes);
+        if (hist_st_acc) atomicAdd(&a.counters[45], hist_st_acc * lane_bytes);
     }
     if (tid == 0) {
         atomicAdd(&a.counters[0], b_sh.cells);
@@ -612,6 +623,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         atomicAdd(&a.counters[19], k_sh.dg_f); atomicAdd(&a.counters[20], k_sh.dg_c);
         atomicAdd(&a.counters[21], k_sh.dg_e); atomicAdd(&a.counters[22], k_sh.dg_r);
         if (k_sh.dg_redo) atomicAdd(&a.counters[37], k_sh.dg_redo);
+        atomicAdd(&a.counters[46], k_sh.base_tiles); atomicAdd(&a.counters[47], k_sh.base_cells);
         if (PROF) {
             if (!a.pre_oriented) atomicAdd(&a.counters[6], t_ori);    // ([6] holds sr_orient_kernel's cells otherwise)
             atomicAdd(&a.counters[7], t_bp);

@@ -1,5 +1,6 @@
 // sr_blk_pass.inc -- blocked kernel (sr_align_blk.inc), part 3: a pass over a block of levels -- reach and tile windows
 // (kreach, kwindow), the pass tables (blk_setup), the tile queue (blk_pass), the I/D recompute pass (blk_recompute).
+#include "sr_base_cone.h"       // backward cone of a base case (shared with the host twin)
 // reach() with compile-time gap-extends (the host guarantees pen.e1 == E1, pen.e2 == E2): no runtime division
 template <bool TWO, int E1, int E2>
 __device__ __forceinline__ int kreach(const SrPen &p, int s, int begin) {
@@ -43,25 +44,49 @@ __device__ __forceinline__ void kwindow(const SrPen &pen, const BJob &b, int s0,
 // Tables of one pass (levels s0 .. s0+B-1 of every active aligner): wave 0, one lane per aligner.  The first pass of a batch
 // of searches runs it inside blk_pass; later passes get their tables from the wave-0 section that ends the previous pass
 // (control, or the section after breakpoint detection), so a pass costs one barrier and one serial hop less.
-template <bool TWO, int NT, int B, int E1, int E2, bool TIGHT = false>
+// BASE: the aligners are base cases.  Each knows its end diagonal (kend) and the levels it was given (pad1 = lj), so every
+// level's range, and the tile window with it, is intersected with the backward cone of the end (sr_base_cone.h): cells outside
+// it cannot lie on a path to the end, are not computed (NULL inside the window) and not stored.  The window keeps the wide
+// margin on its forward sides: a reader in the cone reads neighbours in the (wider) cone of the source level, which lie
+// within the source block's forward range + scope + 1 as before, so inside its window.  A job whose clipped range is empty
+// gets no tiles (it cannot end within its levels and is re-queued or fails as before).
+// The cells counted (cells_l -> counters[0], b_sh.cells, blk_surplus) stay those of the UNCLIPPED ranges, as the oracle
+// counts them; tiles and row bytes are counted as executed (base_tiles / base_cells: the clipped figures).
+#ifndef SR_BASE_CONE
+#define SR_BASE_CONE 1             // (0: A/B build that computes the full forward triangle, as before)
+#endif
+template <bool TWO, int NT, int B, int E1, int E2, bool TIGHT = false, bool BASE = false>
 __device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs) {
     const int tid = threadIdx.x;                         // (tid < 64)
-    int nt = 0, glo = 0, ghi = -1, cells = 0;
+    constexpr bool CONE = BASE && SR_BASE_CONE;
+    int nt = 0, glo = 0, ghi = -1, cells = 0, ccells = 0;
     const bool act = tid < njobs && b_sh.job[tid].active;
     const int pglo = (tid < BJ_MAX) ? k_sh.jglo[tid] : 0, pghi = (tid < BJ_MAX) ? k_sh.jghi[tid] : -1;
     if (act) {
         const BJob &b = b_sh.job[tid];
-        int Rw = 0;
+        int Rw = 0, clo0 = 0, chi0 = 0;
 #pragma unroll
         for (int j = 0; j < B; j++) {
             Rw = kreach<TWO, E1, E2>(pen, s0 + j, b.begin);
-            const int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
-            k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
+            int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
             cells += (khi >= klo) ? khi - klo + 1 : 0;
+            if (CONE) {
+                const int rb = sr_cone_reach(E1, E2, TWO, b.pad1 - 1 - (s0 + j));      // (< 0 past the job's levels: empty)
+                klo = max(klo, b.kend - rb); khi = min(khi, b.kend + rb);
+                if (j == 0) { clo0 = b.kend - rb; chi0 = b.kend + rb; }                // the block's widest cone
+            }
+            k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
+            ccells += (khi >= klo) ? khi - klo + 1 : 0;
         }
         (void)Rw;
         kwindow<TWO, B, E1, E2, TIGHT>(pen, b, s0, glo, ghi);
-        nt = (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN;
+        if (CONE) {
+            const int mg = TIGHT ? 1 : pen.scope + 1;
+            const int wlo = max(max(-b.plen - 1, -Rw - mg), clo0 - 1), whi = min(min(b.tlen + 1, Rw + mg), chi0 + 1);
+            glo = (wlo + b.shift) >> 2; ghi = (whi >= wlo) ? (whi + b.shift) >> 2 : glo - 1;
+        }
+        nt = max(0, (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN);
+        if (BASE && ccells) atomicAdd(&k_sh.base_cells, (unsigned long long)ccells);
     }
     // (jmerge, jband, jbandown, nband and the second prefix sum are what is left of two round-4 experiments that stayed off,
     // merged tail tiles and the band-first tile order (profiles/r04_ab.log, DESIGN.md section 7): no tile is merged, the
@@ -82,17 +107,17 @@ __device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs) {
         for (int j = 0; j < B; j++) { k_sh.jak[j][tid] = 0; k_sh.jreach[j][tid] = 0; }
     }
     if (tid == 0) k_sh.jtstart[0] = 0;
-    if (tid == 63) { k_sh.nband = hincl; k_sh.total_tiles = incl + hincl; k_sh.next_tile = NT / 64; }
+    if (tid == 63) { k_sh.nband = hincl; k_sh.total_tiles = incl + hincl; k_sh.next_tile = NT / 64; if (BASE) k_sh.base_tiles += (unsigned long long)incl; }
     k_sh.cells_l[tid] += (unsigned long long)cells;      // (tid < 64)
 }
 
-template <typename OT, bool TWO, int NT, int B, int E1, int E2, bool PROF, int X = 0, int OE1 = 0, typename ST = OT, bool RING = false>
+template <typename OT, bool TWO, int NT, int B, int E1, int E2, bool PROF, int X = 0, int OE1 = 0, typename ST = OT, bool RING = false, bool BASE = false>
 __device__ __forceinline__ void blk_pass(const KRows<OT, ST> &R, int s0, const SrPen &pen, int njobs,
                                          unsigned &row_ld, unsigned &row_st, const bool setup = true) {
     const int tid = threadIdx.x;
     if (setup) {
         const unsigned long long tsu0 = KTICK();
-        if (tid < 64) blk_setup<TWO, NT, B, E1, E2, RING && KTIGHT_OF(OT, ST, B, X)>(s0, pen, njobs);
+        if (tid < 64) blk_setup<TWO, NT, B, E1, E2, RING && KTIGHT_OF(OT, ST, B, X), BASE>(s0, pen, njobs);
         __syncthreads();
         if (PROF && threadIdx.x == 0) k_sh.t_setup += KTICK() - tsu0;
     }

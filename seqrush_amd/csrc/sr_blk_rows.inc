@@ -35,7 +35,8 @@ struct KShared {
 #endif
     int redo_from;                     // base cases: first job of the batch that outgrew the levels it was given (BJ_MAX: none)
     int pend_op, pend_len;             // CIGAR emission: the run being built (not yet stored)
-    unsigned long long row_w[2][16];   // per wave, lane accesses of its tiles' row loads / stores (summed when the kernel ends)
+    unsigned long long row_w[4][16];   // per wave, lane accesses of its tiles' row loads / stores (summed when the kernel ends); [2..3]: the base-case histories' share
+    unsigned long long base_tiles, base_cells;   // base cases: tiles really run, level-diagonals really computed (cone-clipped; cells_l counts the unclipped ranges)
     unsigned long long cells_l[64];    // wavefront cells per lane of wave 0 (= aligner), summed when the kernel ends
     unsigned long long t_c1, t_c2;                           // PROF: control section: max_ak stores, per-segment control
     unsigned long long t_setup, t_p2a, t_p2f, t_p2e, t_p2w;     // PROF: ticks of the set-up sections, of breakpoint detection's stages

@@ -569,8 +569,11 @@ __device__ __forceinline__ void blk_tile16(const KR &R, const int s0, const int 
     const unsigned long long ownb = __builtin_amdgcn_ballot_w64(owned);
     Q4 kk;                                               // the lane's diagonals
     kk.a = h2_pack(k0, k0 + 1); kk.b = h2_pack(k0 + 2, k0 + 3);
-    // the ranges of a block's levels are nested (level 0 the narrowest): a tile inside level 0's range needs no range masks
-    const int klo0 = RFL(k_sh.jklo[0][tix]), khi0 = RFL(k_sh.jkhi[0][tix]);
+    // the ranges of a block's levels are nested (level 0 the narrowest): a tile inside level 0's range needs no range masks.
+    // (Base cases, never ring tiles: a level's range is forward range x backward cone, blk_setup -- the forward side widens
+    // with the level, the cone side narrows, so the intersection of the block's ranges is that of its first and last level.)
+    int klo0 = RFL(k_sh.jklo[0][tix]), khi0 = RFL(k_sh.jkhi[0][tix]);
+    if constexpr (!RING) { klo0 = max(klo0, RFL(k_sh.jklo[B - 1][tix])); khi0 = min(khi0, RFL(k_sh.jkhi[B - 1][tix])); }
     const bool inside = __builtin_amdgcn_ballot_w64(!(k0 >= klo0 && k0 + 3 <= khi0)) == 0ull;
     Q4 hI1[B], hD1[B], hI2[B], hD2[B], mvh[XK ? B : 1];
 #pragma unroll

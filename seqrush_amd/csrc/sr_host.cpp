@@ -23,6 +23,7 @@
 #include "sr_sort.h"
 #include "sr_iter_rule.h"
 #include "sr_inv_rule.h"
+#include "sr_base_cone.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -2519,6 +2520,12 @@ extern "C" int sr_iterative_stop_host(const uint64_t *counts, uint64_t nchecks, 
     for (uint64_t k = 0; k < nchecks && !s.stopped; k++) sr_iter_step(&s, counts[k], (uint32_t)k);
     if (s.stopped) *stop_check = (uint64_t)s.stop_check + 1;
     return SR_OK;
+}
+
+// the blocked kernel's backward cone of a base case (sr_base_cone.h, what blk_setup clips every level's range with):
+// diagonals either side of the end diagonal that a level with `levels_left` levels to go keeps; < 0: none
+extern "C" int sr_base_cone_reach(int e1, int e2, int two, int levels_left) {
+    return sr_cone_reach(e1, e2, two != 0, levels_left);
 }
 
 // canonical labels of a node array: the minimum element of each set (what sr_ctx_download_labels returns)

@@ -465,7 +465,10 @@ class Context:
                     st_wait_cycles=int(out[32]), st_body_cycles=int(out[33]), st_tiles=int(out[34]), st_ext_iters=int(out[35]),
                     lds_row_bytes=int(out[36]), base_requeues=int(out[37]),
                     bounds_first=[int(out[40]), int(out[41]), int(out[42]), int(out[43])],
-                    experiment=[int(out[44]), int(out[45]), int(out[46]), int(out[47])])
+                    experiment=[int(out[44]), int(out[45]), int(out[46]), int(out[47])],
+                    # blocked kernel: the base-case histories' share of row_bytes_*, base-case tiles and level-diagonals as executed
+                    hist_bytes_loaded=int(out[44]), hist_bytes_stored=int(out[45]), base_tiles=int(out[46]),
+                    base_level_diagonals=int(out[47]))
 
     def close(self):
         if self._h:
