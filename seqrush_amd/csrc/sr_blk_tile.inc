@@ -342,8 +342,12 @@ __device__ __forceinline__ Q4 q4_bound(Q4 v, Q4 L) {
 // (margin 16384 for int16 rows, 8192 for the 16-bit ring of 32-bit searches: ~4 800 / ~2 400 levels at 17 per 5 levels) and
 // be extended, stored and tested for overlaps like a cell (round 4: found by the bounds-checked build -- an LDS window of a
 // "live" cell 2 KB in front of the sequences -- on a 50 kb pair of score > 16 000; C5's mean score is 15 000).  Tiles of
-// deep levels (`deep`, uniform) therefore reset the sources a block takes its chains up from when they are loaded: the
-// creep of a chain is then bounded by one block.
+// deep levels (`deep`, uniform) therefore reset, when they are loaded, the chain sources of the four gap components and the
+// M[s - x] sources of the block's first x levels: the creep through THOSE sources is bounded by one block.  The gap-open
+// sources -- Lmo1[0..4] (M[s - o1 - e1]) and every Lmo2[j] (M[s - o2 - e2]), the rows prefetched inside the level loop
+// included -- are not reset, so a NULL can still creep through M -> I/D -> M across blocks (ADVICE.md round 4 estimates the
+// valid range near level 6 600 / 3 300 from reading the code).  tests/test_deep_gpu.py runs one-sided gaps and unrelated pairs
+// past those levels on both cell widths, production and bounds-checked build, against the oracle.
 template <uint32_t NUL, int BIAS>
 __device__ __forceinline__ Q4 q4_renull(Q4 v) {
     uint32_t ta, tb, ra, rb;
@@ -536,7 +540,8 @@ __device__ __forceinline__ void blk_tile16(const KR &R, const int s0, const int 
     }
     // deep levels: creeping NULLs are reset (q4_renull) where a block takes its chains up -- the M[s - x] sources of the
     // block's first levels and the gap chains' sources -- under ONE uniform branch per tile (nothing per level: the
-    // level code is not duplicated).  An M chain then creeps at most two steps (34) and a gap chain ten before the next reset.
+    // level code is not duplicated).  Through these sources an M chain creeps at most two steps (34) and a gap chain ten
+    // before the next reset; the gap-open sources (Lmo1[0..4], every Lmo2[j]) pass unreset (see q4_renull).
     const bool deep = s0 >= (BIAS ? SR_DEEP_RING16 : SR_DEEP_INT16);
     if (deep) {
 #pragma unroll

@@ -60,9 +60,11 @@ def run_gpu(recs, **kw):
     return ss, al, labels, nodes, cnt
 
 
-def check_parity(recs, **kw):
+def check_parity(recs, oracle=None, **kw):
+    """oracle: an object with OracleSeqRush's align_pair / align_and_unite / canonical_labels / gfa that holds the oracle's
+    answers on (recs, kw) already (test_deep_gpu.OracleOnce: one oracle run shared by every regime of an input)"""
     ss, al, labels, nodes, cnt = run_gpu(recs, **kw)
-    o = ob.OracleSeqRush(records=recs)
+    o = oracle if oracle is not None else ob.OracleSeqRush(records=recs)
     op = oracle_params(**kw)
     for i in range(al.n):
         q, t = int(al.query_idx[i]), int(al.target_idx[i])
