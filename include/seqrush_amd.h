@@ -450,6 +450,20 @@ int sr_sgd_tables(const char *gfa_in, const sr_sort_params *p, sr_sort_params *r
  * copies, SGD, ordering, groom, topological sort, path verification, GFA writing).  Returns the number of slots written. */
 int sr_sort_stats(double *out, uint32_t cap);
 
+/* -------- compaction by per-handle tables ----------------------------------------------
+ * compact() + renumber_nodes_sequentially() of any GFA with S / L / P lines and numeric node ids.  All three
+ * executions return the same bytes.  In sr_ctx_build_gfa_opts / sr_ctx_build_gfa_sorted, compact == 2 compacts on the
+ * context's device, straight from the arrays graph induction left there (0 and 1 as before).
+ * stats (or NULL): [0] rounds, [1] rounds run by the host procedure because they held an irregular list (one that
+ * meets its own mirror, or a cycle), [2] chains merged, [3] longest list of links, [4] pointer-jumping launches,
+ * [5] compaction + renumbering in microseconds (hipEvents on a device, host clock for -1 and -2), [6] upload +
+ * download in microseconds (host clock; 0 for -1 and -2), [7] 0. */
+#define SR_COMPACT_DEVICE_HOST (-1)          /* sr_compact.cpp's greedy procedure */
+#define SR_COMPACT_DEVICE_TABLES_HOST (-2)   /* the table formulation on the host, in index order */
+int sr_compact_gfa(const char *gfa_in, int device, char **gfa_out, uint64_t *n_nodes, uint64_t *n_edges, uint64_t stats[8]);
+/* stats of the calling thread's last compaction by tables (sr_compact_gfa, or a context build with compact == 2) */
+int sr_compact_stats(uint64_t stats[8]);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

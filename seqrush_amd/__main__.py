@@ -22,6 +22,8 @@ def main(argv=None):
     ap.add_argument("-p", "--paf", default=None)
     ap.add_argument("--output-alignments", default=None)
     ap.add_argument("--no-compact", action="store_true")
+    ap.add_argument("--compact-on", choices=("host", "device"), default="host",
+                    help="where compaction + renumbering run: the host procedure, or per-handle tables on the GPU (same bytes)")
     ap.add_argument("--no-sort", action="store_true")
     ap.add_argument("--sort", action="store_true",
                     help="Ygs layout: path-guided SGD on the GPU (reproducible), grooming, topological sort")
@@ -46,6 +48,9 @@ def main(argv=None):
     ns = ap.parse_args(argv)
     if ns.sort and ns.no_sort:
         print("Error: --sort and --no-sort exclude each other", file=sys.stderr)
+        return 1
+    if ns.compact_on == "device" and ns.no_compact:
+        print("Error: --compact-on device and --no-compact exclude each other", file=sys.stderr)
         return 1
     if ns.iterative and (ns.paf is not None or ns.gpus > 1):
         # before any rank starts: the stop rule is global and sequential, and -p has no alignment stage to stop
@@ -74,7 +79,7 @@ def main(argv=None):
     args = Args(sequences=ns.sequences, output=ns.output, min_match_length=ns.min_match_length,
                 threads=ns.threads, scores=ns.scores, orientation_scores=ns.orientation_scores,
                 max_divergence=ns.max_divergence, sparsification=ns.sparsification, paf=ns.paf,
-                output_alignments=ns.output_alignments, no_compact=ns.no_compact, no_sort=ns.no_sort,
+                output_alignments=ns.output_alignments, no_compact=ns.no_compact, compact_on=ns.compact_on, no_sort=ns.no_sort,
                 sort=ns.sort, sort_seed=ns.sort_seed, sgd_iter_max=ns.sgd_iter_max, skip_sgd=ns.skip_sgd,
                 skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
                 aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative,

@@ -34,6 +34,7 @@ EXPORTS = [
     "sr_append_paf_tagged", "sr_inversion_sites_host", "sr_inversion_candidate", "sr_inversion_accept",
     "sr_inversion_scan_device",
     "sr_ctx_inversion_join_stats", "sr_inversion_sites_host_join", "sr_inversion_accept_site", "sr_inversion_scan_device_join",
+    "sr_compact_gfa", "sr_compact_stats",
 ]
 
 
@@ -223,6 +224,8 @@ def load():
     L.sr_inversion_scan_device_join.argtypes = [i32, C.POINTER(C.c_uint32), C.POINTER(u64), u64, u64, C.c_uint32, PP, PI32, PI32,
                                                 C.POINTER(C.POINTER(InvSiteC)), C.POINTER(C.POINTER(u64)), C.POINTER(PI32),
                                                 C.POINTER(u64), C.POINTER(u64)]
+    L.sr_compact_gfa.argtypes = [C.c_char_p, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.sr_compact_stats.argtypes = [C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

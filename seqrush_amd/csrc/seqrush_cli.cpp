@@ -76,7 +76,7 @@ static std::string rust_f64(double x) {
 
 static void usage() {
     fprintf(stderr, "usage: seqrush_mi355x -s in.fa [-o output.gfa] [-k 0] [-S 0,5,8,2,24,1] [--orientation-scores 0,1,1,1]\n"
-                    "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--device N]\n"
+                    "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--compact-on host|device] [--device N]\n"
                     "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
                     "       [--patch-inversions [--inversion-min-size N] [--inversion-join N]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
@@ -88,6 +88,7 @@ int main(int argc, char **argv) {
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
+    bool compact_dev = false;
     bool no_sort = false, no_compact = false, sort = false, iterative = false, verbose = false, patch_inv = false;
     unsigned long long inv_min = 0, inv_join = 0;
     bool inv_join_given = false;
@@ -118,6 +119,11 @@ int main(int argc, char **argv) {
         else if (a == "--aligner") aligner = val("--aligner");
         else if (a == "--no-sort") no_sort = true;
         else if (a == "--no-compact") no_compact = true;
+        else if (a == "--compact-on") {
+            const std::string w = val("--compact-on");
+            if (w != "host" && w != "device") { fprintf(stderr, "Error: --compact-on takes host or device\n"); return 1; }
+            compact_dev = w == "device";
+        }
         else if (a == "--sort") sort = true;
         else if (a == "--sort-seed") sp.seed = strtoull(val("--sort-seed"), nullptr, 10);
         else if (a == "--sgd-iter-max") sp.iter_max = strtoull(val("--sgd-iter-max"), nullptr, 10);
@@ -179,6 +185,7 @@ int main(int argc, char **argv) {
     if (!labels_in.empty() && (shard_count > 1 || !labels_out.empty())) { fprintf(stderr, "Error: --labels-in is the merge run: no --shard / --labels-out\n"); return 1; }
     if (aligner != "allwave" && aligner != "AllWave") { fprintf(stderr, "Error: aligner '%s' is out of scope; only 'allwave'\n", aligner.c_str()); return 1; }
     if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
+    if (compact_dev && no_compact) { fprintf(stderr, "Error: --compact-on device and --no-compact exclude each other\n"); return 1; }
     if (!no_sort && !sort) { fprintf(stderr, "Error: only --no-sort output is implemented by default; pass --sort for the Ygs layout; compaction runs unless --no-compact\n"); return 1; }
     std::vector<Seq> seqs;
     if (!load_sequences(sequences, seqs)) { fprintf(stderr, "Error: cannot read %s\n", sequences.c_str()); return 1; }
@@ -321,8 +328,16 @@ int main(int argc, char **argv) {
     char *gfa = nullptr;
     uint64_t nn = 0, ne = 0;
     sp.device = device;
-    if (sort ? sr_ctx_build_gfa_sorted(ctx, &set, no_compact ? 0 : 1, &sp, &gfa, &nn, &ne)
-             : sr_ctx_build_gfa_opts(ctx, &set, no_compact ? 0 : 1, &gfa, &nn, &ne)) return die();   // compact + renumber unless --no-compact
+    const int compact = no_compact ? 0 : (compact_dev ? 2 : 1);          // compact + renumber unless --no-compact
+    if (sort ? sr_ctx_build_gfa_sorted(ctx, &set, compact, &sp, &gfa, &nn, &ne)
+             : sr_ctx_build_gfa_opts(ctx, &set, compact, &gfa, &nn, &ne)) return die();
+    if (verbose && compact_dev) {
+        uint64_t cs[8] = {0};
+        sr_compact_stats(cs);
+        printf("Compaction on device: rounds=%llu host_rounds=%llu chains=%llu longest_list=%llu jumps=%llu compact_us=%llu copy_us=%llu\n",
+               (unsigned long long)cs[0], (unsigned long long)cs[1], (unsigned long long)cs[2], (unsigned long long)cs[3],
+               (unsigned long long)cs[4], (unsigned long long)cs[5], (unsigned long long)cs[6]);
+    }
     sr_ctx_destroy(ctx);
     std::ofstream o(output, std::ios::binary);
     o << gfa;

@@ -271,6 +271,8 @@ static bool compact_round(SrGraph &g) {
     return true;
 }
 
+bool sr_graph_compact_round(SrGraph &g) { return compact_round(g); }
+
 void sr_graph_compact(SrGraph &g) {                  // compact() ops:91-112
     while (compact_round(g)) {}
 }

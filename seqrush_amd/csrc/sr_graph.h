@@ -15,5 +15,6 @@ struct SrGraph {
 };
 
 void sr_graph_compact(SrGraph &g);                   // BidirectedGraph::compact, ops:91-112
+bool sr_graph_compact_round(SrGraph &g);             // one round of it: true when a chain was merged
 void sr_graph_renumber(SrGraph &g);                  // renumber_nodes_sequentially, ops:75-89
 char *sr_graph_format_gfa(const SrGraph &g, const char *const *names, uint64_t *n_nodes, uint64_t *n_edges);   // write_gfa, ops:880-925

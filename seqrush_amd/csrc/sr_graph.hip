@@ -169,6 +169,15 @@ static void gi_exclusive_scan(const uint32_t *in, unsigned long long n, uint32_t
     hipLaunchKernelGGL(gi_scan_apply, dim3((unsigned)ntiles), dim3(GI_BLOCK), 0, st, in, n, tile_sum, out);
 }
 
+// the same scan for other stages (sr_compact.hip): tile_sum has ceil(n / 1024) + 1 entries, *grand gets the total
+extern "C" int srk_scan_u32(const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *tile_sum, uint32_t *grand, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n >= 0xffffffffULL) return -1;
+    if (n == 0) return (int)hipMemsetAsync(grand, 0, sizeof(uint32_t), st);
+    gi_exclusive_scan(in, n, out, tile_sum, grand, st);
+    return (int)hipGetLastError();
+}
+
 // All device pointers; `first` has uf_size entries, hash table keys/vals have hcap (power of two) entries,
 // flag/nid/eslot/steps N entries, tile_sum ceil(N/1024)+1, counts[2] = {nodes, edges}.
 extern "C" int srk_graph_induce(const unsigned long long *labels, const uint8_t *bases, const uint8_t *islast,

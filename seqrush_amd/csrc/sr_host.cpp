@@ -21,6 +21,7 @@
 #include "sr_internal.h"
 #include "sr_graph.h"
 #include "sr_sort.h"
+#include "sr_compact.h"
 #include "sr_iter_rule.h"
 #include "sr_inv_rule.h"
 #include "sr_base_cone.h"
@@ -2594,8 +2595,9 @@ struct PairHash {
     }
 };
 
+// compact: 0 = none, 1 = sr_compact.cpp on the host, 2 = already compacted on the device (ctx_induce_graph)
 static char *finish_gfa(SrGraph &g, const sr_seqset *seqs, int compact, uint64_t *n_nodes, uint64_t *n_edges) {
-    if (compact) { sr_graph_compact(g); sr_graph_renumber(g); }     // src/bidirected_gfa_writer.rs:39-51
+    if (compact && compact != 2) { sr_graph_compact(g); sr_graph_renumber(g); }     // src/bidirected_gfa_writer.rs:39-51
     return sr_graph_format_gfa(g, seqs->names, n_nodes, n_edges);
 }
 
@@ -2604,6 +2606,7 @@ extern "C" int sr_build_gfa_opts(const sr_seqset *seqs, const uint64_t *labels, 
     if (!seqs || !labels || !gfa || !seqs->names) return fail(SR_ERR_INVALID, "null argument");
     const uint64_t N = seqs->offsets[seqs->n];
     if (N >= 0x7fffffffULL) return fail(SR_ERR_UNSUPPORTED, "graph induction supports < 2^31 bases");
+    if (compact == 2) return fail(SR_ERR_INVALID, "compact == 2 (on the device) needs a context: sr_ctx_build_gfa_opts");
     const uint64_t ufn = 2 * N + 2;
     std::vector<uint32_t> node_of(ufn, 0);
     SrGraph g;
@@ -2665,7 +2668,9 @@ extern "C" int sr_build_gfa_from_nodes(const sr_seqset *seqs, const uint64_t *no
 
 // graph induction on the device from the context's union-find (sr_graph.hip); same
 // text as sr_build_gfa() on the downloaded canonical labels.  which = 3 of sr_ctx_kernel_ms times it.
-static int ctx_induce_graph(sr_ctx *c, const sr_seqset *seqs, SrGraph &g) {
+// compact == 2: the induced arrays go straight into compaction on the same device and stream (sr_compact.hip); g is
+// then the compacted, renumbered graph and the induced one never reaches the host
+static int ctx_induce_graph(sr_ctx *c, const sr_seqset *seqs, SrGraph &g, int compact = 0) {
     if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");
     if (!seqs || !seqs->names) return fail(SR_ERR_INVALID, "null argument");
     const uint64_t N = seqs->offsets[seqs->n];
@@ -2704,6 +2709,11 @@ static int ctx_induce_graph(sr_ctx *c, const sr_seqset *seqs, SrGraph &g) {
     if ((r = sr_ctx_sync(c))) return r;
     uint32_t counts[2] = {0, 0};
     HIPCHK(hipMemcpy(counts, d_counts, 8, hipMemcpyDeviceToHost));
+    if (compact == 2) {
+        std::vector<uint64_t> poff(seqs->offsets, seqs->offsets + seqs->n + 1);
+        return srk_compact_induced(c->device, (void *)c->stream, d_steps, N, d_edges, counts[1], d_nbase, counts[0], poff.data(), seqs->n,
+                                   g, nullptr);
+    }
     std::vector<uint8_t> nbase(counts[0] ? counts[0] : 1);
     std::vector<unsigned long long> edges(counts[1] ? counts[1] : 1);
     g = SrGraph();
@@ -2723,7 +2733,7 @@ static int ctx_induce_graph(sr_ctx *c, const sr_seqset *seqs, SrGraph &g) {
 extern "C" int sr_ctx_build_gfa_opts(sr_ctx *c, const sr_seqset *seqs, int compact, char **gfa, uint64_t *n_nodes, uint64_t *n_edges) {
     if (!gfa) return fail(SR_ERR_INVALID, "null argument");
     SrGraph g;
-    int r = ctx_induce_graph(c, seqs, g);
+    int r = ctx_induce_graph(c, seqs, g, compact);
     if (r) return r;
     *gfa = finish_gfa(g, seqs, compact, n_nodes, n_edges);
     return SR_OK;
@@ -2734,9 +2744,9 @@ extern "C" int sr_ctx_build_gfa_sorted(sr_ctx *c, const sr_seqset *seqs, int com
                                        uint64_t *n_nodes, uint64_t *n_edges) {
     if (!p || !gfa) return fail(SR_ERR_INVALID, "null argument");
     SrGraph g;
-    int r = ctx_induce_graph(c, seqs, g);
+    int r = ctx_induce_graph(c, seqs, g, compact);
     if (r) return r;
-    if (compact) { sr_graph_compact(g); sr_graph_renumber(g); }
+    if (compact && compact != 2) { sr_graph_compact(g); sr_graph_renumber(g); }
     sr_sort_params prm = *p;
     if (prm.device >= 0) prm.device = c->device;
     if ((r = sr_graph_ygs(g, prm, prm.device >= 0 ? (void *)c->stream : nullptr))) return r;

@@ -185,6 +185,7 @@ int srk_graph_induce(const unsigned long long *labels, const uint8_t *bases, con
                      uint32_t *steps, uint8_t *node_base, unsigned long long *hkeys, uint32_t *hvals,
                      uint64_t hcap, uint32_t *eslot, unsigned long long *edges, uint32_t *tile_sum,
                      uint32_t *counts, int *error_flag, void *stream);
+int srk_scan_u32(const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *tile_sum, uint32_t *grand, void *stream);   // sr_graph.hip's exclusive scan
 const char *srk_source_digest(void);                                 // digest of the sources this library was built from (Makefile, scripts/src_digest.py)
 const char *srk_align_blk_build_tag(void);                         // name of the blocked kernel's build (scripts/build_variant.sh)
 int srk_align_blk_max_levels(void);                                // deepest block of the build (static LDS tables)

@@ -34,6 +34,7 @@ class Args:
     paf: Optional[str] = None               # -p: replay alignments from a PAF file instead of aligning
     output_alignments: Optional[str] = None  # --output-alignments
     no_compact: bool = False                # --no-compact (default: compact + renumber, bidirected_gfa_writer.rs:39-51)
+    compact_on: str = "host"                # added: --compact-on host|device: where compaction + renumbering run
     no_sort: bool = True                    # --no-sort: the unsorted graph
     sort: bool = False                      # added: --sort, the Ygs layout (the reference's default); wins over no_sort
     sort_seed: int = 9399220                # added: --sort-seed, seed of the counter-based SGD draws
@@ -369,17 +370,20 @@ class Context:
         self.seqset = seqset
         check(self.L.sr_ctx_load_paf(self._h, C.byref(seqset.c), C.byref(params.c), paf_path.encode()))
 
-    def build_gfa(self, compact: bool = False, sort: "Optional[SortParams]" = None):
+    def build_gfa(self, compact: bool = False, sort: "Optional[SortParams]" = None, compact_on: str = "host"):
         """graph induction on the device from this context's union-find (+ compaction and
         renumbering, src/bidirected_gfa_writer.rs:39-51) + GFA text;
         -> (gfa_text, n_nodes, n_edges), byte-identical to build_gfa(seqset, download_labels(), compact).
-        sort: SortParams -> the Ygs layout before the writer (src/bidirected_gfa_writer.rs:53-117)"""
+        sort: SortParams -> the Ygs layout before the writer (src/bidirected_gfa_writer.rs:53-117)
+        compact_on: "host" (sr_compact.cpp) or "device": compaction by tables on this context's device, straight from
+        the induced arrays (sr_compact.hip; the same bytes; compact_stats() afterwards)"""
+        mode = compact_mode(compact, compact_on)
         out = C.c_void_p(); nn = C.c_uint64(); ne = C.c_uint64()
         if sort is None:
-            check(self.L.sr_ctx_build_gfa_opts(self._h, C.byref(self.seqset.c), 1 if compact else 0, C.byref(out),
+            check(self.L.sr_ctx_build_gfa_opts(self._h, C.byref(self.seqset.c), mode, C.byref(out),
                                                C.byref(nn), C.byref(ne)))
         else:
-            check(self.L.sr_ctx_build_gfa_sorted(self._h, C.byref(self.seqset.c), 1 if compact else 0, C.byref(sort.c),
+            check(self.L.sr_ctx_build_gfa_sorted(self._h, C.byref(self.seqset.c), mode, C.byref(sort.c),
                                                  C.byref(out), C.byref(nn), C.byref(ne)))
         text = C.cast(out, C.c_char_p).value.decode()
         self.L.sr_free(out)
@@ -519,6 +523,40 @@ def sort_gfa(text: str, **params) -> str:
     res = C.cast(out, C.c_char_p).value.decode()
     L.sr_free(out)
     return res
+
+
+COMPACT_STATS = ("rounds", "host_rounds", "chains", "longest_list", "jumps", "compact_us", "copy_us", "reserved")
+
+
+def compact_mode(compact: bool, compact_on: str) -> int:
+    """the C ABI's `compact` argument: 0 none, 1 on the host, 2 on the context's device"""
+    if compact_on not in ("host", "device"):
+        raise SeqRushError(-1, f"compact_on must be 'host' or 'device', not {compact_on!r}")
+    if compact_on == "device" and not compact:
+        raise SeqRushError(-1, "--compact-on device and --no-compact exclude each other")
+    return 0 if not compact else (2 if compact_on == "device" else 1)
+
+
+def compact_gfa(text: str, device: int = -1, stats: Optional[dict] = None) -> str:
+    """compact() + renumbering of any GFA with S / L / P lines and numeric node ids -> GFA text.  device: -1 the greedy
+    host procedure (sr_compact.cpp), -2 the table formulation on the host, >= 0 the same in HIP on that device; all
+    three return the same bytes.  stats: a dict that receives COMPACT_STATS"""
+    L = _lib.load()
+    out = C.c_void_p(); nn = C.c_uint64(); ne = C.c_uint64()
+    st = (C.c_uint64 * 8)()
+    check(L.sr_compact_gfa(text.encode(), device, C.byref(out), C.byref(nn), C.byref(ne), st))
+    res = C.cast(out, C.c_char_p).value.decode()
+    L.sr_free(out)
+    if stats is not None:
+        stats.update(zip(COMPACT_STATS, (int(v) for v in st)))
+    return res
+
+
+def compact_stats() -> dict:
+    """COMPACT_STATS of this thread's last compaction by tables (compact_gfa, Context.build_gfa(compact_on="device"))"""
+    st = (C.c_uint64 * 8)()
+    check(_lib.load().sr_compact_stats(st))
+    return dict(zip(COMPACT_STATS, (int(v) for v in st)))
 
 
 def sgd_layout(text: str, **params) -> np.ndarray:
@@ -730,8 +768,14 @@ class SeqRush:
                                    "is not reproducible run to run, SURVEY 0.4); pass --sort for the Ygs layout; "
                                    "compaction runs unless --no-compact")
         sort = SortParams.from_args(args) if args.sort else None
-        # graph induction on the device, compaction on the host, Ygs: SGD on the device, groom + topological sort on the host
-        text, _, _ = self.ctx.build_gfa(compact=not args.no_compact, sort=sort)
+        # graph induction on the device, compaction on the host or (--compact-on device) on the device, Ygs: SGD on the
+        # device, groom + topological sort on the host
+        where = {"compact_on": "device"} if args.compact_on == "device" else {}     # (the default call is unchanged)
+        if args.compact_on not in ("host", "device"):
+            raise SeqRushError(-1, f"compact_on must be 'host' or 'device', not {args.compact_on!r}")
+        text, _, _ = self.ctx.build_gfa(compact=not args.no_compact, sort=sort, **where)
+        if args.verbose and args.compact_on == "device":
+            print("Compaction on device: " + " ".join(f"{k}={v}" for k, v in list(compact_stats().items())[:7]))
         with open(args.output, "w") as fh:
             fh.write(text)
 
