@@ -386,6 +386,15 @@ int sr_inversion_scan_device(int device, const uint32_t *ops, const uint64_t *ci
 int sr_inversion_scan_device_join(int device, const uint32_t *ops, const uint64_t *cigar_off, uint64_t n, uint64_t min_size,
                                   uint32_t join_below, const sr_params *pen, const int32_t *score, const int32_t *max_score,
                                   sr_inv_site **sites, uint64_t **owner, int32_t **cost, uint64_t *count, uint64_t stats[4]);
+/* tests: the stages of the tree: selection on `device` for `seqs` and k-mer size `kmer` (1..32): sketch = n rows of 1000
+ * u64, the first sketch_n[i] of row i ascending, the rest of the row still the fill value 2^64-1; shared / denom = n*n u32
+ * (diagonal 0).  All four sr_free. */
+int sr_sketch_device(int device, const sr_seqset *seqs, uint32_t kmer, uint64_t **sketch, uint32_t **sketch_n,
+                     uint32_t **shared, uint32_t **denom);
+/* tests: sr_knn_select_kernel on given n*n shared / denom matrices: sel[i*n+j] bit 0 = j among i's k_nearest, bit 1 = among
+ * its k_farthest (both clamped to n like the load path does).  sr_free. */
+int sr_knn_select_device(int device, const uint32_t *shared, const uint32_t *denom, uint32_t n, uint32_t k_nearest,
+                         uint32_t k_farthest, uint8_t **sel);
 
 /* -------- consumer (A9): graph induction + GFA, host C++ -----------------
  * build_bidirected_graph_with_options (bidirected_builder.rs:17-289) +

@@ -647,7 +647,11 @@ int sro_sparsified_pairs(const sro_seqrush *s, const sro_sparsification *sp, uin
                     const uint64_t r = (uint64_t)sh[i * n + (uint64_t)best] * dn[i * n + j];
                     if (nearest ? (l > r) : (l < r)) best = (int64_t)j;
                 }
-                if (best < 0) break;
+                if (best < 0) {                         /* row exhausted: the farthest passes still run */
+                    if (!nearest) break;
+                    pass = kn - 1;
+                    continue;
+                }
                 row[best] |= nearest ? 1 : 2;
             }
         }

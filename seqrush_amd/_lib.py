@@ -35,6 +35,7 @@ EXPORTS = [
     "sr_inversion_scan_device",
     "sr_ctx_inversion_join_stats", "sr_inversion_sites_host_join", "sr_inversion_accept_site", "sr_inversion_scan_device_join",
     "sr_compact_gfa", "sr_compact_stats",
+    "sr_sketch_device", "sr_knn_select_device",
 ]
 
 
@@ -224,6 +225,10 @@ def load():
     L.sr_inversion_scan_device_join.argtypes = [i32, C.POINTER(C.c_uint32), C.POINTER(u64), u64, u64, C.c_uint32, PP, PI32, PI32,
                                                 C.POINTER(C.POINTER(InvSiteC)), C.POINTER(C.POINTER(u64)), C.POINTER(PI32),
                                                 C.POINTER(u64), C.POINTER(u64)]
+    PU32P = C.POINTER(C.POINTER(C.c_uint32))
+    L.sr_sketch_device.argtypes = [i32, PS, C.c_uint32, C.POINTER(C.POINTER(u64)), PU32P, PU32P, PU32P]
+    L.sr_knn_select_device.argtypes = [i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.POINTER(C.POINTER(C.c_uint8))]
     L.sr_compact_gfa.argtypes = [C.c_char_p, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.sr_compact_stats.argtypes = [C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None

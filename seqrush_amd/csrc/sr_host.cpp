@@ -692,33 +692,66 @@ static int upload_sequences(sr_ctx *c, const sr_seqset *seqs, const PackedSeqs &
     return SR_OK;
 }
 
-// `tree:` sparsification: bottom-1000 sketches, pairwise similarities and the k-nearest / k-farthest selection on the device
-static int tree_selection(sr_ctx *c, const sr_params *p, const SeqDev &sd, std::vector<uint8_t> &sel) {
-    const uint32_t n = c->n;
-    const int S = 1000;
-    std::vector<uint32_t> npad(n);
-    uint64_t stride = 2;
-    for (uint32_t i = 0; i < n; i++) { uint32_t v = 2; while (v < c->len[i]) v <<= 1; npad[i] = v; stride = std::max<uint64_t>(stride, v); }
+// `tree:` sparsification: bottom-1000 sketches, pairwise similarities and the k-nearest / k-farthest selection on the device.
+// ONE routine for the load path and the tests: entries (sr_sketch_device, sr_knn_select_device): padded lengths, stride,
+// allocations, fills and launches are here and nowhere else.
+//   h_shared / h_denom given: the matrices come from the host and the sketch / Jaccard stages do not run (len, d_* unused);
+//   sel == nullptr: the selection does not run;  tap: copies of the intermediates for the tests
+#define SR_SKETCH_SIZE 1000
+struct TreeTap { std::vector<unsigned long long> *sketch = nullptr; std::vector<uint32_t> *sketch_n = nullptr, *shared = nullptr, *denom = nullptr; };
+static int tree_stages(hipStream_t stream, uint32_t n, const uint32_t *len, const uint8_t *d_bases, const uint64_t *d_goff,
+                       const uint32_t *d_len, uint32_t kmer, const uint32_t *h_shared, const uint32_t *h_denom,
+                       uint32_t k_nearest, uint32_t k_farthest, std::vector<uint8_t> *sel, const TreeTap *tap) {
+    const int S = SR_SKETCH_SIZE;
+    const size_t nn = (size_t)n * n;
     struct Tmp { std::vector<void *> v; ~Tmp() { for (void *q : v) (void)hipFree(q); } } tmp;
     auto talloc = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr; tmp.v.push_back(q); return q; };
-    unsigned long long *d_scr = (unsigned long long *)talloc((size_t)n * stride * 8);
-    unsigned long long *d_sk = (unsigned long long *)talloc((size_t)n * S * 8);
-    uint32_t *d_skn = (uint32_t *)talloc((size_t)n * 4), *d_npad = (uint32_t *)talloc((size_t)n * 4);
-    uint32_t *d_sh = (uint32_t *)talloc((size_t)n * n * 4), *d_dn = (uint32_t *)talloc((size_t)n * n * 4);
-    uint8_t *d_sel = (uint8_t *)talloc((size_t)n * n);
-    if (!d_scr || !d_sk || !d_skn || !d_npad || !d_sh || !d_dn || !d_sel) return fail(SR_ERR_NOMEM, "not enough device memory for the k-mer sketches");
-    HIPCHK(hipMemcpyAsync(d_npad, npad.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(d_sel, 0, (size_t)n * n, c->stream));
-    HIPCHK(hipMemsetAsync(d_sh, 0, (size_t)n * n * 4, c->stream));
-    HIPCHK(hipMemsetAsync(d_dn, 0, (size_t)n * n * 4, c->stream));
-    if (srk_sketch(c->d_bases, sd.goff, sd.len, n, (int)p->tree_kmer, S, d_scr, stride, d_npad, d_sk, d_skn, c->stream) ||
-        srk_jaccard(d_sk, d_skn, n, S, d_sh, d_dn, c->stream) ||
-        srk_knn_select(d_sh, d_dn, n, (int)std::min<uint32_t>(p->tree_k_nearest, n), (int)std::min<uint32_t>(p->tree_k_farthest, n), d_sel, c->stream))
-        return fail(SR_ERR_HIP, "sketch kernel launch failed");
-    sel.resize((size_t)n * n);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(sel.data(), d_sel, (size_t)n * n, hipMemcpyDeviceToHost));
+    uint32_t *d_sh = (uint32_t *)talloc(nn * 4), *d_dn = (uint32_t *)talloc(nn * 4);
+    if (!d_sh || !d_dn) return fail(SR_ERR_NOMEM, "not enough device memory for the k-mer sketches");
+    unsigned long long *d_sk = nullptr;
+    uint32_t *d_skn = nullptr;
+    std::vector<uint32_t> npad;                    // (read by an asynchronous copy: lives until the synchronize below)
+    if (h_shared) {
+        HIPCHK(hipMemcpyAsync(d_sh, h_shared, nn * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_dn, h_denom, nn * 4, hipMemcpyHostToDevice, stream));
+    } else {
+        npad.resize(n);
+        uint64_t stride = 2;
+        for (uint32_t i = 0; i < n; i++) { uint32_t v = 2; while (v < len[i]) v <<= 1; npad[i] = v; stride = std::max<uint64_t>(stride, v); }
+        unsigned long long *d_scr = (unsigned long long *)talloc((size_t)n * stride * 8);
+        d_sk = (unsigned long long *)talloc((size_t)n * S * 8);
+        d_skn = (uint32_t *)talloc((size_t)n * 4);
+        uint32_t *d_npad = (uint32_t *)talloc((size_t)n * 4);
+        if (!d_scr || !d_sk || !d_skn || !d_npad) return fail(SR_ERR_NOMEM, "not enough device memory for the k-mer sketches");
+        HIPCHK(hipMemcpyAsync(d_npad, npad.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(d_sk, 0xFF, (size_t)n * S * 8, stream));     // (a write past a row's count shows in sr_sketch_device)
+        HIPCHK(hipMemsetAsync(d_sh, 0, nn * 4, stream));
+        HIPCHK(hipMemsetAsync(d_dn, 0, nn * 4, stream));
+        if (srk_sketch(d_bases, d_goff, d_len, n, (int)kmer, S, d_scr, stride, d_npad, d_sk, d_skn, stream) ||
+            srk_jaccard(d_sk, d_skn, n, S, d_sh, d_dn, stream))
+            return fail(SR_ERR_HIP, "sketch kernel launch failed");
+    }
+    uint8_t *d_sel = nullptr;
+    if (sel) {
+        if (!(d_sel = (uint8_t *)talloc(nn))) return fail(SR_ERR_NOMEM, "not enough device memory for the k-mer sketches");
+        HIPCHK(hipMemsetAsync(d_sel, 0, nn, stream));
+        if (srk_knn_select(d_sh, d_dn, n, (int)std::min<uint32_t>(k_nearest, n), (int)std::min<uint32_t>(k_farthest, n), d_sel, stream))
+            return fail(SR_ERR_HIP, "sketch kernel launch failed");
+        sel->resize(nn);
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    if (sel) HIPCHK(hipMemcpy(sel->data(), d_sel, nn, hipMemcpyDeviceToHost));
+    if (tap) {
+        if (tap->sketch && d_sk) { tap->sketch->resize((size_t)n * S); HIPCHK(hipMemcpy(tap->sketch->data(), d_sk, (size_t)n * S * 8, hipMemcpyDeviceToHost)); }
+        if (tap->sketch_n && d_skn) { tap->sketch_n->resize(n); HIPCHK(hipMemcpy(tap->sketch_n->data(), d_skn, (size_t)n * 4, hipMemcpyDeviceToHost)); }
+        if (tap->shared) { tap->shared->resize(nn); HIPCHK(hipMemcpy(tap->shared->data(), d_sh, nn * 4, hipMemcpyDeviceToHost)); }
+        if (tap->denom) { tap->denom->resize(nn); HIPCHK(hipMemcpy(tap->denom->data(), d_dn, nn * 4, hipMemcpyDeviceToHost)); }
+    }
     return SR_OK;
+}
+static int tree_selection(sr_ctx *c, const sr_params *p, const SeqDev &sd, std::vector<uint8_t> &sel) {
+    return tree_stages(c->stream, c->n, c->len.data(), c->d_bases, sd.goff, sd.len, p->tree_kmer, nullptr, nullptr,
+                       p->tree_k_nearest, p->tree_k_farthest, &sel, nullptr);
 }
 
 // ordered pair list of this rank + what follows from it: DP cells, worst-case CIGAR reserve per pair, divergence thresholds
@@ -2256,6 +2289,73 @@ extern "C" int sr_inversion_scan_device_join(int device, const uint32_t *ops, co
     if (!*cost) return fail(SR_ERR_NOMEM, "out of memory");
     for (size_t j = 0; j < jobs.size(); j++) (*cost)[j] = jobs[j].cost;
     return SR_OK;
+}
+
+// tests: the stages of `tree:` selection (tree_stages, the routine the load path runs)
+static int test_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SR_ERR_NO_DEVICE, "no HIP device available (seqrush_amd has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(SR_ERR_INVALID, "device ordinal out of range");
+    HIPCHK(hipSetDevice(device));
+    return SR_OK;
+}
+template <class T>
+static int to_malloc(const std::vector<T> &v, T **out) {
+    *out = (T *)malloc((v.empty() ? 1 : v.size()) * sizeof(T));
+    if (!*out) return fail(SR_ERR_NOMEM, "out of memory");
+    if (!v.empty()) memcpy(*out, v.data(), v.size() * sizeof(T));
+    return SR_OK;
+}
+
+extern "C" int sr_sketch_device(int device, const sr_seqset *seqs, uint32_t kmer, uint64_t **sketch, uint32_t **sketch_n,
+                                uint32_t **shared, uint32_t **denom) {
+    if (!seqs || !seqs->bases || !seqs->offsets || !sketch || !sketch_n || !shared || !denom) return fail(SR_ERR_INVALID, "null argument");
+    if (seqs->n == 0 || (uint64_t)seqs->n * seqs->n > 0xffffffffULL) return fail(SR_ERR_INVALID, "bad sequence count");
+    if (kmer < 1 || kmer > 32) return fail(SR_ERR_UNSUPPORTED, "tree sparsification: k-mer size must be in 1..32 on the device");
+    const uint32_t n = seqs->n;
+    std::vector<uint32_t> len(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t L = seqs->offsets[i + 1] - seqs->offsets[i];
+        if (L == 0 || seqs->offsets[i + 1] < seqs->offsets[i]) return fail(SR_ERR_EMPTY_SEQ, "Empty sequences are not allowed");
+        if (L > 0x7fff0000ULL) return fail(SR_ERR_UNSUPPORTED, "sequence too long");
+        len[i] = (uint32_t)L;
+    }
+    int r;
+    if ((r = test_device(device))) return r;
+    struct Tmp { std::vector<void *> v; ~Tmp() { for (void *q : v) (void)hipFree(q); } } tmp;
+    auto up = [&](const void *src, size_t bytes) -> void * {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+        tmp.v.push_back(q);
+        if (hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return q;
+    };
+    const uint8_t *d_bases = (const uint8_t *)up(seqs->bases + seqs->offsets[0], seqs->offsets[n] - seqs->offsets[0]);
+    std::vector<uint64_t> goff(n);
+    for (uint32_t i = 0; i < n; i++) goff[i] = seqs->offsets[i] - seqs->offsets[0];
+    const uint64_t *d_goff = (const uint64_t *)up(goff.data(), (size_t)n * 8);
+    const uint32_t *d_len = (const uint32_t *)up(len.data(), (size_t)n * 4);
+    if (!d_bases || !d_goff || !d_len) return fail(SR_ERR_NOMEM, "device allocation failed");
+    std::vector<unsigned long long> sk;
+    std::vector<uint32_t> skn, sh, dn;
+    TreeTap tap;
+    tap.sketch = &sk; tap.sketch_n = &skn; tap.shared = &sh; tap.denom = &dn;
+    if ((r = tree_stages(nullptr, n, len.data(), d_bases, d_goff, d_len, kmer, nullptr, nullptr, 0, 0, nullptr, &tap))) return r;
+    unsigned long long *skp = nullptr;
+    if ((r = to_malloc(sk, &skp)) || (r = to_malloc(skn, sketch_n)) || (r = to_malloc(sh, shared)) || (r = to_malloc(dn, denom))) return r;
+    *sketch = (uint64_t *)skp;
+    return SR_OK;
+}
+
+extern "C" int sr_knn_select_device(int device, const uint32_t *shared, const uint32_t *denom, uint32_t n, uint32_t k_nearest,
+                                    uint32_t k_farthest, uint8_t **sel) {
+    if (!shared || !denom || !sel) return fail(SR_ERR_INVALID, "null argument");
+    if (n == 0 || (uint64_t)n * n > 0xffffffffULL) return fail(SR_ERR_INVALID, "bad sequence count");
+    int r;
+    if ((r = test_device(device))) return r;
+    std::vector<uint8_t> s;
+    if ((r = tree_stages(nullptr, n, nullptr, nullptr, nullptr, nullptr, 0, shared, denom, k_nearest, k_farthest, &s, nullptr))) return r;
+    return to_malloc(s, sel);
 }
 
 // ------------------------------------------------------------------ PAF input (seam 3, `seqrush -p`)

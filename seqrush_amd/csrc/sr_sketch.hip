@@ -122,7 +122,7 @@ __global__ void sr_jaccard_kernel(const unsigned long long *sketch, const uint32
     }
 }
 
-// one thread per row: kn nearest then kf farthest neighbours (each as k selection passes), sel[i][j] = 1
+// one thread per row: kn nearest then kf farthest neighbours (each as k selection passes): sel[i][j] bit 0 / bit 1
 __global__ void sr_knn_select_kernel(const uint32_t *shared, const uint32_t *denom, uint32_t n, int kn, int kf, uint8_t *sel) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -137,7 +137,11 @@ __global__ void sr_knn_select_kernel(const uint32_t *shared, const uint32_t *den
             const unsigned long long l = (unsigned long long)S[j] * D[best], r = (unsigned long long)S[best] * D[j];
             if (nearest ? (l > r) : (l < r)) best = (int)j;
         }
-        if (best < 0) break;
+        if (best < 0) {                                     // row exhausted (kn or kf > n - 1)
+            if (!nearest) break;
+            pass = kn - 1;                                  // no more nearest: the farthest passes still run
+            continue;
+        }
         row[best] |= nearest ? 1 : 2;
     }
 }

@@ -996,6 +996,38 @@ def inversion_scan_device(cigars, min_size: int, device: int = 0):
     return out
 
 
+def _take(L, p, shape, dtype):
+    """copy a malloc'ed result array into numpy and sr_free it"""
+    out = np.ctypeslib.as_array(p, shape=(max(1, int(np.prod(shape))),))[: int(np.prod(shape))].astype(dtype, copy=True).reshape(shape)
+    L.sr_free(C.cast(p, C.c_void_p))
+    return out
+
+
+def sketch_device(seqset: SeqSet, kmer: int, device: int = 0):
+    """tests: the sketch and Jaccard stages of `tree:` selection as the load path runs them -> (sketch (n, 1000) u64 with the
+    unwritten entries still 2^64-1, sketch_n (n,) u32, shared (n, n) u32, denom (n, n) u32)"""
+    L = _lib.load()
+    sk = C.POINTER(C.c_uint64)(); skn = C.POINTER(C.c_uint32)(); sh = C.POINTER(C.c_uint32)(); dn = C.POINTER(C.c_uint32)()
+    check(L.sr_sketch_device(device, C.byref(seqset.c), int(kmer), C.byref(sk), C.byref(skn), C.byref(sh), C.byref(dn)))
+    n = seqset.n
+    return (_take(L, sk, (n, 1000), np.uint64), _take(L, skn, (n,), np.uint32), _take(L, sh, (n, n), np.uint32),
+            _take(L, dn, (n, n), np.uint32))
+
+
+def knn_select_device(shared, denom, k_nearest: int, k_farthest: int, device: int = 0) -> np.ndarray:
+    """tests: the selection stage on given (n, n) shared / denom matrices -> sel (n, n) u8, bit 0 nearest, bit 1 farthest"""
+    L = _lib.load()
+    sh = np.ascontiguousarray(shared, dtype=np.uint32); dn = np.ascontiguousarray(denom, dtype=np.uint32)
+    n = sh.shape[0]
+    if sh.shape != (n, n) or dn.shape != (n, n):
+        raise ValueError("shared / denom must be square and of one shape")
+    p = C.POINTER(C.c_uint8)()
+    u32p = C.POINTER(C.c_uint32)
+    check(L.sr_knn_select_device(device, sh.ctypes.data_as(u32p), dn.ctypes.data_as(u32p), n, int(k_nearest), int(k_farthest),
+                                 C.byref(p)))
+    return _take(L, p, (n, n), np.uint8)
+
+
 def rust_f64(x: float) -> str:
     """an f64 the way Rust's Display prints it: shortest round-trip digits, never an exponent, no '.0' on integers"""
     import decimal
