@@ -473,6 +473,38 @@ int sr_compact_gfa(const char *gfa_in, int device, char **gfa_out, uint64_t *n_n
 /* stats of the calling thread's last compaction by tables (sr_compact_gfa, or a context build with compact == 2) */
 int sr_compact_stats(uint64_t stats[8]);
 
+/* -------- graph statistics (`--stats FILE`) ------------------------------------------------
+ * Exact integer statistics of any GFA with S / L / P lines and numeric node ids, as the parser of sr_sort_gfa reads it:
+ * nodes are 1..V in ascending id order, identical L lines count once.  The columns of `odgi stats -S`, per-node depth and
+ * path count, base pairs and nodes by path count, pairwise shared base pairs of paths (`odgi similarity`), the layout error
+ * of src/bin/measure_layout_quality.rs:100-210 per path, self loops, tips and weakly connected components.
+ * device >= 0: HIP kernels on that device (sr_stats.hip); SR_STATS_DEVICE_HOST: the same tables in plain loops on the host.
+ * Both give the same integers.  More than 4096 paths, 2^30 nodes or 2^31 steps, edges or bases: SR_ERR_UNSUPPORTED.
+ * An empty graph gives zeros.  Arrays of the result (index v - 1 for node v, c for c paths, i * paths + j for a pair):
+ * the sum of squared errors is kept split as e = a 2^16 + b -> sums of a^2, a b, b^2, and is
+ * sq[0] 2^32 + sq[1] 2^17 + sq[2] in 128 bits. */
+#define SR_STATS_DEVICE_HOST (-1)
+typedef struct {
+    uint64_t length, nodes, edges, paths, steps;        /* odgi stats -S */
+    uint64_t rev_steps, depth_bp;                       /* steps on the reverse strand; sum of depth * length */
+    uint64_t self_loops, tips, components;
+    uint32_t *depth, *paths_on;                         /* [nodes] */
+    uint64_t *bp_by_paths, *nodes_by_paths;             /* [paths + 1] */
+    uint64_t *shared;                                   /* [paths * paths], symmetric */
+    uint64_t *path_pairs, *path_abs, *path_len;         /* [paths]: step pairs, sum e, sum of the first node's length */
+    uint64_t *path_sq;                                  /* [paths * 3]: the three parts of sum e^2 */
+    uint64_t total_pairs, total_abs, total_len, total_sq[3];   /* over every path with at least 2 steps */
+    uint64_t stats_us;                                  /* the stage: hipEvents on a device, host clock for the twin */
+    uint64_t kernel_us[5];                              /* steps, nodes, similarity, layout, topology */
+} sr_graph_stats;
+int sr_graph_stats_gfa(const char *gfa_in, int device, sr_graph_stats **out);
+void sr_graph_stats_free(sr_graph_stats *s);
+/* TSV report of a result (names: one per path, NULL = path indices); the only place where a float is formed, so every
+ * front end writes the same bytes.  *text is malloc'ed (sr_free). */
+int sr_graph_stats_report(const sr_graph_stats *s, const char *const *names, char **text);
+/* tests: the split sum of squares over n values below 2^32 on the host */
+int sr_stats_sq_sums_host(const uint64_t *e, uint64_t n, uint64_t out[3]);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

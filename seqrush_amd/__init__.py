@@ -9,9 +9,10 @@ reference's interfaces for that path (``Aligner`` trait, ``SeqRush`` /
 from .aligner import (AlignmentSequence, AlignmentRecord, Aligner, AllwaveAligner,  # noqa: F401
                       AlignerBackend, create_aligner)
 from .seqrush import (Args, Sequence, SeqRush, load_sequences, run_seqrush,  # noqa: F401
-                      AlignmentScores, SeqSet, Params, Context, build_gfa)
+                      AlignmentScores, SeqSet, Params, Context, build_gfa, graph_stats, graph_stats_report)
 from ._lib import SeqRushError  # noqa: F401
 
 __all__ = ["AlignmentSequence", "AlignmentRecord", "Aligner", "AllwaveAligner", "AlignerBackend",
            "create_aligner", "Args", "Sequence", "SeqRush", "load_sequences", "run_seqrush",
-           "AlignmentScores", "SeqSet", "Params", "Context", "build_gfa", "SeqRushError"]
+           "AlignmentScores", "SeqSet", "Params", "Context", "build_gfa", "SeqRushError", "graph_stats",
+           "graph_stats_report"]

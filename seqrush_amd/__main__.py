@@ -41,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--inversion-join", type=int, default=0,
                     help="with --patch-inversions: join gaps across match islands shorter than N and accept a patch against "
                          "what the main alignment paid for the gap (0 = off; N <= -k is the sensible range)")
+    ap.add_argument("--stats", default=None, metavar="FILE",
+                    help="write the statistics report of the final GFA (summary, depth, path similarity, layout error) to FILE")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -84,7 +86,7 @@ def main(argv=None):
                 skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
                 aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative,
                 patch_inversions=ns.patch_inversions, inversion_min_size=ns.inversion_min_size,
-                inversion_join=ns.inversion_join)
+                inversion_join=ns.inversion_join, stats=ns.stats)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

@@ -36,6 +36,7 @@ EXPORTS = [
     "sr_ctx_inversion_join_stats", "sr_inversion_sites_host_join", "sr_inversion_accept_site", "sr_inversion_scan_device_join",
     "sr_compact_gfa", "sr_compact_stats",
     "sr_sketch_device", "sr_knn_select_device",
+    "sr_graph_stats_gfa", "sr_graph_stats_free", "sr_graph_stats_report", "sr_stats_sq_sums_host",
 ]
 
 
@@ -103,6 +104,20 @@ class InvJobC(C.Structure):
 class InvSiteC(C.Structure):
     _fields_ = [("query_start", C.c_uint64), ("query_end", C.c_uint64), ("target_start", C.c_uint64),
                 ("target_end", C.c_uint64), ("kind", C.c_int32), ("candidate", C.c_int32)]
+
+
+class GraphStatsC(C.Structure):
+    """sr_graph_stats (include/seqrush_amd.h, graph statistics)"""
+    _fields_ = [("length", C.c_uint64), ("nodes", C.c_uint64), ("edges", C.c_uint64), ("paths", C.c_uint64), ("steps", C.c_uint64),
+                ("rev_steps", C.c_uint64), ("depth_bp", C.c_uint64),
+                ("self_loops", C.c_uint64), ("tips", C.c_uint64), ("components", C.c_uint64),
+                ("depth", C.POINTER(C.c_uint32)), ("paths_on", C.POINTER(C.c_uint32)),
+                ("bp_by_paths", C.POINTER(C.c_uint64)), ("nodes_by_paths", C.POINTER(C.c_uint64)),
+                ("shared", C.POINTER(C.c_uint64)),
+                ("path_pairs", C.POINTER(C.c_uint64)), ("path_abs", C.POINTER(C.c_uint64)), ("path_len", C.POINTER(C.c_uint64)),
+                ("path_sq", C.POINTER(C.c_uint64)),
+                ("total_pairs", C.c_uint64), ("total_abs", C.c_uint64), ("total_len", C.c_uint64), ("total_sq", C.c_uint64 * 3),
+                ("stats_us", C.c_uint64), ("kernel_us", C.c_uint64 * 5)]
 
 
 class AlignmentsC(C.Structure):
@@ -231,6 +246,11 @@ def load():
                                        C.POINTER(C.POINTER(C.c_uint8))]
     L.sr_compact_gfa.argtypes = [C.c_char_p, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.sr_compact_stats.argtypes = [C.POINTER(u64)]
+    PGS = C.POINTER(GraphStatsC)
+    L.sr_graph_stats_gfa.argtypes = [C.c_char_p, i32, C.POINTER(PGS)]
+    L.sr_graph_stats_free.argtypes = [PGS]; L.sr_graph_stats_free.restype = None
+    L.sr_graph_stats_report.argtypes = [PGS, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.sr_stats_sq_sums_host.argtypes = [C.POINTER(u64), u64, C.POINTER(u64)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

@@ -78,13 +78,13 @@ static void usage() {
     fprintf(stderr, "usage: seqrush_mi355x -s in.fa [-o output.gfa] [-k 0] [-S 0,5,8,2,24,1] [--orientation-scores 0,1,1,1]\n"
                     "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--compact-on host|device] [--device N]\n"
                     "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
-                    "       [--patch-inversions [--inversion-min-size N] [--inversion-join N]]\n"
+                    "       [--patch-inversions [--inversion-min-size N] [--inversion-join N]] [--stats report.tsv]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave";
+                aligner = "allwave", stats_out;
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
@@ -136,6 +136,7 @@ int main(int argc, char **argv) {
         else if (a == "--labels-in") labels_in.push_back(val("--labels-in"));
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--iterative") iterative = true;
+        else if (a == "--stats") stats_out = val("--stats");
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
             const char *v = val("--inversion-min-size");
@@ -341,6 +342,34 @@ int main(int argc, char **argv) {
     sr_ctx_destroy(ctx);
     std::ofstream o(output, std::ios::binary);
     o << gfa;
+    if (!stats_out.empty()) {                                // the report of the text just written
+        std::vector<std::string> pnames;                     // names of the P lines, as the library's parser reads them
+        for (const char *q = gfa; *q;) {
+            const char *eol = strchr(q, '\n');
+            if (!eol) eol = q + strlen(q);
+            if (*q == 'P' && q + 2 < eol && q[1] == '\t') {
+                const char *b = q + 2, *e = (const char *)memchr(b, '\t', (size_t)(eol - b));
+                if (e) pnames.emplace_back(b, e);
+            }
+            q = *eol ? eol + 1 : eol;
+        }
+        std::vector<const char *> pn;
+        for (const auto &n : pnames) pn.push_back(n.c_str());
+        sr_graph_stats *gs = nullptr;
+        char *report = nullptr;
+        if (sr_graph_stats_gfa(gfa, device, &gs)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_free(gfa); return 1; }
+        if (pn.size() != gs->paths || sr_graph_stats_report(gs, pn.data(), &report)) {
+            fprintf(stderr, "Error: %s\n", pn.size() != gs->paths ? "statistics: path names do not match the paths" : sr_last_error());
+            sr_graph_stats_free(gs); sr_free(gfa);
+            return 1;
+        }
+        std::ofstream so(stats_out, std::ios::binary);
+        so << report;
+        sr_free(report);
+        printf("Statistics written to %s\n", stats_out.c_str());
+        if (verbose) printf("Statistics stage: %llu us on device %d\n", (unsigned long long)gs->stats_us, device);
+        sr_graph_stats_free(gs);
+    }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());
     return 0;

@@ -40,5 +40,8 @@ int srk_sgd_device(const SgdProblem &p, int device, void *stream, std::vector<do
 int sr_graph_ygs(SrGraph &g, const sr_sort_params &prm, void *stream);
 // GFA text with S / L / P lines -> SrGraph + path names (numeric node ids)
 int sr_graph_parse_gfa(const char *text, SrGraph &g, std::vector<std::string> &names);
+// the statistics stage on a parsed graph (sr_stats.hip): device >= 0 on that HIP device and `stream` (null: a stream of its
+// own), -1 the host twin; *out as sr_graph_stats_gfa returns it
+int sr_graph_stats_run(const SrGraph &g, int device, void *stream, sr_graph_stats **out);
 int sr_fail(int code, const std::string &msg);     // sr_host.cpp: sets sr_last_error()
 void sr_sort_note_write_ms(double ms);              // slot [3] of sr_sort_stats(), also added to the stage's wall time [9]

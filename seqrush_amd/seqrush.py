@@ -13,8 +13,8 @@ from typing import List, Optional, Sequence as Seq
 import numpy as np
 
 from . import _lib
-from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, check,
-                   SeqRushError)
+from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
+                   check, SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -52,6 +52,7 @@ class Args:
     patch_inversions: bool = False          # added: --patch-inversions, realign large two-sided CIGAR gaps on the other strand
     inversion_min_size: int = 0             # added: --inversion-min-size N (0 = 2 * min_match_length)
     inversion_join: int = 0                 # added: --inversion-join J: join gaps across match islands shorter than J (0 = off)
+    stats: Optional[str] = None             # added: --stats FILE: the statistics report of the final GFA
 
 
 @dataclasses.dataclass
@@ -559,6 +560,99 @@ def compact_stats() -> dict:
     return dict(zip(COMPACT_STATS, (int(v) for v in st)))
 
 
+SR_STATS_DEVICE_HOST = -1
+STATS_KERNELS = ("steps", "nodes", "similarity", "layout", "topology")
+
+
+class _GraphStats:
+    """an owned sr_graph_stats"""
+
+    def __init__(self, text: str, device: int):
+        self.L = _lib.load()
+        self.p = C.POINTER(GraphStatsC)()
+        check(self.L.sr_graph_stats_gfa(text.encode(), int(device), C.byref(self.p)))
+
+    def close(self):
+        if self.p:
+            self.L.sr_graph_stats_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def as_dict(self) -> dict:
+        s = self.p.contents
+        V, P = int(s.nodes), int(s.paths)
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].astype(dt, copy=True)
+
+        def sq(parts):
+            return (int(parts[0]) << 32) + (int(parts[1]) << 17) + int(parts[2])
+        d = {k: int(getattr(s, k)) for k in ("length", "nodes", "edges", "paths", "steps", "rev_steps", "depth_bp", "self_loops",
+                                             "tips", "components", "total_pairs", "total_abs", "total_len", "stats_us")}
+        d["depth"], d["paths_on"] = arr(s.depth, V, np.uint32), arr(s.paths_on, V, np.uint32)
+        d["bp_by_paths"], d["nodes_by_paths"] = arr(s.bp_by_paths, P + 1, np.uint64), arr(s.nodes_by_paths, P + 1, np.uint64)
+        d["shared"] = arr(s.shared, P * P, np.uint64).reshape(P, P)
+        d["path_pairs"], d["path_abs"], d["path_len"] = (arr(q, P, np.uint64) for q in (s.path_pairs, s.path_abs, s.path_len))
+        d["path_sq_parts"] = arr(s.path_sq, 3 * P, np.uint64).reshape(P, 3)
+        d["path_sq"] = [sq(row) for row in d["path_sq_parts"]]
+        d["total_sq_parts"] = [int(v) for v in s.total_sq]
+        d["total_sq"] = sq(s.total_sq)
+        d["kernel_us"] = dict(zip(STATS_KERNELS, (int(v) for v in s.kernel_us)))
+        return d
+
+    def report(self, names) -> str:
+        arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        out = C.c_void_p()
+        check(self.L.sr_graph_stats_report(self.p, C.cast(arr, C.POINTER(C.c_char_p)), C.byref(out)))
+        res = C.cast(out, C.c_char_p).value.decode()
+        self.L.sr_free(out)
+        return res
+
+
+def _path_names(text: str):
+    """the names of the P lines the library's parser reads as paths, in order"""
+    names = []
+    for line in text.split("\n"):
+        f = line.rstrip("\r").split("\t")
+        if f[0][:1] == "P" and len(f) >= 3:
+            names.append(f[1])
+    return names
+
+
+def graph_stats(text: str, device: int = 0) -> dict:
+    """exact integer statistics of any GFA with S / L / P lines and numeric node ids.  device >= 0:
+    HIP kernels on that device, -1: the host twin (the same integers).  -> dict: length, nodes, edges, paths, steps,
+    rev_steps, depth_bp, self_loops, tips, components; depth / paths_on (per node, ascending id), bp_by_paths /
+    nodes_by_paths (index = number of paths), shared (P x P shared base pairs), path_pairs / path_abs / path_len /
+    path_sq (per path; path_sq as Python ints, path_sq_parts the three split sums), total_*; stats_us, kernel_us"""
+    with _GraphStats(text, device) as gs:
+        return gs.as_dict()
+
+
+def _graph_stats_report(text: str, device: int):
+    with _GraphStats(text, device) as gs:
+        s = gs.p.contents
+        return gs.report(_path_names(text)), dict(stats_us=int(s.stats_us))
+
+
+def graph_stats_report(text: str, device: int = 0) -> str:
+    """the TSV report of graph_stats(text, device), formatted by the library (the only place where a float is formed)"""
+    return _graph_stats_report(text, device)[0]
+
+
+def stats_sq_sums_host(values):
+    """tests: the split sum of squares of values below 2^32 -> (sum a^2, sum a b, sum b^2) with e = a 2^16 + b"""
+    a = np.ascontiguousarray(values, dtype=np.uint64)
+    out = (C.c_uint64 * 3)()
+    check(_lib.load().sr_stats_sq_sums_host(a.ctypes.data_as(C.POINTER(C.c_uint64)), len(a), out))
+    return tuple(int(v) for v in out)
+
+
 def sgd_layout(text: str, **params) -> np.ndarray:
     """the path-guided SGD positions of a GFA's nodes (ascending id order) -> float64 array"""
     L = _lib.load()
@@ -778,6 +872,14 @@ class SeqRush:
             print("Compaction on device: " + " ".join(f"{k}={v}" for k, v in list(compact_stats().items())[:7]))
         with open(args.output, "w") as fh:
             fh.write(text)
+        if args.stats:
+            # the stage parses the text just written (keeping the tables on the device: DESIGN.md section 7 item 5)
+            report, st = _graph_stats_report(text, args.device)
+            with open(args.stats, "w") as fh:
+                fh.write(report)
+            print(f"Statistics written to {args.stats}")
+            if args.verbose:
+                print(f"Statistics stage: {st['stats_us']} us on device {args.device}")
 
 
 def run_seqrush(args: Args):
