@@ -298,6 +298,28 @@ int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, 
 /* host twin of the blocked alignment kernel's base-case cone: a level with `levels_left` levels to its job's last one
  * computes the diagonals within this many of the end diagonal tlen - plen (< 0: none) */
 int sr_base_cone_reach(int e1, int e2, int two, int levels_left);
+/* Mirror partners of the blocked alignment kernel: when a batch holds (q, t) and (t, q), the first (q, t) with
+ * q < t is the primary and the first (t, q) its secondary; the kernel aligns the primary and writes the secondary's result as
+ * the transposed CIGAR unless a tie-break decided something (then it aligns the secondary too).  mirror_out[i] = the
+ * partner's index inside i's batch, top bit set on the secondary, 0xffffffff = no partner.  batch_first: nbatch + 1 pair
+ * indices (NULL = one batch).  A batch with no more pairs than `workgroups` (what its launch has; 0 = pair every batch) gets
+ * no partners: every pair has a workgroup there and mirroring could only lengthen the launch.  *partners_out = number of
+ * primaries (the workspace report's "mirror_partners"). */
+int sr_mirror_map(const uint32_t *query_idx, const uint32_t *target_idx, uint64_t count, const uint32_t *batch_first,
+                  uint32_t nbatch, uint32_t workgroups, uint32_t *mirror_out, uint64_t *partners_out);
+/* per pair of the loaded list: the orientation scores of the last alignment stage (forward; reverse complement, INT32_MAX
+ * where it was not searched to the end); either pointer may be NULL */
+int sr_ctx_orientation_scores(sr_ctx *c, int32_t *fwd, int32_t *rev);
+/* host twins of the kernel's tie rules (csrc/sr_mirror_rule.h).  Backtrace, M step: off[1..9] = candidate offsets of the tags
+ * I1o I1e I2o I2e D1o D1e D2o D2e MISMS (< 0: none; off[0] unused) -> the tag picked by this pair's order (transposed = 0)
+ * or the transposed pair's (1), 0 = none; the transposed pair's priority of a tag; 1 = the kernel flags the step.  Breakpoint
+ * call: n candidates (value, distance, component 0..4 = M I1 I2 D1 D2, diagonal) -> the index either walk accepts, returns
+ * 1 = the kernel flags the call. */
+int sr_mirror_bt_pick(const int *off, int transposed);
+int sr_mirror_bt_rank_transposed(int tag);
+int sr_mirror_bt_tie_host(const int *off);
+int sr_mirror_bp_pick_host(const int *val, const int *dist, const int *comp, const int *diag, int n, int value_bias,
+                           int *pick_out, int *pick_t_out);
 
 /* -------- inversion patching (`--patch-inversions`; src/inversion_aware_seqrush.rs:118-255, src/cigar_analysis.rs:23-147) ----
  * After each batch's alignment kernel the device scans every CIGAR for two-sided gaps between match ops (qgap / tgap =

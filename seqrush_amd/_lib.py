@@ -37,6 +37,8 @@ EXPORTS = [
     "sr_compact_gfa", "sr_compact_stats",
     "sr_sketch_device", "sr_knn_select_device",
     "sr_graph_stats_gfa", "sr_graph_stats_free", "sr_graph_stats_report", "sr_stats_sq_sums_host",
+    "sr_mirror_map", "sr_mirror_bt_pick", "sr_mirror_bt_rank_transposed", "sr_mirror_bt_tie_host", "sr_mirror_bp_pick_host",
+    "sr_ctx_orientation_scores",
 ]
 
 
@@ -251,6 +253,14 @@ def load():
     L.sr_graph_stats_free.argtypes = [PGS]; L.sr_graph_stats_free.restype = None
     L.sr_graph_stats_report.argtypes = [PGS, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.sr_stats_sq_sums_host.argtypes = [C.POINTER(u64), u64, C.POINTER(u64)]
+    PI = C.POINTER(C.c_int)
+    L.sr_mirror_map.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                C.POINTER(C.c_uint32), C.POINTER(u64)]
+    L.sr_ctx_orientation_scores.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.sr_mirror_bt_pick.argtypes = [PI, i32]
+    L.sr_mirror_bt_rank_transposed.argtypes = [i32]
+    L.sr_mirror_bt_tie_host.argtypes = [PI]
+    L.sr_mirror_bp_pick_host.argtypes = [PI, PI, PI, PI, i32, i32, PI, PI]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

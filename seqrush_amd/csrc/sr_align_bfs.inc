@@ -529,7 +529,9 @@ __device__ __forceinline__ void bfs_bt_push(GP<uint32_t> buf, int &n, int op, in
     buf[n++] = ((uint32_t)len << 4) | (uint32_t)op;
 }
 
-// one thread: backtrace of base case `bj` (oracle wfa_full); reversed run-length ops into buf
+// one thread: backtrace of base case `bj` (oracle wfa_full); reversed run-length ops into buf.  Returns the error bits,
+// | SR_MIRROR_BT_TIE when an M step had an I tag and a D tag at the maximum offset and no MISMS (sr_mirror_rule.h: the
+// transposed pair would have picked the other one; the steps inside an I / D component are symmetric)
 template <typename OT, bool TWO>
 // hist / hstride: first cell and cells per row of the history rows [level][component] the job's columns live in
 __device__ SR_BT_ATTR int bfs_backtrace(GP<OT> hist, unsigned hstride, int bj, int score, GP<uint32_t> buf, int *n_out) {
@@ -537,7 +539,7 @@ __device__ SR_BT_ATTR int bfs_backtrace(GP<OT> hist, unsigned hstride, int bj, i
     const BJob &b = b_sh.job[bj];
     const int plen = b.plen, tlen = b.tlen, cb = b.begin, ce = b.chk;
     const int off = b.base + b.shift;
-    int err = 0, n = 0;
+    int err = 0, n = 0, tie = 0;
     int s = score, k = tlen - plen, comp = ce, o = tlen;
     bool done = false;
 #define HR(S, C) (hist + ((size_t)(S) * 5 + (size_t)(C)) * (size_t)hstride + off)
@@ -549,29 +551,30 @@ __device__ SR_BT_ATTR int bfs_backtrace(GP<OT> hist, unsigned hstride, int bj, i
                 done = true; break;
             }
             const unsigned lim = (unsigned)min(tlen, plen + k);
-            int bo = NULLV, bty = 0;
+            int bo = NULLV, bty = 0, bi = NULLV;                  // bi: the furthest offset an I tag reaches
             if (s >= pen.x) bt_best(bo, bty, bnd((int)HR(s - pen.x, SR_C_M)[k] + 1, lim), 9);
             if (s >= pen.o1 + pen.e1) {
                 const GP<OT> r = HR(s - pen.o1 - pen.e1, SR_C_M);
-                bt_best(bo, bty, bnd((int)r[k - 1] + 1, lim), 1);
+                bt_best_ins(bo, bty, bi, bnd((int)r[k - 1] + 1, lim), 1);
                 bt_best(bo, bty, bnd((int)r[k + 1], lim), 5);
             }
             if (s >= pen.e1) {
-                bt_best(bo, bty, bnd((int)HR(s - pen.e1, SR_C_I1)[k - 1] + 1, lim), 2);
+                bt_best_ins(bo, bty, bi, bnd((int)HR(s - pen.e1, SR_C_I1)[k - 1] + 1, lim), 2);
                 bt_best(bo, bty, bnd((int)HR(s - pen.e1, SR_C_D1)[k + 1], lim), 6);
             }
             if (TWO) {
                 if (s >= pen.o2 + pen.e2) {
                     const GP<OT> r = HR(s - pen.o2 - pen.e2, SR_C_M);
-                    bt_best(bo, bty, bnd((int)r[k - 1] + 1, lim), 3);
+                    bt_best_ins(bo, bty, bi, bnd((int)r[k - 1] + 1, lim), 3);
                     bt_best(bo, bty, bnd((int)r[k + 1], lim), 7);
                 }
                 if (s >= pen.e2) {
-                    bt_best(bo, bty, bnd((int)HR(s - pen.e2, SR_C_I2)[k - 1] + 1, lim), 4);
+                    bt_best_ins(bo, bty, bi, bnd((int)HR(s - pen.e2, SR_C_I2)[k - 1] + 1, lim), 4);
                     bt_best(bo, bty, bnd((int)HR(s - pen.e2, SR_C_D2)[k + 1], lim), 8);
                 }
             }
             if (bty == 0 || bo > o) { err |= SR_DEV_ERR_BACKTRACE; break; }
+            if (sr_mirror_bt_tie(bty, bo, bi)) tie = SR_MIRROR_BT_TIE;
             bfs_bt_push(buf, n, SR_OP_M, o - bo, err);
             o = bo;
             switch (bty) {
@@ -616,7 +619,7 @@ __device__ SR_BT_ATTR int bfs_backtrace(GP<OT> hist, unsigned hstride, int bj, i
 #undef HR
     if (!done) err |= SR_DEV_ERR_BACKTRACE;
     *n_out = n;
-    return err;
+    return err | tie;
 }
 
 // thread 0: describe aligner jid
@@ -922,7 +925,7 @@ __global__ void __launch_bounds__(NT, (NT >= 512 ? NT / 256 : SR_MIN_WAVES)) sr_
                         const int e = bfs_backtrace<OT, TWO>(bhist, b_sh.geom.hist_stride, tid, b_sh.base_score[tid],
                                                              btbuf + (size_t)tid * SR_BFS_BTCAP, &n);
                         b_sh.bt_n[tid] = n;
-                        if (e) atomicOr(&b_sh.err, e);
+                        if (e & ~SR_MIRROR_BT_TIE) atomicOr(&b_sh.err, e & ~SR_MIRROR_BT_TIE);      // (this kernel has no use for the tie bit)
                     }
                     __syncthreads();
                 }

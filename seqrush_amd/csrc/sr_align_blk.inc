@@ -91,6 +91,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             k_sh.bnd_flag = 0; k_sh.bnd_off = k_sh.bnd_ext = k_sh.bnd_what = 0; k_sh.lds_seq_bytes = 16u * a.max_words + 16u;
 #endif
             k_sh.dg_steps = k_sh.dg_nbase = k_sh.dg_nbp = k_sh.dg_npass = 0; k_sh.base_tiles = k_sh.base_cells = 0;
+            k_sh.mir_next = -1; k_sh.mir_pairs = k_sh.mir_ties = 0;
             b_sh.geom.brow = a.brow; b_sh.geom.ring_scope = a.ring_scope; b_sh.geom.ring_hot = a.ring_hot;
             b_sh.geom.bbase_jobs = a.bbase_jobs; b_sh.geom.hist_w = a.hist_w; b_sh.geom.hist_levels = a.hist_levels;
             b_sh.geom.urow = urow;
@@ -102,15 +103,35 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
     constexpr bool KTIGHT = KTIGHT_OF(OT, RT, B, X);      // ring tiles cover a block's own range only (kwindow)
     const int scope = pen.scope;
     const int gap_opening = TWO ? max(pen.o1, pen.o2) : pen.o1;
+    // Mirrored emission (DESIGN.md 4.3, sr_mirror_rule.h).  a.mirror pairs (q, t) with the (t, q) of the same batch: the
+    // secondary is skipped when it is dequeued; the primary's workgroup either writes the secondary's outputs itself -- the
+    // transposed CIGAR, when the primary ran on the forward strand without an error and without a tie-sensitive decision --
+    // or aligns the secondary next (mir_next), as an ordinary pair, without going to the queue.
     for (;;) {
+        if (tid < 64) {
+            // the cells of the pairs so far leave the lanes' sums: what a pair adds to b_sh.cells is then its own
+            unsigned long long cl = k_sh.cells_l[tid];
+            k_sh.cells_l[tid] = 0ull;
+            for (int o = 32; o > 0; o >>= 1) cl += __shfl_xor(cl, o, 64);
+            if (tid == 0) b_sh.cells += cl;
+        }
         if (tid == 0) {
-            b_sh.pair = (int)atomicAdd(a.queue_head, 1u);
+            int pr = k_sh.mir_next;
+            k_sh.mir_next = -1;
+            while (pr < 0) {
+                pr = (int)atomicAdd(a.queue_head, 1u);
+                if (pr >= (int)a.npairs) { pr = (int)a.npairs; break; }
+                if (a.order) pr = (int)a.order[pr];          // cost-sorted dequeue order (longest pairs first)
+                if (a.mirror && a.mirror[pr] != SR_MIRROR_NONE && (a.mirror[pr] & SR_MIRROR_SECONDARY)) pr = -1;   // its primary's business
+            }
+            b_sh.pair = pr;
             b_sh.err = 0; b_sh.cig_cnt = 0; b_sh.score_acc = 0; k_sh.pend_op = -1; k_sh.pend_len = 0;
+            k_sh.mir_tie = 0;
+            k_sh.mir_snap[0] = b_sh.cells; k_sh.mir_snap[1] = k_sh.dg_steps; k_sh.mir_snap[2] = k_sh.dg_nbase; k_sh.mir_snap[3] = k_sh.dg_nbp;
         }
         __syncthreads();
-        int pair = RFL(b_sh.pair);
+        const int pair = RFL(b_sh.pair);
         if (pair >= (int)a.npairs) break;
-        if (a.order) pair = (int)a.order[pair];              // cost-sorted dequeue order (longest pairs first)
         const uint32_t q = a.pair_q[pair], t = a.pair_t[pair];
         const int plen = (int)a.seqlen[q], tlen = (int)a.seqlen[t];
         const int pw = SR_SEQ_WORDS(plen), tw = SR_SEQ_WORDS(tlen);
@@ -479,7 +500,8 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                         const int e = bfs_backtrace<OT, TWO>(bhist + b_sh.job[tid].hbase, b_sh.job[tid].hw, tid, b_sh.base_score[tid],
                                                              btbuf + (size_t)tid * SR_BFS_BTCAP, &n);
                         b_sh.bt_n[tid] = n;
-                        if (e) atomicOr(&b_sh.err, e);
+                        if (e & SR_MIRROR_BT_TIE) k_sh.mir_tie = 1;
+                        if (e & ~SR_MIRROR_BT_TIE) atomicOr(&b_sh.err, e & ~SR_MIRROR_BT_TIE);
                         KPRIO_LO();
                     }
                     __syncthreads();
@@ -561,6 +583,8 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         }
         if (part) atomicAdd(&b_sh.score_acc, part);
         __syncthreads();
+        // (read between the two barriers: past the second one thread 0 may already be resetting them for the next pair)
+        const int p_err = RFL(b_sh.err), p_score = RFL(b_sh.score_acc), p_tie = RFL(k_sh.mir_tie);
         if (tid == 0) {
             a.is_reverse[pair] = is_rev ? 1 : 0;
             a.score[pair] = b_sh.err ? -1 : b_sh.score_acc;
@@ -577,19 +601,47 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
 #endif
         }
         __syncthreads();
+        // ---------------- the pair's secondary: emitted by symmetry or queued for this workgroup
+        const uint32_t mir = a.mirror ? a.mirror[pair] : SR_MIRROR_NONE;
+        bool mir_emit = false;
+        if (mir != SR_MIRROR_NONE && !(mir & SR_MIRROR_SECONDARY)) {
+            // (orientation as its own kernel: the secondary's strand and orientation scores are already there, and stay)
+            mir_emit = p_err == 0 && !is_rev && p_tie == 0 && !(a.pre_oriented && a.is_reverse[mir] != 0);
+            if (mir_emit) {
+                // the transposed CIGAR: I <-> D (op codes 2 and 3), same runs, into the secondary's own arena region
+                // (the same reserve, |q| + |t| + 2 ops); the barrier above ordered the primary's ops
+                GP<uint32_t> ops2 = (GP<uint32_t>)a.cigar_ops + a.cigar_base[mir];
+                for (uint32_t i = tid; i < cnt; i += NT) { const uint32_t v = ops[i]; ops2[i] = v ^ ((v & 2u) >> 1); }
+                if (tid < 64) {
+                    // the secondary's tallies as the oracle counts them are its primary's: cells, levels, base cases, searches
+                    unsigned long long cl = k_sh.cells_l[tid];
+                    k_sh.cells_l[tid] = 0ull;
+                    for (int o = 32; o > 0; o >>= 1) cl += __shfl_xor(cl, o, 64);
+                    if (tid == 0) {
+                        b_sh.cells += cl;
+                        b_sh.cells += b_sh.cells - k_sh.mir_snap[0]; k_sh.dg_steps += k_sh.dg_steps - k_sh.mir_snap[1];
+                        k_sh.dg_nbase += k_sh.dg_nbase - k_sh.mir_snap[2]; k_sh.dg_nbp += k_sh.dg_nbp - k_sh.mir_snap[3];
+                        k_sh.mir_pairs += 1ull;
+                        a.score[mir] = p_score; a.cigar_cnt[mir] = cnt;
+                        if (!a.pre_oriented) { a.is_reverse[mir] = 0; a.ori_fwd[mir] = fwd; a.ori_rev[mir] = rev; }
+                    }
+                }
+            } else if (tid == 0) { k_sh.mir_next = (int)mir; k_sh.mir_ties += 1ull; }
+        }
         if (a.fuse_unite) {
             // unite the bases of the match runs (what sr_unite_kernel does for a pair, sr_uf.hip); same filter: aligned, and
             // the score within the divergence bound.  The CIGAR was stored by this workgroup and the barrier above orders it.
-            const int sc = RFL(b_sh.err) ? -1 : RFL(b_sh.score_acc);
+            const int sc = p_err ? -1 : p_score;
             if (sc >= 0 && sc <= a.max_score[pair]) {
                 unsigned long long united = 0, runs = 0;
                 int uerr = 0;
                 uf_unite_cigar<NT>((const uint32_t *)a.cigar_ops + a.cigar_base[pair], cnt, a.seq_goff[q], a.seq_goff[t],
                                    (unsigned long long)plen, is_rev != 0, 0ull, 0ull, a.min_match_len, a.uf_nodes, united, runs, uerr);
                 for (int o = 32; o > 0; o >>= 1) { united += __shfl_xor(united, o, 64); runs += __shfl_xor(runs, o, 64); }
+                // (a secondary emitted by symmetry would unite exactly these base pairs again: only its tallies are added)
                 if ((tid & 63) == 0) {
-                    if (united) atomicAdd(&a.counters[4], united);
-                    if (runs) atomicAdd(&a.counters[5], runs);
+                    if (united) atomicAdd(&a.counters[4], mir_emit ? 2ull * united : united);
+                    if (runs) atomicAdd(&a.counters[5], mir_emit ? 2ull * runs : runs);
                 }
                 if (uerr) atomicOr(a.error_flag, uerr);
             }
@@ -623,6 +675,8 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         atomicAdd(&a.counters[19], k_sh.dg_f); atomicAdd(&a.counters[20], k_sh.dg_c);
         atomicAdd(&a.counters[21], k_sh.dg_e); atomicAdd(&a.counters[22], k_sh.dg_r);
         if (k_sh.dg_redo) atomicAdd(&a.counters[37], k_sh.dg_redo);
+        if (k_sh.mir_pairs) atomicAdd(&a.counters[38], k_sh.mir_pairs);
+        if (k_sh.mir_ties) atomicAdd(&a.counters[39], k_sh.mir_ties);
         atomicAdd(&a.counters[46], k_sh.base_tiles); atomicAdd(&a.counters[47], k_sh.base_cells);
         if (PROF) {
             if (!a.pre_oriented) atomicAdd(&a.counters[6], t_ori);    // ([6] holds sr_orient_kernel's cells otherwise)

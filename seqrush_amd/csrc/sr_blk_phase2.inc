@@ -15,8 +15,9 @@
 //   F  filter: diagonals whose M offset plus the other aligner's U bound (blk_tile keeps U = running
 //      max of M per diagonal, a superset bound of the scope window) reaches tlen -> candidate list
 //   E  candidates x scope levels: exact overlap test per component, 64-bit atomicMin of the packed
-//      (value, walk order, diagonal) per call
-//   W  one thread per segment replays the reference loop with the done-checks over the calls' results.
+//      (value, walk order, diagonal) per call -- and of the key the transposed pair would form (pc_best_t)
+//   W  one thread per segment replays the reference loop with the done-checks over the calls' results; an accepted
+//      result whose two keys name different (component, diagonal) marks the pair tie-sensitive (k_sh.mir_tie).
 template <typename OT, bool TWO, int NT, int B, int E1, int E2, typename ST = OT, bool PROF = false>
 __device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t> clist, GP<int> gmak,
                                            const SrPen &pen, const int s0, const int nact, const int gap_opening) {
@@ -48,10 +49,10 @@ __device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t>
             for (int j = 0; j < B; j++) { k_sh.pc_idx[tid][0][j] = -1; k_sh.pc_idx[tid][1][j] = -1; }
             while (f <= avail) {
                 if (lf) {
-                    k_sh.pc_side[tid][n] = 0; k_sh.pc_s0[tid][n] = f; k_sh.pc_s1[tid][n] = r; k_sh.pc_best[tid][n] = ~0ull;
+                    k_sh.pc_side[tid][n] = 0; k_sh.pc_s1[tid][n] = r; k_sh.pc_best[tid][n] = ~0ull; k_sh.pc_best_t[tid][n] = ~0ull;
                     k_sh.pc_idx[tid][0][f - s0] = n; n++; r++;
                 }
-                k_sh.pc_side[tid][n] = 1; k_sh.pc_s0[tid][n] = r; k_sh.pc_s1[tid][n] = f; k_sh.pc_best[tid][n] = ~0ull;
+                k_sh.pc_side[tid][n] = 1; k_sh.pc_s1[tid][n] = f; k_sh.pc_best[tid][n] = ~0ull; k_sh.pc_best_t[tid][n] = ~0ull;
                 k_sh.pc_idx[tid][1][r - s0] = n; n++; f++; lf = 1;
             }
             k_sh.pc_n[tid] = n;
@@ -245,11 +246,10 @@ __device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t>
                                     const int val = score_0 + L - gap;
                                     const int o0 = c0[jj][c], o1 = c1[u][c];
                                     if (val < bp0 && o0 >= 0 && o1 >= 0 && o0 + o1 >= tlen) {
-                                        const int rank = (c == SR_C_D2) ? 0 : (c == SR_C_I2) ? 1 : (c == SR_C_D1) ? 2 : (c == SR_C_I1) ? 3 : 4;
-                                        const unsigned long long key = ((unsigned long long)(unsigned)(val + gapmax) << 42) |   // (i * 5 + rank < 5 * SR_BLK_MAK_SLOTS: 10 bits)
-                                                                       ((unsigned long long)(unsigned)(i * 5 + rank) << 32) |
-                                                                       (unsigned long long)(unsigned)(k0 + (1 << 30));
-                                        atomicMin(&k_sh.pc_best[p][cix[jj]], key);
+                                        // (value, i * 5 + walk rank, diagonal): i * 5 + rank < 5 * SR_BLK_MAK_SLOTS: 10 bits.  The second key
+                                        // is the transposed pair's: the other walk order, the largest diagonal (sr_mirror_rule.h)
+                                        atomicMin(&k_sh.pc_best[p][cix[jj]], sr_mirror_bp_key((unsigned)(val + gapmax), i, c, k0));
+                                        atomicMin(&k_sh.pc_best_t[p][cix[jj]], sr_mirror_bp_key_t((unsigned)(val + gapmax), i, c, k0));
                                     }
                                 }
                             }
@@ -276,10 +276,12 @@ __device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t>
                     const int score_0 = half ? r : f, score_1 = half ? f : r;
                     const int min_1 = (score_1 > scope - 1) ? score_1 - (scope - 1) : 0;
                     if (score_0 + min_1 - gap_opening >= sg.bp_score) { ph = 3; break; }
-                    const unsigned long long key = k_sh.pc_best[tid][ci++];
+                    const unsigned long long key = k_sh.pc_best[tid][ci], key_t = k_sh.pc_best_t[tid][ci];
+                    ci++;
                     if (key != ~0ull) {
                         const int val = (int)(key >> 42) - gapmax;
                         if (val < sg.bp_score) {
+                            if (sr_mirror_bp_tie(key, key_t)) k_sh.mir_tie = 1;     // the transposed pair would have split elsewhere
                             const int ord = (int)((key >> 32) & 1023ull), i = ord / 5, rank = ord - i * 5;
                             const int c = (rank == 0) ? SR_C_D2 : (rank == 1) ? SR_C_I2 : (rank == 2) ? SR_C_D1 : (rank == 3) ? SR_C_I1 : SR_C_M;
                             const int k0 = (int)(unsigned)(key & 0xffffffffull) - (1 << 30), k1 = kinv - k0;

@@ -22,10 +22,11 @@ struct KShared {
     // batched breakpoint detection (phase 2) of one pass: up to K_P2 segments, <= 2*KB_MAX overlap calls each
     int p2n, p2seg[K_P2];
     unsigned p2mask_lo, p2mask_hi;
-    int pc_n[K_P2], pc_s0[K_P2][2 * KB_MAX], pc_s1[K_P2][2 * KB_MAX];
+    int pc_n[K_P2], pc_s1[K_P2][2 * KB_MAX];            // calls of a segment; the other aligner's level of each
     unsigned char pc_side[K_P2][2 * KB_MAX];
     signed char pc_idx[K_P2][2][KB_MAX];               // call index of (side, level of the block) or -1
     unsigned long long pc_best[K_P2][2 * KB_MAX];
+    unsigned long long pc_best_t[K_P2][2 * KB_MAX];    // the same call as the transposed pair would decide it (sr_mirror_rule.h)
     int pu_start[2 * K_P2 + 1], pu_glo[2 * K_P2];
     int pu_kmin[2 * K_P2], pu_kmax[2 * K_P2];          // band of diagonals of a filter unit (segment, side) that passed the filter at some level
     int cl_n;
@@ -33,6 +34,11 @@ struct KShared {
     unsigned lds_seq_bytes;                                // dynamic LDS of the workgroup: four sequence copies + read slack
     int bnd_flag; unsigned bnd_off, bnd_ext, bnd_what;     // first offending access of the workgroup (offset, extent, what: 1 ring / 2 history row, 3 LDS window)
 #endif
+    // mirrored emission (sr_align_blk.inc): the pair in hand had a tie-sensitive decision; the secondary this workgroup aligns
+    // next (-1: none, take a pair from the queue); the pair's counters [0..3] as they stood when it began
+    int mir_tie, mir_next;
+    unsigned long long mir_snap[4];
+    unsigned long long mir_pairs, mir_ties;    // secondaries emitted by symmetry / aligned after all -> counters[38], [39]
     int redo_from;                     // base cases: first job of the batch that outgrew the levels it was given (BJ_MAX: none)
     int pend_op, pend_len;             // CIGAR emission: the run being built (not yet stored)
     unsigned long long row_w[4][16];   // per wave, lane accesses of its tiles' row loads / stores (summed when the kernel ends); [2..3]: the base-case histories' share

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include "sr_internal.h"
+#include "sr_mirror_rule.h"
 
 #define NULLV SR_NULL_OFF
 // Symbol width of the packed sequence buffer: 2 bits (inputs over upper-case ACGT), 4 bits (<= 16 distinct
@@ -205,6 +206,13 @@ __device__ __forceinline__ void cig_append(GP<uint32_t> ops, uint32_t &cnt, uint
 __device__ __forceinline__ void bt_best(int &bo, int &bty, int off, int type) {
     if (off < 0) return;
     if (off > bo || (off == bo && type > bty)) { bo = off; bty = type; }
+}
+
+// an I tag's candidate: also kept as the furthest offset any I tag reaches (tie tracking, sr_mirror_rule.h)
+__device__ __forceinline__ void bt_best_ins(int &bo, int &bty, int &bi, int off, int type) {
+    if (off < 0) return;
+    bi = max(bi, off);
+    bt_best(bo, bty, off, type);
 }
 
 template <int NT>

@@ -25,6 +25,7 @@
 #include "sr_iter_rule.h"
 #include "sr_inv_rule.h"
 #include "sr_base_cone.h"
+#include "sr_mirror_rule.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -52,6 +53,7 @@ static const SrKnob SR_KNOBS[] = {
     {"SR_NO_REORDER", "off", "keep list order instead of the cost-sorted dequeue order"},
     {"SR_ORIENT_LEVELS", "off", "orientation level by level even for the default penalties"},
     {"SR_NO_KBITS", "off", "no q-gram bound in the orientation kernel"},
+    {"SR_NO_MIRROR", "off", "1 = no pair has a mirror partner: (q, t) and (t, q) are both aligned (A/B runs, tests)"},
     {"SR_NO_FUSED_UNITE", "off", "sr_ctx_run launches sr_unite_kernel per batch instead of uniting inside the blocked alignment kernel"},
     {"SR_PROFILE_TICKS", "0", "1 = launch the instrumented instance (100 MHz tick counters)"},
     {"SR_FORCE_INT32", "off", "tests: 32-bit offsets (and the 16-bit ring of 32-bit searches) whatever the sequence length"},
@@ -264,6 +266,8 @@ struct sr_ctx {
     int onwg = 0;                      // workgroups (= waves) of the orientation kernel, 0 = orientation inside the alignment kernel
     size_t olds_bytes = 0;
     int32_t *d_max_score = nullptr;
+    uint32_t *d_mirror = nullptr;                  // [np] SrAlignArgs::mirror (blocked kernel, 2-bit symbols), nullptr = none
+    uint64_t mirror_partners = 0;                  // primaries of the rank's list
     // kernel timing: [kind] -> one event pair per batch (kinds: 0 align, 1 unite, 4 orientation) or a single pair (2, 3)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
     int ev_used[5] = {0, 0, 0, 0, 0};
@@ -319,7 +323,7 @@ static void free_dev(sr_ctx *c) {
     c->dev_allocs.clear();
     c->d_nodes = c->d_minarr = c->d_labels = c->d_counters = nullptr;
     c->d_error = nullptr; c->d_queue = nullptr; c->d_oqueue = nullptr; c->d_order = nullptr; c->d_cbase = nullptr;
-    c->d_bases = nullptr; c->d_max_score = nullptr; c->onwg = 0;
+    c->d_bases = nullptr; c->d_max_score = nullptr; c->d_mirror = nullptr; c->mirror_partners = 0; c->onwg = 0;
     c->d_okeys = c->d_okeys2 = nullptr; c->d_ovals = nullptr; c->d_otemp = nullptr; c->otemp_bytes = 0;
     c->loaded = false; c->from_paf = false; c->aligned_batch_valid = false;
     for (int k = 0; k < 5; k++) c->ev_used[k] = 0;
@@ -800,6 +804,86 @@ static int build_pair_list(sr_ctx *c, const sr_params *p, const SeqDev &sd, cons
     return SR_OK;
 }
 
+// The mirror map of a pair list that runs in the given batches (sr_mirror_rule.h; batch b = pairs [batch_first[b],
+// batch_first[b + 1])): the first (q, t) with q < t of a batch is the primary of the first (t, q) of the same batch, its
+// secondary.  Self pairs, further copies of either and pairs whose partner sits in another batch have none.  A batch with
+// no more pairs than the launch has workgroups gets no partners at all: every pair has a workgroup of its own there, the
+// launch lasts as long as its longest pair, and a primary that aligns its secondary after itself (a tie, the reverse
+// strand) could only lengthen it while the secondary's workgroup stood idle.  Returns the number of primaries.
+static uint64_t mirror_map(const uint32_t *q, const uint32_t *t, const uint32_t *batch_first, uint32_t nbatch, uint32_t workgroups,
+                           uint32_t *out) {
+    uint64_t partners = 0;
+    for (uint32_t b = 0; b < nbatch; b++) {
+        const uint32_t f = batch_first[b], l = batch_first[b + 1];
+        for (uint32_t i = f; i < l; i++) out[i] = SR_MIRROR_NONE;
+        if ((uint64_t)l - f >= (uint64_t)SR_MIRROR_SECONDARY) continue;          // (the top bit of an entry is the mark)
+        if (l - f <= workgroups) continue;                                       // a workgroup per pair: nothing to gain
+        std::unordered_map<uint64_t, uint32_t> first;                            // ordered (q, t) -> its first index in the batch
+        for (uint32_t i = f; i < l; i++)
+            if (q[i] != t[i]) first.emplace(((uint64_t)q[i] << 32) | t[i], i);
+        for (uint32_t i = f; i < l; i++) {
+            if (q[i] >= t[i]) continue;
+            if (first.find(((uint64_t)q[i] << 32) | t[i])->second != i) continue;                // a further copy
+            const auto other = first.find(((uint64_t)t[i] << 32) | q[i]);
+            if (other == first.end()) continue;
+            out[i] = other->second - f;
+            out[other->second] = (i - f) | SR_MIRROR_SECONDARY;
+            partners++;
+        }
+    }
+    return partners;
+}
+// the same without a context (tests): batch_first = NULL: one batch; workgroups = what the launch would have (0: pair
+// every batch)
+extern "C" int sr_mirror_map(const uint32_t *query_idx, const uint32_t *target_idx, uint64_t count, const uint32_t *batch_first,
+                             uint32_t nbatch, uint32_t workgroups, uint32_t *mirror_out, uint64_t *partners_out) {
+    if ((count && (!query_idx || !target_idx || !mirror_out)) || count > 0xfffffff0ULL) return fail(SR_ERR_INVALID, "bad pair list");
+    const uint32_t one[2] = {0, (uint32_t)count};
+    if (!batch_first) { batch_first = one; nbatch = 1; }
+    if (nbatch == 0 || batch_first[0] != 0 || batch_first[nbatch] != count) return fail(SR_ERR_INVALID, "batches do not cover the pair list");
+    for (uint32_t b = 0; b < nbatch; b++)
+        if (batch_first[b] > batch_first[b + 1]) return fail(SR_ERR_INVALID, "batches do not cover the pair list");
+    const uint64_t n = mirror_map(query_idx, target_idx, batch_first, nbatch, workgroups, mirror_out);
+    if (partners_out) *partners_out = n;
+    return SR_OK;
+}
+// the rules of sr_mirror_rule.h for the tests.  off[1..9]: candidate offsets of the nine tags (< 0: none); transposed: rank
+// the tags as the transposed pair does -> the tag picked (0: none)
+extern "C" int sr_mirror_bt_pick(const int *off, int transposed) {
+    int bo = -1, bty = 0;
+    for (int tag = 1; tag <= 9; tag++) {
+        if (off[tag] < 0) continue;
+        const int r = transposed ? sr_mirror_bt_rank_t(tag) : tag, rb = transposed ? sr_mirror_bt_rank_t(bty) : bty;
+        if (off[tag] > bo || (off[tag] == bo && r > rb)) { bo = off[tag]; bty = tag; }
+    }
+    return bty;
+}
+extern "C" int sr_mirror_bt_rank_transposed(int tag) { return sr_mirror_bt_rank_t(tag); }
+// what the kernel's backtrace computes for the same candidates: 1 = tie-sensitive
+extern "C" int sr_mirror_bt_tie_host(const int *off) {
+    int bo = -1, bty = 0, bi = -1;
+    for (int tag = 1; tag <= 9; tag++) {
+        if (off[tag] < 0) continue;
+        if (tag <= SR_BT_I2_EXT && off[tag] > bi) bi = off[tag];
+        if (off[tag] > bo || (off[tag] == bo && tag > bty)) { bo = off[tag]; bty = tag; }
+    }
+    return bty != 0 && sr_mirror_bt_tie(bty, bo, bi) ? 1 : 0;
+}
+// breakpoint call: n candidates (value, distance i, component, diagonal) -> the candidate each walk accepts (index) and
+// whether the packed keys call the choice tie-sensitive; value_bias makes the values non-negative (the kernel adds gap-open)
+extern "C" int sr_mirror_bp_pick_host(const int *val, const int *dist, const int *comp, const int *diag, int n, int value_bias,
+                                      int *pick_out, int *pick_t_out) {
+    unsigned long long best = ~0ull, best_t = ~0ull;
+    *pick_out = *pick_t_out = -1;
+    for (int j = 0; j < n; j++) {
+        const unsigned long long k = sr_mirror_bp_key((unsigned)(val[j] + value_bias), dist[j], comp[j], diag[j]);
+        const unsigned long long kt = sr_mirror_bp_key_t((unsigned)(val[j] + value_bias), dist[j], comp[j], diag[j]);
+        if (k < best) { best = k; *pick_out = j; }
+        if (kt < best_t) { best_t = kt; *pick_t_out = j; }
+    }
+    return n > 0 && sr_mirror_bp_tie(best, best_t) ? 1 : 0;
+}
+
 // kernel choice and workgroup shape.  impl 2 = score-blocked wave-tiled kernel (when this build has an instance for the
 // penalties), impl 1 = level-synchronous kernel (any penalties; rings deeper than 32 levels take its wide instance)
 static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const SrPen &ori, uint64_t maxlen, uint32_t np, Plan &pl) {
@@ -841,9 +925,9 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     pl.wave_wg = impl == 2 && (c->nthreads == 64 || (c->nthreads == 128 && kblock == 10));   // lean builds: 16 / 8 pairs per CU
     if (pl.wave_wg) pl.wg_per_cu = c->nthreads == 64 ? 16 : 8;
     // static tables of the kernel (upper estimates; the blocked kernel's scan arrays of the fused unite grow with the
-    // workgroup: 23 416 / 26 536 / 32 776 bytes at 256 / 512 / 1024 threads)
+    // workgroup: 25 024 / 28 144 / 34 384 bytes at 256 / 512 / 1024 threads with the second key table of breakpoint detection)
     auto static_lds = [&](int nthreads) -> size_t {
-        return (size_t)(pl.wave_wg ? 6 : impl != 2 ? 28 : nthreads >= 1024 ? 33 : nthreads >= 512 ? 26 : 23) * 1024;
+        return (size_t)(pl.wave_wg ? 6 : impl != 2 ? 28 : nthreads >= 1024 ? 34 : nthreads >= 512 ? 28 : 25) * 1024;
     };
     const size_t lds_per_wg = c->lds_bytes + static_lds(c->nthreads);
     pl.wg_per_cu = (int)std::min<size_t>((size_t)pl.wg_per_cu, std::max<size_t>(1, (160 * 1024) / lds_per_wg));
@@ -1025,7 +1109,16 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     }
     DEV_UPLOAD(c->d_order, uint32_t, order);
     DEV_UPLOAD(c->d_max_score, int32_t, max_score);
-    HIPCHK(hipStreamSynchronize(c->stream));   // the uploads above have read their host vectors (pq, pt, cb, order)
+    // mirror partners: blocked kernel on 2-bit buffers (elsewhere the reference's complement is no involution and the strand
+    // decision loses its symmetry), pairs aligned with an orientation search
+    std::vector<uint32_t> mirror;
+    c->mirror_partners = 0;
+    if (impl == 2 && pk.sm.bits == 2 && !forced_strand && np > 0) {
+        mirror.assign(np, SR_MIRROR_NONE);
+        if (!knob("SR_NO_MIRROR")) c->mirror_partners = mirror_map(c->pair_q.data(), c->pair_t.data(), c->batch_first.data(), nbatch, (uint32_t)nwg, mirror.data());
+        DEV_UPLOAD(c->d_mirror, uint32_t, mirror);
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));   // the uploads above have read their host vectors (pq, pt, cb, order, mirror)
     if ((r = dev_alloc(c, &d, sizeof(uint32_t)))) return r; c->d_queue = (uint32_t *)d;
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bring_wg * rsz))) return r; a.bring = d;
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bhist_wg * osz))) return r; a.bhist = d;
@@ -1116,6 +1209,7 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     memset(&u, 0, sizeof(u));
     u.pair_q = d_pq; u.pair_t = d_pt; u.npairs = np; u.seqlen = sd.len; u.seq_goff = sd.goff;
     a.fuse_unite = 0; a.uf_nodes = c->d_nodes; a.seq_goff = sd.goff; a.max_score = c->d_max_score; a.min_match_len = p->min_match_len;
+    a.mirror = c->d_mirror;
     c->fuse_unite = impl == 2 && !knob("SR_NO_FUSED_UNITE");
     u.is_reverse = a.is_reverse; u.score = a.score; u.max_score = c->d_max_score;
     u.cigar_ops = a.cigar_ops; u.cigar_base = c->d_cbase; u.cigar_cnt = a.cigar_cnt;
@@ -1138,13 +1232,14 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
              "\"base_history_bytes_per_workgroup\": %llu, \"workspace_bytes\": %llu, \"cigar_arena_bytes\": %llu, "
              "\"orientation_ring_bytes\": %llu, \"union_find_bytes\": %llu, \"device_free_bytes_at_load\": %zu, \"kernel_build\": \"%s\", "
              "\"ring_depth_m\": %d, \"ring_depth_id\": %d, \"fused_unite\": %d, \"wave_build\": %d, \"level_kernel_wide\": %d, "
-             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"knobs\": ",
+             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"knobs\": ",
              np, pl.nbatch, pk.sm.bits, pl.osz, pl.impl == 2 ? pl.rsz : pl.osz, pl.impl, pl.impl == 2 ? pl.kblock : 1, pen.two ? 1 : 0, pl.lazy_id,
              pl.nwg, c->nthreads, pl.wg_per_cu, c->lds_bytes,
              (unsigned long long)(pl.bring_wg * pl.rsz), (unsigned long long)(pl.bhist_wg * pl.osz),
              (unsigned long long)((uint64_t)pl.nwg * pl.per_wg_bytes), (unsigned long long)(pl.arena_ops * 4), (unsigned long long)pl.oring_bytes,
              (unsigned long long)(3ULL * c->uf_size * 8), pl.free_b, srk_align_blk_build_tag(), pl.kdepth, pl.kdepth2, c->fuse_unite ? 1 : 0,
-             pl.wave_wg ? 1 : 0, (pl.impl == 1 && pl.ring_scope + 1 > 32) ? 1 : 0, c->aa.profile_ticks, oroute, srk_source_digest());
+             pl.wave_wg ? 1 : 0, (pl.impl == 1 && pl.ring_scope + 1 > 32) ? 1 : 0, c->aa.profile_ticks, oroute, srk_source_digest(),
+             (unsigned long long)c->mirror_partners);
     c->workspace_report = std::string(buf) + knobs_json() + "}";
 }
 
@@ -1200,6 +1295,16 @@ extern "C" int sr_ctx_pairs(const sr_ctx *c, uint32_t **q_out, uint32_t **t_out,
     memcpy(*t_out, c->pair_t.data(), m * 4);
     return SR_OK;
 }
+// the orientation scores the alignment stage left per pair (forward; reverse complement, INT32_MAX where it was not better)
+extern "C" int sr_ctx_orientation_scores(sr_ctx *c, int32_t *fwd, int32_t *rev) {
+    if (!c || !c->loaded || c->from_paf || !c->aa.ori_fwd) return fail(SR_ERR_INVALID, "context has no alignment stage");
+    const size_t np = c->pair_q.size();
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (fwd && np) HIPCHK(hipMemcpy(fwd, c->aa.ori_fwd, np * 4, hipMemcpyDeviceToHost));
+    if (rev && np) HIPCHK(hipMemcpy(rev, c->aa.ori_rev, np * 4, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
 extern "C" uint32_t sr_ctx_num_batches(const sr_ctx *c) { return (c && c->loaded) ? (uint32_t)c->batch_first.size() - 1 : 0; }
 extern "C" const char *sr_ctx_workspace_report(const sr_ctx *c) { return c ? c->workspace_report.c_str() : ""; }
 
@@ -1218,6 +1323,7 @@ static void batch_args(const sr_ctx *c, uint32_t b, SrAlignArgs *a, SrUniteArgs 
         a->pair_q += f; a->pair_t += f; a->npairs = cnt; if (a->order) a->order += f;
         a->is_reverse += f; a->score += f; a->ori_fwd += f; a->ori_rev += f; a->cigar_cnt += f;
         if (a->max_score) a->max_score += f;
+        if (a->mirror) a->mirror += f;
         a->cigar_base = c->d_cbase + f + b;
     }
     if (u) {

@@ -105,6 +105,9 @@ struct SrAlignArgs {
     const uint64_t *seq_goff;       // [n] global offsets (concatenated coordinates)
     const int32_t *max_score;       // [npairs] divergence filter bound or INT_MAX
     uint64_t min_match_len;
+    // impl 2: [npairs] the (t, q) of the same batch that goes with (q, t) -- index inside the batch, SR_MIRROR_SECONDARY marks
+    // the one that is skipped in the queue, SR_MIRROR_NONE = no partner (sr_mirror_rule.h); NULL = none at all
+    const uint32_t *mirror;
     // outputs
     uint8_t *is_reverse;       // [npairs]
     int32_t *score;            // [npairs]

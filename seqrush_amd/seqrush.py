@@ -295,6 +295,13 @@ class Context:
         check(self.L.sr_ctx_align_all(self._h, 1 if unite else 0, C.byref(p)))
         return Alignments(p)
 
+    def orientation_scores(self):
+        """(forward, reverse-complement) orientation scores of the last alignment stage over this rank's pairs"""
+        n = self.num_pairs
+        fw = np.zeros(max(n, 1), dtype=np.int32); rv = np.zeros(max(n, 1), dtype=np.int32)
+        check(self.L.sr_ctx_orientation_scores(self._h, fw.ctypes.data_as(C.POINTER(C.c_int32)), rv.ctypes.data_as(C.POINTER(C.c_int32))))
+        return fw[:n], rv[:n]
+
     def pair_results(self):
         """(score, is_reverse, n_cigar_ops) arrays over this rank's pairs; resident for every batch"""
         n = self.num_pairs
@@ -469,6 +476,9 @@ class Context:
                     tk_p2_filter=int(out[29]), tk_p2_exact=int(out[30]), tk_p2_replay=int(out[31]),
                     st_wait_cycles=int(out[32]), st_body_cycles=int(out[33]), st_tiles=int(out[34]), st_ext_iters=int(out[35]),
                     lds_row_bytes=int(out[36]), base_requeues=int(out[37]),
+                    # blocked kernel: secondaries written as their primary's transposed CIGAR / aligned after all (a tie, a
+                    # reverse strand or an error in the primary)
+                    mirror_pairs=int(out[38]), mirror_ties=int(out[39]),
                     bounds_first=[int(out[40]), int(out[41]), int(out[42]), int(out[43])],
                     experiment=[int(out[44]), int(out[45]), int(out[46]), int(out[47])],
                     # blocked kernel: the base-case histories' share of row_bytes_*, base-case tiles and level-diagonals as executed
@@ -1210,3 +1220,24 @@ def pair_list(n: int, params: Params):
     out = [(int(q[i]), int(t[i])) for i in range(m)]
     L.sr_free(C.cast(q, C.c_void_p)); L.sr_free(C.cast(t, C.c_void_p))
     return out
+
+
+MIRROR_NONE, MIRROR_SECONDARY = 0xffffffff, 0x80000000
+
+
+def mirror_map(pairs, batch_first=None, workgroups=0):
+    """The blocked kernel's mirror partners of an ordered pair list that runs in the given batches (host only;
+    include/seqrush_amd.h sr_mirror_map) -> (entries, primaries): entries[i] = partner's index inside i's batch, | MIRROR_SECONDARY
+    on the pair that is not aligned by itself, MIRROR_NONE = no partner.  batch_first: nbatch + 1 pair indices, None = one batch;
+    workgroups: what the launch has -- a batch with no more pairs than that gets no partners (0: pair every batch)"""
+    L = _lib.load()
+    m = len(pairs)
+    q = np.ascontiguousarray([a for a, _ in pairs] or [0], dtype=np.uint32)
+    t = np.ascontiguousarray([b for _, b in pairs] or [0], dtype=np.uint32)
+    out = np.zeros(max(m, 1), dtype=np.uint32)
+    n = C.c_uint64()
+    PU = C.POINTER(C.c_uint32)
+    bf = None if batch_first is None else np.ascontiguousarray(batch_first, dtype=np.uint32)
+    check(L.sr_mirror_map(q.ctypes.data_as(PU), t.ctypes.data_as(PU), m, None if bf is None else bf.ctypes.data_as(PU),
+                          0 if bf is None else len(bf) - 1, int(workgroups), out.ctypes.data_as(PU), C.byref(n)))
+    return [int(x) for x in out[:m]], int(n.value)
