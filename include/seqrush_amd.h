@@ -527,6 +527,55 @@ int sr_graph_stats_report(const sr_graph_stats *s, const char *const *names, cha
 /* tests: the split sum of squares over n values below 2^32 on the host */
 int sr_stats_sq_sums_host(const uint64_t *e, uint64_t n, uint64_t out[3]);
 
+/* -------- 2-D layout (`--layout FILE`, `--layout-svg FILE`) -----------------------------------
+ * Path-guided SGD in the plane of any GFA with S / L / P lines and numeric node ids, as the parser of sr_sort_gfa reads it
+ * (what `odgi layout` + `odgi draw` give, reproducibly): two end points per node, pulled to their distance along the
+ * paths.  Deterministic like the Ygs SGD (counter-based draws, Zipf by table, sub-rounds with order-free int64
+ * accumulation): the device result is bit-identical to the host twin's.  A layout is defined only up to an isometry of
+ * the plane.  More than 2^30 nodes or 2^31 steps: SR_ERR_UNSUPPORTED.  A graph without a path of two steps or more keeps
+ * its initial state: x = cumulative node length in id order, y = a seeded value within half a node length of 0.
+ * A zero field is derived (the value in brackets); the seed is taken as it is. */
+#define SR_LAYOUT_DEVICE_HOST_TWIN (-1)   /* the batched SGD on one host thread (bit-identical to the device) */
+#define SR_LAYOUT_DEVICE_SEQUENTIAL (-2)  /* every term applied at once (yardstick for the quality only) */
+typedef struct {
+    uint64_t seed;              /* counter-based draws: splitmix64(seed, iteration, term, draw); default 9399220 */
+    uint64_t iter_max;          /* [30]: iterations 0..iter_max run; at least 2 */
+    double theta;               /* [0.99]; cooling iterations use 0.001 */
+    double eps;                 /* [0.01] */
+    double eta_max;             /* [(longest path in bp)^2] */
+    double cooling_start;       /* [0.5]: cooling for iterations > floor(cooling_start * iter_max) */
+    uint64_t space;             /* [longest path in bp] */
+    uint64_t space_max;         /* [100] */
+    uint64_t space_quant;       /* [100] */
+    uint64_t min_term_updates;  /* [10 * total path steps]: terms per iteration */
+    uint64_t terms_per_round;   /* terms per sub-round [DESIGN.md section 12] */
+    int32_t device;             /* >= 0: HIP device, SR_LAYOUT_DEVICE_HOST_TWIN, SR_LAYOUT_DEVICE_SEQUENTIAL */
+    int32_t reserved;
+} sr_layout_params;
+void sr_layout_params_default(sr_layout_params *p);
+/* the layout of gfa_in (p NULL = defaults): 4 doubles per node in ascending id order, x0 y0 x1 y1 (end point 0 = the
+ * node's start on its forward strand); n_nodes must be its number of nodes */
+int sr_layout_gfa(const char *gfa_in, const sr_layout_params *p, double *xy_out, uint64_t n_nodes);
+/* the outputs, formed here so that every front end writes the same bytes; *text is malloc'ed (sr_free).
+ * TSV (the columns of `odgi layout --tsv`): "idx\tX\tY", rows 2v and 2v + 1 for the v-th node, %.4f.
+ * SVG: one <line> per node, one thin <line> per L line from the out-end of its from-handle to the in-end of its
+ * to-handle, viewBox = bounding box + 2 %. */
+int sr_layout_tsv(const double *xy, uint64_t n, char **text);
+int sr_layout_svg(const char *gfa_in, const double *xy, uint64_t n, char **text);
+/* quality of a layout on the host in double: out[0] sampled path stress = mean of ((|p_i - p_j| - d) / d)^2 over the pairs
+ * that `samples` term draws select (cooling off, a stream of its own from `seed`), out[1] mean | |end1 - end0| - len | over
+ * the nodes in bp, out[2] pairs used, out[3] 0 */
+int sr_layout_quality(const char *gfa_in, const double *xy, uint64_t n, uint64_t seed, uint64_t samples, double out[4]);
+/* the calling thread's last sr_layout_gfa: [0] SGD ms (device: hipEvents), [1] terms per iteration, [2] iterations,
+ * [3] sub-rounds per iteration, [4] nodes, [5] path steps, [6] wall time of the stage in ms on a host clock.  Returns the
+ * number of slots written. */
+int sr_layout_stats(double *out, uint32_t cap);
+/* tests: the parameters sr_layout_gfa resolves for gfa_in, and the selection of terms t0 .. t0 + count - 1 of iteration k
+ * (cooling: 0 / 1): end points i, j (2 * node index + end; 0xffffffff = skipped draw) and their path distance d */
+int sr_layout_resolve(const char *gfa_in, const sr_layout_params *p, sr_layout_params *resolved);
+int sr_layout_select_host(const char *gfa_in, const sr_layout_params *p, uint64_t k, uint64_t t0, uint64_t count, int cooling,
+                          uint32_t *i_out, uint32_t *j_out, double *d_out);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

@@ -43,6 +43,11 @@ def main(argv=None):
                          "what the main alignment paid for the gap (0 = off; N <= -k is the sensible range)")
     ap.add_argument("--stats", default=None, metavar="FILE",
                     help="write the statistics report of the final GFA (summary, depth, path similarity, layout error) to FILE")
+    ap.add_argument("--layout", default=None, metavar="FILE",
+                    help="write the 2-D path-guided SGD layout of the final GFA (two end points per node) to FILE as TSV")
+    ap.add_argument("--layout-svg", default=None, metavar="FILE", help="draw the same layout to FILE as SVG")
+    ap.add_argument("--layout-seed", type=int, default=9399220)
+    ap.add_argument("--layout-iter-max", type=int, default=30)
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -86,7 +91,8 @@ def main(argv=None):
                 skip_groom=ns.skip_groom, skip_topo=ns.skip_topo,
                 aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative,
                 patch_inversions=ns.patch_inversions, inversion_min_size=ns.inversion_min_size,
-                inversion_join=ns.inversion_join, stats=ns.stats)
+                inversion_join=ns.inversion_join, stats=ns.stats, layout=ns.layout, layout_svg=ns.layout_svg,
+                layout_seed=ns.layout_seed, layout_iter_max=ns.layout_iter_max)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

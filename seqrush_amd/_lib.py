@@ -39,6 +39,8 @@ EXPORTS = [
     "sr_graph_stats_gfa", "sr_graph_stats_free", "sr_graph_stats_report", "sr_stats_sq_sums_host",
     "sr_mirror_map", "sr_mirror_bt_pick", "sr_mirror_bt_rank_transposed", "sr_mirror_bt_tie_host", "sr_mirror_bp_pick_host",
     "sr_ctx_orientation_scores",
+    "sr_layout_params_default", "sr_layout_gfa", "sr_layout_tsv", "sr_layout_svg", "sr_layout_quality", "sr_layout_stats",
+    "sr_layout_resolve", "sr_layout_select_host",
 ]
 
 
@@ -71,6 +73,16 @@ class SortParamsC(C.Structure):
         ("eta_max", C.c_double), ("cooling_start", C.c_double), ("space", C.c_uint64), ("space_max", C.c_uint64),
         ("space_quant", C.c_uint64), ("min_term_updates", C.c_uint64), ("terms_per_round", C.c_uint64),
         ("skip_sgd", C.c_int32), ("skip_groom", C.c_int32), ("skip_topo", C.c_int32), ("device", C.c_int32),
+    ]
+
+
+class LayoutParamsC(C.Structure):
+    """sr_layout_params (include/seqrush_amd.h, 2-D layout)"""
+    _fields_ = [
+        ("seed", C.c_uint64), ("iter_max", C.c_uint64), ("theta", C.c_double), ("eps", C.c_double),
+        ("eta_max", C.c_double), ("cooling_start", C.c_double), ("space", C.c_uint64), ("space_max", C.c_uint64),
+        ("space_quant", C.c_uint64), ("min_term_updates", C.c_uint64), ("terms_per_round", C.c_uint64),
+        ("device", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -253,6 +265,15 @@ def load():
     L.sr_graph_stats_free.argtypes = [PGS]; L.sr_graph_stats_free.restype = None
     L.sr_graph_stats_report.argtypes = [PGS, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.sr_stats_sq_sums_host.argtypes = [C.POINTER(u64), u64, C.POINTER(u64)]
+    LP = C.POINTER(LayoutParamsC)
+    L.sr_layout_params_default.argtypes = [LP]; L.sr_layout_params_default.restype = None
+    L.sr_layout_gfa.argtypes = [C.c_char_p, LP, PD, u64]
+    L.sr_layout_tsv.argtypes = [PD, u64, C.POINTER(vp)]
+    L.sr_layout_svg.argtypes = [C.c_char_p, PD, u64, C.POINTER(vp)]
+    L.sr_layout_quality.argtypes = [C.c_char_p, PD, u64, u64, u64, PD]
+    L.sr_layout_stats.argtypes = [PD, C.c_uint32]
+    L.sr_layout_resolve.argtypes = [C.c_char_p, LP, LP]
+    L.sr_layout_select_host.argtypes = [C.c_char_p, LP, u64, u64, u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), PD]
     PI = C.POINTER(C.c_int)
     L.sr_mirror_map.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                 C.POINTER(C.c_uint32), C.POINTER(u64)]

@@ -79,12 +79,13 @@ static void usage() {
                     "       [-d max_divergence] [-x none|auto|random:F|connectivity:P|tree:kn[,kf[,rf[,k]]]] [-p in.paf] [--output-alignments out.paf] --no-sort|--sort [--no-compact] [--compact-on host|device] [--device N]\n"
                     "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
                     "       [--patch-inversions [--inversion-min-size N] [--inversion-join N]] [--stats report.tsv]\n"
+                    "       [--layout graph.lay.tsv] [--layout-svg graph.svg] [--layout-seed N] [--layout-iter-max N]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave", stats_out;
+                aligner = "allwave", stats_out, layout_out, layout_svg_out;
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
@@ -94,6 +95,8 @@ int main(int argc, char **argv) {
     bool inv_join_given = false;
     sr_sort_params sp;
     sr_sort_params_default(&sp);
+    sr_layout_params lp;
+    sr_layout_params_default(&lp);
     // multi-GPU without a collective library in this host: every process aligns one shard (--shard R/N) and writes its
     // canonical labels (--labels-out); a last run merges the files (--labels-in, repeatable) and writes the graph.
     // (With RCCL at hand the exchange is one all-gather: python -m seqrush_amd --gpus N, bench.py.)
@@ -137,6 +140,10 @@ int main(int argc, char **argv) {
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--iterative") iterative = true;
         else if (a == "--stats") stats_out = val("--stats");
+        else if (a == "--layout") layout_out = val("--layout");
+        else if (a == "--layout-svg") layout_svg_out = val("--layout-svg");
+        else if (a == "--layout-seed") lp.seed = strtoull(val("--layout-seed"), nullptr, 10);
+        else if (a == "--layout-iter-max") lp.iter_max = strtoull(val("--layout-iter-max"), nullptr, 10);
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
             const char *v = val("--inversion-min-size");
@@ -369,6 +376,32 @@ int main(int argc, char **argv) {
         printf("Statistics written to %s\n", stats_out.c_str());
         if (verbose) printf("Statistics stage: %llu us on device %d\n", (unsigned long long)gs->stats_us, device);
         sr_graph_stats_free(gs);
+    }
+    if (!layout_out.empty() || !layout_svg_out.empty()) {    // the 2-D layout of the text just written
+        uint64_t n_seg = 0;
+        for (const char *q = gfa; *q;) {
+            if (q[0] == 'S' && q[1] == '\t') n_seg++;
+            const char *eol = strchr(q, '\n');
+            q = eol ? eol + 1 : q + strlen(q);
+        }
+        lp.device = device;
+        std::vector<double> xy(4 * n_seg + 1);
+        char *tsv = nullptr, *svg = nullptr;
+        if (sr_layout_gfa(gfa, &lp, xy.data(), n_seg) || (!layout_out.empty() && sr_layout_tsv(xy.data(), n_seg, &tsv)) ||
+            (!layout_svg_out.empty() && sr_layout_svg(gfa, xy.data(), n_seg, &svg))) {
+            fprintf(stderr, "Error: %s\n", sr_last_error());
+            sr_free(tsv); sr_free(gfa);
+            return 1;
+        }
+        if (tsv) { std::ofstream lo(layout_out, std::ios::binary); lo << tsv; }
+        if (svg) { std::ofstream lo(layout_svg_out, std::ios::binary); lo << svg; }
+        sr_free(tsv); sr_free(svg);
+        printf("Layout written to %s\n", (!layout_out.empty() ? layout_out : layout_svg_out).c_str());
+        if (verbose) {
+            double st[7] = {0};
+            sr_layout_stats(st, 7);
+            printf("Layout stage: SGD %.3f ms, stage %.3f ms on device %d\n", st[0], st[6], device);
+        }
     }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   check, SeqRushError)
+                   LayoutParamsC, check, SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -53,6 +53,10 @@ class Args:
     inversion_min_size: int = 0             # added: --inversion-min-size N (0 = 2 * min_match_length)
     inversion_join: int = 0                 # added: --inversion-join J: join gaps across match islands shorter than J (0 = off)
     stats: Optional[str] = None             # added: --stats FILE: the statistics report of the final GFA
+    layout: Optional[str] = None            # added: --layout FILE: 2-D layout of the final GFA as TSV
+    layout_svg: Optional[str] = None        # added: --layout-svg FILE: the same layout drawn as SVG
+    layout_seed: int = 9399220              # added: --layout-seed N
+    layout_iter_max: int = 30               # added: --layout-iter-max N
 
 
 @dataclasses.dataclass
@@ -663,6 +667,120 @@ def stats_sq_sums_host(values):
     return tuple(int(v) for v in out)
 
 
+LAYOUT_STATS = ("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
+
+
+def _layout_params(params) -> LayoutParamsC:
+    if isinstance(params, LayoutParamsC):
+        return params
+    lp = LayoutParamsC()
+    _lib.load().sr_layout_params_default(C.byref(lp))
+    for k, v in params.items():
+        if k == "reserved" or not hasattr(lp, k):
+            raise AttributeError(k)
+        setattr(lp, k, v)
+    return lp
+
+
+def _n_segments(text: str) -> int:
+    return sum(1 for line in text.split("\n") if line.startswith("S\t"))
+
+
+def _pd(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _xy(xy, n=None):
+    a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    if a.size % 4 or (n is not None and a.size != 4 * n):
+        raise SeqRushError(-1, "a layout has 4 values per node: x0 y0 x1 y1")
+    return a, a.size // 4
+
+
+def _take_text(out) -> str:
+    res = C.cast(out, C.c_char_p).value.decode()
+    _lib.load().sr_free(out)
+    return res
+
+
+def layout_gfa(text: str, n_nodes: Optional[int] = None, **params) -> np.ndarray:
+    """the 2-D path-guided SGD layout of any GFA with S / L / P lines and numeric node ids.
+    params: sr_layout_params fields (device >= 0: that GPU, -1: the host twin with the same bits, -2: the sequential
+    yardstick).  -> float64 array [nodes, 4]: x0 y0 x1 y1 per node in ascending id order.  n_nodes: the number of nodes
+    the caller expects (default: the S lines of text)"""
+    lp = _layout_params(params)
+    n = _n_segments(text) if n_nodes is None else int(n_nodes)
+    out = np.zeros(max(4 * n, 1), dtype=np.float64)
+    check(_lib.load().sr_layout_gfa(text.encode(), C.byref(lp), _pd(out), n))
+    return out[:4 * n].reshape(n, 4)
+
+
+def layout_tsv(xy) -> str:
+    """`idx X Y` rows of a layout (two per node), formatted by the library"""
+    a, n = _xy(xy)
+    out = C.c_void_p()
+    check(_lib.load().sr_layout_tsv(_pd(a), n, C.byref(out)))
+    return _take_text(out)
+
+
+def layout_svg(text: str, xy) -> str:
+    """the layout drawn as SVG: one line per node, one thin line per L line of text; formatted by the library"""
+    a, n = _xy(xy)
+    out = C.c_void_p()
+    check(_lib.load().sr_layout_svg(text.encode(), _pd(a), n, C.byref(out)))
+    return _take_text(out)
+
+
+def layout_quality(text: str, xy, seed: int = 1, samples: int = 200000) -> dict:
+    """sampled path stress and mean node length error of a layout (host, double) -> dict(stress, node_len_err, pairs)"""
+    a, n = _xy(xy)
+    out = np.zeros(4, dtype=np.float64)
+    check(_lib.load().sr_layout_quality(text.encode(), _pd(a), n, int(seed), int(samples), _pd(out)))
+    return dict(stress=float(out[0]), node_len_err=float(out[1]), pairs=int(out[2]))
+
+
+def layout_stats() -> dict:
+    """LAYOUT_STATS of the calling thread's last layout_gfa"""
+    out = (C.c_double * 7)()
+    n = _lib.load().sr_layout_stats(out, 7)
+    if n < 0:
+        check(n)
+    return {k: float(out[i]) for i, k in enumerate(LAYOUT_STATS)}
+
+
+def layout_resolve(text: str, **params) -> dict:
+    """tests: the parameters layout_gfa resolves for text"""
+    lp = _layout_params(params)
+    res = LayoutParamsC()
+    check(_lib.load().sr_layout_resolve(text.encode(), C.byref(lp), C.byref(res)))
+    return {f: getattr(res, f) for f, _ in LayoutParamsC._fields_ if f != "reserved"}
+
+
+def layout_select(text: str, k: int, t0: int, count: int, cooling: bool = False, **params):
+    """tests: the selection of terms t0 .. t0 + count - 1 of iteration k -> list of (i, j, d), None for a skipped draw"""
+    lp = _layout_params(params)
+    i = np.zeros(max(count, 1), dtype=np.uint32); j = np.zeros(max(count, 1), dtype=np.uint32)
+    d = np.zeros(max(count, 1), dtype=np.float64)
+    check(_lib.load().sr_layout_select_host(text.encode(), C.byref(lp), k, t0, count, 1 if cooling else 0,
+                                            i.ctypes.data_as(C.POINTER(C.c_uint32)), j.ctypes.data_as(C.POINTER(C.c_uint32)), _pd(d)))
+    return [None if int(i[q]) == 0xffffffff else (int(i[q]), int(j[q]), float(d[q])) for q in range(count)]
+
+
+def write_layout(text: str, args: "Args"):
+    """the --layout / --layout-svg stage of both Python front ends on the final GFA text"""
+    xy = layout_gfa(text, seed=args.layout_seed, iter_max=args.layout_iter_max, device=args.device)
+    if args.layout:
+        with open(args.layout, "w") as fh:
+            fh.write(layout_tsv(xy))
+    if args.layout_svg:
+        with open(args.layout_svg, "w") as fh:
+            fh.write(layout_svg(text, xy))
+    print(f"Layout written to {args.layout or args.layout_svg}")
+    if args.verbose:
+        st = layout_stats()
+        print(f"Layout stage: SGD {st['sgd_ms']:.3f} ms, stage {st['stage_ms']:.3f} ms on device {args.device}")
+
+
 def sgd_layout(text: str, **params) -> np.ndarray:
     """the path-guided SGD positions of a GFA's nodes (ascending id order) -> float64 array"""
     L = _lib.load()
@@ -890,6 +1008,8 @@ class SeqRush:
             print(f"Statistics written to {args.stats}")
             if args.verbose:
                 print(f"Statistics stage: {st['stats_us']} us on device {args.device}")
+        if args.layout or args.layout_svg:
+            write_layout(text, args)
 
 
 def run_seqrush(args: Args):
