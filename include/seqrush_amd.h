@@ -576,6 +576,53 @@ int sr_layout_resolve(const char *gfa_in, const sr_layout_params *p, sr_layout_p
 int sr_layout_select_host(const char *gfa_in, const sr_layout_params *p, uint64_t k, uint64_t t0, uint64_t count, int cooling,
                           uint32_t *i_out, uint32_t *j_out, double *d_out);
 
+/* -------- path-by-bin coverage (`--bin FILE`, `--viz FILE.png`) ---------------------------------
+ * What `odgi bin` writes and `odgi viz` draws, of any GFA with S / L / P lines and numeric node ids as the parser of
+ * sr_sort_gfa reads it: nodes 1..V in ascending id order laid end to end give the pangenome sequence of `length` bp, cut
+ * into bins of bin_width bp (the last one may be shorter).  cov[p * bins + b] = base pairs of bin b that the steps of path p
+ * cover (a path that revisits a node counts every visit), inv = those of them covered by reverse steps.
+ * device >= 0: HIP kernels on that device (sr_bin.hip); SR_BIN_DEVICE_HOST: plain loops on the host.  Both give the same
+ * integers.  Limits of the graph as for the statistics (2^30 nodes, 2^31 steps and bases); paths * bins above 2^26:
+ * SR_ERR_UNSUPPORTED.  An empty graph gives bins = 0 and empty tables. */
+#define SR_BIN_DEVICE_HOST (-1)
+typedef struct {
+    uint64_t bin_width, bins;   /* exactly one non-zero, else SR_ERR_INVALID; bins = n: bin_width = ceil(length / n) */
+} sr_bin_params;
+typedef struct {
+    uint64_t length, paths, bins, bin_width;            /* bins = ceil(length / bin_width): may be below the count asked for */
+    uint64_t *cov, *inv;                                /* [paths * bins] */
+    uint64_t bin_us;                                    /* the stage: hipEvents on a device, host clock for the twin */
+    uint64_t kernel_us[3];                              /* position scan, steps, download of the tables */
+} sr_path_bins;
+int sr_path_bins_gfa(const char *gfa_in, const sr_bin_params *p, int device, sr_path_bins **out);
+void sr_path_bins_free(sr_path_bins *b);
+/* The outputs, formed here so that every front end writes the same bytes; names: one per path, NULL = path indices;
+ * *text, *rgb and *png are malloc'ed (sr_free).
+ * TSV: a `#` line with bin_width, bins, length and paths, the header "path bin cov_bp inv_bp mean_cov mean_inv", then one row
+ * per cell with cov_bp > 0 by path in file order, then by bin (1-based, as in `odgi bin`); mean_cov = cov / length of the
+ * bin, mean_inv = inv / cov, both %.6f: the only floats. */
+int sr_path_bins_tsv(const sr_path_bins *b, const char *const *names, char **text);
+/* Image: `bins` pixels wide, paths * path_height + (paths - 1) * path_gap high, path p a band in file order from the top,
+ * gap rows and empty cells white; 3 bytes per pixel, rows from the top.  More than 2^30 bytes: SR_ERR_UNSUPPORTED.
+ * path: the path's colour (a hash of its name) blended towards white by min(cov, bin length) / bin length;
+ * strand: red where more than half of the covered base pairs are reverse, else black;
+ * depth: grey, black at a mean coverage of depth_max.  All in integer arithmetic (sr_bin_rule.h). */
+#define SR_VIZ_MODE_PATH 0
+#define SR_VIZ_MODE_STRAND 1
+#define SR_VIZ_MODE_DEPTH 2
+typedef struct {
+    int mode;                   /* SR_VIZ_MODE_*; default path */
+    uint32_t path_height;       /* 10: rows per path, >= 1 */
+    uint32_t path_gap;          /* 1: white rows between paths */
+    uint32_t depth_max;         /* 4: depth mode, >= 1 */
+} sr_viz_params;
+void sr_viz_params_default(sr_viz_params *p);
+int sr_path_bins_rgb(const sr_path_bins *b, const char *const *names, const sr_viz_params *p, uint8_t **rgb, uint32_t *width,
+                     uint32_t *height);
+/* the same image as a PNG: 8-bit RGB, not interlaced, filter 0 on every row, a zlib stream of stored blocks (no
+ * compression, no dependency).  An image without a pixel (no path or no bin): SR_ERR_INVALID. */
+int sr_path_bins_png(const sr_path_bins *b, const char *const *names, const sr_viz_params *p, uint8_t **png, uint64_t *size);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

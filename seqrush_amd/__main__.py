@@ -48,6 +48,18 @@ def main(argv=None):
     ap.add_argument("--layout-svg", default=None, metavar="FILE", help="draw the same layout to FILE as SVG")
     ap.add_argument("--layout-seed", type=int, default=9399220)
     ap.add_argument("--layout-iter-max", type=int, default=30)
+    ap.add_argument("--bin", default=None, metavar="FILE",
+                    help="write the path-by-bin coverage table of the final GFA (what `odgi bin` writes) to FILE as TSV")
+    ap.add_argument("--bin-width", type=int, default=None, metavar="W", help="bin width of --bin in bp")
+    ap.add_argument("--bin-count", type=int, default=None, metavar="N", help="number of bins of --bin (default 1500)")
+    ap.add_argument("--viz", default=None, metavar="FILE.png",
+                    help="draw the paths of the final GFA over bins of its sequence (what `odgi viz` draws) to FILE.png")
+    ap.add_argument("--viz-width", type=int, default=None, metavar="N", help="bins = pixels across (default 1500)")
+    ap.add_argument("--viz-path-height", type=int, default=None, metavar="H", help="rows per path (default 10)")
+    ap.add_argument("--viz-path-gap", type=int, default=None, metavar="G", help="white rows between paths (default 1)")
+    ap.add_argument("--viz-mode", choices=("path", "strand", "depth"), default=None,
+                    help="path: coverage in the path's colour; strand: reverse bins red; depth: grey by mean coverage")
+    ap.add_argument("--viz-depth-max", type=int, default=None, metavar="D", help="depth mode: the mean coverage drawn black (default 4)")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -58,6 +70,24 @@ def main(argv=None):
         return 1
     if ns.compact_on == "device" and ns.no_compact:
         print("Error: --compact-on device and --no-compact exclude each other", file=sys.stderr)
+        return 1
+    # the rules of seqrush_mi355x: an option of --bin / --viz needs its flag, and a given value is a positive integer
+    # (--viz-path-gap: non-negative)
+    given = {f: getattr(ns, f.lstrip("-").replace("-", "_")) for f in
+             ("--bin-width", "--bin-count", "--viz-width", "--viz-path-height", "--viz-path-gap", "--viz-mode", "--viz-depth-max")}
+    for flag, v in given.items():
+        if v is None:
+            continue
+        owner = flag[:5]
+        if getattr(ns, owner[2:]) is None:
+            print(f"Error: {flag} is an option of {owner}: give both", file=sys.stderr)
+            return 1
+        low = 0 if flag == "--viz-path-gap" else 1
+        if flag != "--viz-mode" and not low <= v <= (0xffffffff if owner == "--viz" else 2 ** 64 - 1):
+            print(f"Error: {flag} needs a {'non-negative' if low == 0 else 'positive'} integer, got '{v}'", file=sys.stderr)
+            return 1
+    if ns.bin_width is not None and ns.bin_count is not None:
+        print("Error: --bin-width and --bin-count exclude each other", file=sys.stderr)
         return 1
     if ns.iterative and (ns.paf is not None or ns.gpus > 1):
         # before any rank starts: the stop rule is global and sequential, and -p has no alignment stage to stop
@@ -92,7 +122,10 @@ def main(argv=None):
                 aligner=ns.aligner, verbose=ns.verbose, device=ns.device, gpus=ns.gpus, iterative=ns.iterative,
                 patch_inversions=ns.patch_inversions, inversion_min_size=ns.inversion_min_size,
                 inversion_join=ns.inversion_join, stats=ns.stats, layout=ns.layout, layout_svg=ns.layout_svg,
-                layout_seed=ns.layout_seed, layout_iter_max=ns.layout_iter_max)
+                layout_seed=ns.layout_seed, layout_iter_max=ns.layout_iter_max, bin=ns.bin, bin_width=ns.bin_width or 0,
+                bin_count=ns.bin_count or 0, viz=ns.viz, viz_width=ns.viz_width or 1500,
+                viz_path_height=ns.viz_path_height or 10, viz_path_gap=1 if ns.viz_path_gap is None else ns.viz_path_gap,
+                viz_mode=ns.viz_mode or "path", viz_depth_max=ns.viz_depth_max or 4)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

@@ -41,6 +41,7 @@ EXPORTS = [
     "sr_ctx_orientation_scores",
     "sr_layout_params_default", "sr_layout_gfa", "sr_layout_tsv", "sr_layout_svg", "sr_layout_quality", "sr_layout_stats",
     "sr_layout_resolve", "sr_layout_select_host",
+    "sr_path_bins_gfa", "sr_path_bins_free", "sr_path_bins_tsv", "sr_viz_params_default", "sr_path_bins_rgb", "sr_path_bins_png",
 ]
 
 
@@ -132,6 +133,23 @@ class GraphStatsC(C.Structure):
                 ("path_sq", C.POINTER(C.c_uint64)),
                 ("total_pairs", C.c_uint64), ("total_abs", C.c_uint64), ("total_len", C.c_uint64), ("total_sq", C.c_uint64 * 3),
                 ("stats_us", C.c_uint64), ("kernel_us", C.c_uint64 * 5)]
+
+
+class BinParamsC(C.Structure):
+    """sr_bin_params (include/seqrush_amd.h, path-by-bin coverage)"""
+    _fields_ = [("bin_width", C.c_uint64), ("bins", C.c_uint64)]
+
+
+class PathBinsC(C.Structure):
+    """sr_path_bins"""
+    _fields_ = [("length", C.c_uint64), ("paths", C.c_uint64), ("bins", C.c_uint64), ("bin_width", C.c_uint64),
+                ("cov", C.POINTER(C.c_uint64)), ("inv", C.POINTER(C.c_uint64)),
+                ("bin_us", C.c_uint64), ("kernel_us", C.c_uint64 * 3)]
+
+
+class VizParamsC(C.Structure):
+    """sr_viz_params"""
+    _fields_ = [("mode", C.c_int), ("path_height", C.c_uint32), ("path_gap", C.c_uint32), ("depth_max", C.c_uint32)]
 
 
 class AlignmentsC(C.Structure):
@@ -274,6 +292,13 @@ def load():
     L.sr_layout_stats.argtypes = [PD, C.c_uint32]
     L.sr_layout_resolve.argtypes = [C.c_char_p, LP, LP]
     L.sr_layout_select_host.argtypes = [C.c_char_p, LP, u64, u64, u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), PD]
+    PPB, PVP = C.POINTER(PathBinsC), C.POINTER(VizParamsC)
+    L.sr_path_bins_gfa.argtypes = [C.c_char_p, C.POINTER(BinParamsC), i32, C.POINTER(PPB)]
+    L.sr_path_bins_free.argtypes = [PPB]; L.sr_path_bins_free.restype = None
+    L.sr_path_bins_tsv.argtypes = [PPB, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.sr_viz_params_default.argtypes = [PVP]; L.sr_viz_params_default.restype = None
+    L.sr_path_bins_rgb.argtypes = [PPB, C.POINTER(C.c_char_p), PVP, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.sr_path_bins_png.argtypes = [PPB, C.POINTER(C.c_char_p), PVP, C.POINTER(vp), C.POINTER(u64)]
     PI = C.POINTER(C.c_int)
     L.sr_mirror_map.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                 C.POINTER(C.c_uint32), C.POINTER(u64)]

@@ -80,12 +80,17 @@ static void usage() {
                     "       [--sort-seed N] [--sgd-iter-max N] [--skip-sgd] [--skip-groom] [--skip-topo] [--iterative] [-v]\n"
                     "       [--patch-inversions [--inversion-min-size N] [--inversion-join N]] [--stats report.tsv]\n"
                     "       [--layout graph.lay.tsv] [--layout-svg graph.svg] [--layout-seed N] [--layout-iter-max N]\n"
+                    "       [--bin bins.tsv [--bin-width W | --bin-count N]] [--viz graph.png [--viz-width N] [--viz-path-height H]\n"
+                    "       [--viz-path-gap G] [--viz-mode path|strand|depth] [--viz-depth-max D]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave", stats_out, layout_out, layout_svg_out;
+                aligner = "allwave", stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt;
+    unsigned long long bin_width = 0, bin_count = 0, viz_width = 1500;
+    sr_viz_params vp;
+    sr_viz_params_default(&vp);
     long long k = 0;
     double max_div = -1.0;
     int device = 0;
@@ -144,6 +149,32 @@ int main(int argc, char **argv) {
         else if (a == "--layout-svg") layout_svg_out = val("--layout-svg");
         else if (a == "--layout-seed") lp.seed = strtoull(val("--layout-seed"), nullptr, 10);
         else if (a == "--layout-iter-max") lp.iter_max = strtoull(val("--layout-iter-max"), nullptr, 10);
+        else if (a == "--bin") bin_out = val("--bin");
+        else if (a == "--viz") viz_out = val("--viz");
+        else if (a == "--bin-width" || a == "--bin-count" || a == "--viz-width" || a == "--viz-path-height" || a == "--viz-path-gap" ||
+                 a == "--viz-depth-max") {
+            const char *v = val(a.c_str());
+            char *end = nullptr;
+            const unsigned long long n = strtoull(v, &end, 10);
+            (a.compare(0, 5, "--bin") == 0 ? bin_opt : viz_opt) = a;
+            const bool zero_ok = a == "--viz-path-gap";
+            if (*v < '0' || *v > '9' || *end != 0 || (n == 0 && !zero_ok) || (a.compare(0, 5, "--viz") == 0 && n > 0xffffffffULL)) {
+                fprintf(stderr, "Error: %s needs a %s integer, got '%s'\n", a.c_str(), zero_ok ? "non-negative" : "positive", v);
+                return 1;
+            }
+            if (a == "--bin-width") bin_width = n;
+            else if (a == "--bin-count") bin_count = n;
+            else if (a == "--viz-width") viz_width = n;
+            else if (a == "--viz-path-height") vp.path_height = (uint32_t)n;
+            else if (a == "--viz-path-gap") vp.path_gap = (uint32_t)n;
+            else vp.depth_max = (uint32_t)n;
+        }
+        else if (a == "--viz-mode") {
+            const std::string m = val("--viz-mode");
+            viz_opt = a;
+            if (m != "path" && m != "strand" && m != "depth") { fprintf(stderr, "Error: --viz-mode takes path, strand or depth\n"); return 1; }
+            vp.mode = m == "path" ? SR_VIZ_MODE_PATH : m == "strand" ? SR_VIZ_MODE_STRAND : SR_VIZ_MODE_DEPTH;
+        }
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
             const char *v = val("--inversion-min-size");
@@ -192,6 +223,12 @@ int main(int argc, char **argv) {
     }
     if (!labels_in.empty() && (shard_count > 1 || !labels_out.empty())) { fprintf(stderr, "Error: --labels-in is the merge run: no --shard / --labels-out\n"); return 1; }
     if (aligner != "allwave" && aligner != "AllWave") { fprintf(stderr, "Error: aligner '%s' is out of scope; only 'allwave'\n", aligner.c_str()); return 1; }
+    if ((!bin_opt.empty() && bin_out.empty()) || (!viz_opt.empty() && viz_out.empty())) {
+        const bool b = !bin_opt.empty() && bin_out.empty();
+        fprintf(stderr, "Error: %s is an option of %s: give both\n", (b ? bin_opt : viz_opt).c_str(), b ? "--bin" : "--viz");
+        return 1;
+    }
+    if (bin_width && bin_count) { fprintf(stderr, "Error: --bin-width and --bin-count exclude each other\n"); return 1; }
     if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
     if (compact_dev && no_compact) { fprintf(stderr, "Error: --compact-on device and --no-compact exclude each other\n"); return 1; }
     if (!no_sort && !sort) { fprintf(stderr, "Error: only --no-sort output is implemented by default; pass --sort for the Ygs layout; compaction runs unless --no-compact\n"); return 1; }
@@ -349,8 +386,9 @@ int main(int argc, char **argv) {
     sr_ctx_destroy(ctx);
     std::ofstream o(output, std::ios::binary);
     o << gfa;
-    if (!stats_out.empty()) {                                // the report of the text just written (DESIGN.md section 11)
-        std::vector<std::string> pnames;                     // names of the P lines, as the library's parser reads them
+    std::vector<std::string> pnames;                         // names of the P lines, as the library's parser reads them
+    std::vector<const char *> pn;
+    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty()) {
         for (const char *q = gfa; *q;) {
             const char *eol = strchr(q, '\n');
             if (!eol) eol = q + strlen(q);
@@ -360,8 +398,9 @@ int main(int argc, char **argv) {
             }
             q = *eol ? eol + 1 : eol;
         }
-        std::vector<const char *> pn;
         for (const auto &n : pnames) pn.push_back(n.c_str());
+    }
+    if (!stats_out.empty()) {                                // the report of the text just written (DESIGN.md section 11)
         sr_graph_stats *gs = nullptr;
         char *report = nullptr;
         if (sr_graph_stats_gfa(gfa, device, &gs)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_free(gfa); return 1; }
@@ -402,6 +441,29 @@ int main(int argc, char **argv) {
             sr_layout_stats(st, 7);
             printf("Layout stage: SGD %.3f ms, stage %.3f ms on device %d\n", st[0], st[6], device);
         }
+    }
+    for (int pass = 0; pass < 2; pass++) {                   // the path-by-bin tables of the text just written
+        const std::string &dst = pass == 0 ? bin_out : viz_out;
+        if (dst.empty()) continue;
+        sr_bin_params bp = {0, 0};
+        if (pass == 0) { bp.bin_width = bin_width; bp.bins = bin_width ? 0 : (bin_count ? bin_count : 1500); }
+        else bp.bins = viz_width;
+        sr_path_bins *pb = nullptr;
+        char *tsv = nullptr;
+        uint8_t *png = nullptr;
+        uint64_t png_size = 0;
+        if (sr_path_bins_gfa(gfa, &bp, device, &pb)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_free(gfa); return 1; }
+        if (pn.size() != pb->paths || (pass == 0 ? sr_path_bins_tsv(pb, pn.data(), &tsv) : sr_path_bins_png(pb, pn.data(), &vp, &png, &png_size))) {
+            fprintf(stderr, "Error: %s\n", pn.size() != pb->paths ? "bins: path names do not match the paths" : sr_last_error());
+            sr_path_bins_free(pb); sr_free(gfa);
+            return 1;
+        }
+        std::ofstream bo(dst, std::ios::binary);
+        if (pass == 0) bo << tsv; else bo.write((const char *)png, (std::streamsize)png_size);
+        sr_free(tsv); sr_free(png);
+        printf("%s written to %s\n", pass == 0 ? "Bins" : "Visualization", dst.c_str());
+        if (verbose) printf("Bin stage: %llu us on device %d\n", (unsigned long long)pb->bin_us, device);
+        sr_path_bins_free(pb);
     }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());

@@ -43,5 +43,8 @@ int sr_graph_parse_gfa(const char *text, SrGraph &g, std::vector<std::string> &n
 // the statistics stage on a parsed graph (sr_stats.hip): device >= 0 on that HIP device and `stream` (null: a stream of its
 // own), -1 the host twin; *out as sr_graph_stats_gfa returns it
 int sr_graph_stats_run(const SrGraph &g, int device, void *stream, sr_graph_stats **out);
+// the path-by-bin tables of a parsed graph (sr_bin.hip), with the same meaning of device and stream; *out as
+// sr_path_bins_gfa returns it
+int sr_graph_bins_run(const SrGraph &g, const sr_bin_params &prm, int device, void *stream, sr_path_bins **out);
 int sr_fail(int code, const std::string &msg);     // sr_host.cpp: sets sr_last_error()
 void sr_sort_note_write_ms(double ms);              // slot [3] of sr_sort_stats(), also added to the stage's wall time [9]

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   LayoutParamsC, check, SeqRushError)
+                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, check, SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -57,6 +57,15 @@ class Args:
     layout_svg: Optional[str] = None        # added: --layout-svg FILE: the same layout drawn as SVG
     layout_seed: int = 9399220              # added: --layout-seed N
     layout_iter_max: int = 30               # added: --layout-iter-max N
+    bin: Optional[str] = None               # added: --bin FILE: path-by-bin coverage of the final GFA as TSV
+    bin_width: int = 0                      # added: --bin-width W | --bin-count N (neither: 1500 bins)
+    bin_count: int = 0
+    viz: Optional[str] = None               # added: --viz FILE.png: the same table drawn, --viz-width bins wide
+    viz_width: int = 1500
+    viz_path_height: int = 10
+    viz_path_gap: int = 1
+    viz_mode: str = "path"                  # path | strand | depth
+    viz_depth_max: int = 4
 
 
 @dataclasses.dataclass
@@ -667,6 +676,142 @@ def stats_sq_sums_host(values):
     return tuple(int(v) for v in out)
 
 
+SR_BIN_DEVICE_HOST = -1
+BIN_KERNELS = ("scan", "steps", "download")
+VIZ_MODES = ("path", "strand", "depth")
+
+
+def _viz_params(mode="path", path_height=10, path_gap=1, depth_max=4) -> VizParamsC:
+    if mode not in VIZ_MODES:
+        raise SeqRushError(-1, f"viz mode must be one of {', '.join(VIZ_MODES)}, not {mode!r}")
+    for k, v in (("path_height", path_height), ("path_gap", path_gap), ("depth_max", depth_max)):
+        if not 0 <= int(v) < 2 ** 32:
+            raise SeqRushError(-1, f"viz {k} must be in 0 .. 2^32 - 1")
+    return VizParamsC(VIZ_MODES.index(mode), int(path_height), int(path_gap), int(depth_max))
+
+
+class PathBins:
+    """an owned sr_path_bins: the path-by-bin tables of a GFA text and the outputs the library
+    forms from them.  names default to the names of the text's P lines"""
+
+    def __init__(self, text: str, device: int = 0, bin_width: int = 0, bins: int = 0):
+        for k, v in (("bin_width", bin_width), ("bins", bins)):
+            if not 0 <= int(v) < 2 ** 64:
+                raise SeqRushError(-1, f"{k} must be in 0 .. 2^64 - 1")
+        self.L = _lib.load()
+        self.p = C.POINTER(PathBinsC)()
+        self.names = _path_names(text)
+        prm = BinParamsC(int(bin_width), int(bins))
+        check(self.L.sr_path_bins_gfa(text.encode(), C.byref(prm), int(device), C.byref(self.p)))
+
+    def close(self):
+        if self.p:
+            self.L.sr_path_bins_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _names(self, names):
+        names = self.names if names is None else list(names)
+        if len(names) != int(self.p.contents.paths):
+            raise SeqRushError(-1, "path bins: one name per path is needed")
+        arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        return C.cast(arr, C.POINTER(C.c_char_p)), arr
+
+    def as_dict(self) -> dict:
+        s = self.p.contents
+        P, B = int(s.paths), int(s.bins)
+
+        def arr(ptr):
+            return np.ctypeslib.as_array(ptr, shape=(max(P * B, 1),))[:P * B].astype(np.uint64, copy=True).reshape(P, B)
+        d = {k: int(getattr(s, k)) for k in ("length", "paths", "bins", "bin_width", "bin_us")}
+        d["cov"], d["inv"] = arr(s.cov), arr(s.inv)
+        d["kernel_us"] = dict(zip(BIN_KERNELS, (int(v) for v in s.kernel_us)))
+        return d
+
+    def tsv(self, names=None) -> str:
+        ptr, _keep = self._names(names)
+        out = C.c_void_p()
+        check(self.L.sr_path_bins_tsv(self.p, ptr, C.byref(out)))
+        return _take_text(out)
+
+    def rgb(self, names=None, **viz) -> np.ndarray:
+        ptr, _keep = self._names(names)
+        vp = _viz_params(**viz)
+        out = C.c_void_p(); w = C.c_uint32(); h = C.c_uint32()
+        check(self.L.sr_path_bins_rgb(self.p, ptr, C.byref(vp), C.byref(out), C.byref(w), C.byref(h)))
+        n = w.value * h.value * 3
+        img = np.frombuffer(C.string_at(out, n), dtype=np.uint8).reshape(h.value, w.value, 3).copy()
+        self.L.sr_free(out)
+        return img
+
+    def png(self, names=None, **viz) -> bytes:
+        ptr, _keep = self._names(names)
+        vp = _viz_params(**viz)
+        out = C.c_void_p(); n = C.c_uint64()
+        check(self.L.sr_path_bins_png(self.p, ptr, C.byref(vp), C.byref(out), C.byref(n)))
+        data = C.string_at(out, n.value)
+        self.L.sr_free(out)
+        return data
+
+
+def path_bins(text: str, device: int = 0, bin_width: int = 0, bins: int = 0) -> dict:
+    """path-by-bin coverage of any GFA with S / L / P lines and numeric node ids: give exactly one of
+    bin_width (bp) and bins (a count; the width is ceil(length / bins)).  device >= 0: HIP kernels on that device, -1: the host
+    twin (the same integers).  -> dict: length, paths, bins, bin_width; cov / inv (uint64 [paths, bins]: base pairs of the bin
+    covered by the path's steps / by its reverse steps); bin_us, kernel_us"""
+    with PathBins(text, device, bin_width, bins) as pb:
+        return pb.as_dict()
+
+
+def path_bins_tsv(text: str, device: int = 0, bin_width: int = 0, bins: int = 0) -> str:
+    """the table of path_bins() as TSV (one row per covered cell, bins 1-based), formatted by the library"""
+    with PathBins(text, device, bin_width, bins) as pb:
+        return pb.tsv()
+
+
+def path_bins_rgb(text: str, device: int = 0, bin_width: int = 0, bins: int = 0, **viz) -> np.ndarray:
+    """the table of path_bins() as an image -> uint8 [height, width = bins, 3].  viz: mode ("path", "strand", "depth"),
+    path_height, path_gap, depth_max"""
+    with PathBins(text, device, bin_width, bins) as pb:
+        return pb.rgb(**viz)
+
+
+def path_bins_png(text: str, device: int = 0, bin_width: int = 0, bins: int = 0, **viz) -> bytes:
+    """the image of path_bins_rgb() as the bytes of a PNG file"""
+    with PathBins(text, device, bin_width, bins) as pb:
+        return pb.png(**viz)
+
+
+def write_bins(text: str, args: "Args"):
+    """the --bin / --viz stage of both Python front ends on the final GFA text"""
+    if args.bin:
+        if args.bin_width and args.bin_count:
+            raise SeqRushError(-1, "--bin-width and --bin-count exclude each other")
+        kw = dict(bin_width=args.bin_width) if args.bin_width else dict(bins=args.bin_count or 1500)
+        with PathBins(text, args.device, **kw) as pb:
+            with open(args.bin, "w") as fh:
+                fh.write(pb.tsv())
+            us = int(pb.p.contents.bin_us)
+        print(f"Bins written to {args.bin}")
+        if args.verbose:
+            print(f"Bin stage: {us} us on device {args.device}")
+    if args.viz:
+        with PathBins(text, args.device, bins=args.viz_width) as pb:
+            data = pb.png(mode=args.viz_mode, path_height=args.viz_path_height, path_gap=args.viz_path_gap,
+                          depth_max=args.viz_depth_max)
+            us = int(pb.p.contents.bin_us)
+        with open(args.viz, "wb") as fh:
+            fh.write(data)
+        print(f"Visualization written to {args.viz}")
+        if args.verbose:
+            print(f"Bin stage: {us} us on device {args.device}")
+
+
 LAYOUT_STATS = ("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
 
 
@@ -1010,6 +1155,8 @@ class SeqRush:
                 print(f"Statistics stage: {st['stats_us']} us on device {args.device}")
         if args.layout or args.layout_svg:
             write_layout(text, args)
+        if args.bin or args.viz:
+            write_bins(text, args)
 
 
 def run_seqrush(args: Args):
