@@ -623,6 +623,56 @@ int sr_path_bins_rgb(const sr_path_bins *b, const char *const *names, const sr_v
  * compression, no dependency).  An image without a pixel (no path or no bin): SR_ERR_INVALID. */
 int sr_path_bins_png(const sr_path_bins *b, const char *const *names, const sr_viz_params *p, uint8_t **png, uint64_t *size);
 
+/* -------- pangenome growth (`--growth FILE`) ------------------------------------------------------
+ * How the pangenome and the core grow as genomes are added (`odgi heaps`, `panacus histgrowth`), of any GFA with S / L / P
+ * lines and numeric node ids as the parser of sr_sort_gfa reads it.  Every path belongs to one of `groups` groups
+ * (group_of[paths]; NULL: every path its own group and n_groups is ignored); a group is present on a node iff a step of
+ * one of its paths lies on it.  For permutation r of the groups and k = 1..groups, pan[r * groups + k - 1] = base pairs of the
+ * nodes on which at least one of its first k groups is present, core[...] = those on which all of them are.
+ * bp_by_groups[c] = base pairs of the nodes on which exactly c groups are present.
+ * Permutation r orders the groups by (splitmix64 hash of (seed, r, group), group) ascending (sr_growth_rule.h); if
+ * groups <= 8 and groups! <= the permutations asked for, all groups! permutations run instead, in lexicographic order
+ * (exhaustive = 1).  perm[r * groups + k - 1] = the group at rank k.
+ * device >= 0: HIP kernels on that device (sr_growth.hip); SR_GROWTH_DEVICE_HOST: plain loops on the host.  Both give the
+ * same integers.  Limits of the graph as for the statistics; more than 4096 groups, or permutations asked for x groups
+ * above 2^24: SR_ERR_UNSUPPORTED.  permutations = 0, a group_of entry >= n_groups or a group without a path:
+ * SR_ERR_INVALID.  An empty graph or one without a path gives groups = 0, empty tables and no error. */
+#define SR_GROWTH_DEVICE_HOST (-1)
+typedef struct {
+    uint64_t seed;              /* default 9399220 */
+    uint64_t permutations;      /* default 1000 */
+} sr_growth_params;
+void sr_growth_params_default(sr_growth_params *p);
+typedef struct {
+    uint64_t length, paths, groups, permutations;       /* permutations actually run (groups! when exhaustive) */
+    int32_t exhaustive, variant;                        /* variant: 0 the host loops, 1 the device kernels (lane = node word, wave = permutation) */
+    uint64_t *pan, *core;                               /* [permutations * groups], row r = permutation r, column k - 1 */
+    uint32_t *perm;                                     /* [permutations * groups], group at rank k */
+    uint64_t *bp_by_groups;                             /* [groups + 1] */
+    uint64_t growth_us, kernel_us[4];                   /* the stage; presence, histogram, ranks, growth */
+    uint64_t seed;                                      /* as given: the report names it */
+} sr_growth;
+int sr_growth_gfa(const char *gfa_in, const uint32_t *group_of, uint32_t n_groups, const sr_growth_params *p, int device,
+                  sr_growth **out);
+void sr_growth_free(sr_growth *g);
+/* groups from path names: mode 0 = every path its own group; 1 = PanSN sample (text before the first '#'); 2 = PanSN
+ * haplotype (text before the second '#'); a name without that many '#' is its own key.  Groups are numbered by first
+ * appearance in file order.  group_names (may be NULL) is malloc'ed as one block (sr_free), one string per group. */
+int sr_growth_groups(const char *const *path_names, uint64_t n_paths, int mode, uint32_t *group_of, uint32_t *n_groups,
+                     char ***group_names);
+/* closed-form expectations over all orders of the groups, in double, [groups] each:
+ * E pan(k) = sum_c bp[c] (1 - prod_{i<k} (G - c - i) / (G - i)),  E core(k) = sum_c bp[c] prod_{i<k} (c - i) / (G - i) */
+int sr_growth_expected(const uint64_t *bp_by_groups, uint32_t groups, double *pan_exp, double *core_exp);
+/* Heaps' law: least squares of log new(k) on log k, k = 2..groups, new(k) = pan_exp[k - 1] - pan_exp[k - 2], points with
+ * new(k) <= 0 skipped; new ~ kappa k^-alpha.  *points < 2: no fit, alpha = kappa = 0, SR_OK. */
+int sr_growth_fit(const double *pan_exp, uint32_t groups, double *alpha, double *kappa, uint32_t *points);
+/* The report, the only place its floats are formed; *text is malloc'ed (sr_free).  TSV: three `#` lines (groups, paths,
+ * permutations, exhaustive, seed, length; unused = bp_by_groups[0], core = bp_by_groups[groups]; alpha, kappa, points and
+ * open iff alpha <= 1, NA without a fit), the header "k pan_exp core_exp pan_mean pan_sd pan_min pan_max core_mean core_sd
+ * core_min core_max", one row per k.  Integers as integers, floats %.6f, sd = the population standard deviation over the
+ * permutations run, from sums kept in 128-bit integers. */
+int sr_growth_report(const sr_growth *g, char **text);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

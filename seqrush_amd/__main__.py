@@ -60,6 +60,12 @@ def main(argv=None):
     ap.add_argument("--viz-mode", choices=("path", "strand", "depth"), default=None,
                     help="path: coverage in the path's colour; strand: reverse bins red; depth: grey by mean coverage")
     ap.add_argument("--viz-depth-max", type=int, default=None, metavar="D", help="depth mode: the mean coverage drawn black (default 4)")
+    ap.add_argument("--growth", default=None, metavar="FILE",
+                    help="write the pangenome growth curves of the final GFA (`odgi heaps`, `panacus histgrowth`) to FILE as TSV")
+    ap.add_argument("--growth-permutations", type=int, default=None, metavar="N", help="orders of the groups sampled (default 1000)")
+    ap.add_argument("--growth-seed", type=int, default=None, metavar="N", help="seed of the sampled orders (default 9399220)")
+    ap.add_argument("--growth-group-by", choices=("path", "sample", "haplotype"), default=None,
+                    help="path: every path a genome; sample / haplotype: paths grouped by their PanSN prefix")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -84,6 +90,17 @@ def main(argv=None):
             return 1
         low = 0 if flag == "--viz-path-gap" else 1
         if flag != "--viz-mode" and not low <= v <= (0xffffffff if owner == "--viz" else 2 ** 64 - 1):
+            print(f"Error: {flag} needs a {'non-negative' if low == 0 else 'positive'} integer, got '{v}'", file=sys.stderr)
+            return 1
+    for flag in ("--growth-permutations", "--growth-seed", "--growth-group-by"):
+        v = getattr(ns, flag.lstrip("-").replace("-", "_"))
+        if v is None:
+            continue
+        if ns.growth is None:
+            print(f"Error: {flag} is an option of --growth: give both", file=sys.stderr)
+            return 1
+        low = 0 if flag == "--growth-seed" else 1
+        if flag != "--growth-group-by" and not low <= v <= 2 ** 64 - 1:
             print(f"Error: {flag} needs a {'non-negative' if low == 0 else 'positive'} integer, got '{v}'", file=sys.stderr)
             return 1
     if ns.bin_width is not None and ns.bin_count is not None:
@@ -125,7 +142,9 @@ def main(argv=None):
                 layout_seed=ns.layout_seed, layout_iter_max=ns.layout_iter_max, bin=ns.bin, bin_width=ns.bin_width or 0,
                 bin_count=ns.bin_count or 0, viz=ns.viz, viz_width=ns.viz_width or 1500,
                 viz_path_height=ns.viz_path_height or 10, viz_path_gap=1 if ns.viz_path_gap is None else ns.viz_path_gap,
-                viz_mode=ns.viz_mode or "path", viz_depth_max=ns.viz_depth_max or 4)
+                viz_mode=ns.viz_mode or "path", viz_depth_max=ns.viz_depth_max or 4, growth=ns.growth,
+                growth_permutations=ns.growth_permutations or 1000,
+                growth_seed=9399220 if ns.growth_seed is None else ns.growth_seed, growth_group_by=ns.growth_group_by or "path")
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

@@ -42,6 +42,8 @@ EXPORTS = [
     "sr_layout_params_default", "sr_layout_gfa", "sr_layout_tsv", "sr_layout_svg", "sr_layout_quality", "sr_layout_stats",
     "sr_layout_resolve", "sr_layout_select_host",
     "sr_path_bins_gfa", "sr_path_bins_free", "sr_path_bins_tsv", "sr_viz_params_default", "sr_path_bins_rgb", "sr_path_bins_png",
+    "sr_growth_params_default", "sr_growth_gfa", "sr_growth_free", "sr_growth_groups", "sr_growth_expected", "sr_growth_fit",
+    "sr_growth_report",
 ]
 
 
@@ -150,6 +152,20 @@ class PathBinsC(C.Structure):
 class VizParamsC(C.Structure):
     """sr_viz_params"""
     _fields_ = [("mode", C.c_int), ("path_height", C.c_uint32), ("path_gap", C.c_uint32), ("depth_max", C.c_uint32)]
+
+
+class GrowthParamsC(C.Structure):
+    """sr_growth_params (include/seqrush_amd.h, pangenome growth)"""
+    _fields_ = [("seed", C.c_uint64), ("permutations", C.c_uint64)]
+
+
+class GrowthC(C.Structure):
+    """sr_growth"""
+    _fields_ = [("length", C.c_uint64), ("paths", C.c_uint64), ("groups", C.c_uint64), ("permutations", C.c_uint64),
+                ("exhaustive", C.c_int32), ("variant", C.c_int32),
+                ("pan", C.POINTER(C.c_uint64)), ("core", C.POINTER(C.c_uint64)), ("perm", C.POINTER(C.c_uint32)),
+                ("bp_by_groups", C.POINTER(C.c_uint64)), ("growth_us", C.c_uint64), ("kernel_us", C.c_uint64 * 4),
+                ("seed", C.c_uint64)]
 
 
 class AlignmentsC(C.Structure):
@@ -299,6 +315,14 @@ def load():
     L.sr_viz_params_default.argtypes = [PVP]; L.sr_viz_params_default.restype = None
     L.sr_path_bins_rgb.argtypes = [PPB, C.POINTER(C.c_char_p), PVP, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.sr_path_bins_png.argtypes = [PPB, C.POINTER(C.c_char_p), PVP, C.POINTER(vp), C.POINTER(u64)]
+    PG, PU32 = C.POINTER(GrowthC), C.POINTER(C.c_uint32)
+    L.sr_growth_params_default.argtypes = [C.POINTER(GrowthParamsC)]; L.sr_growth_params_default.restype = None
+    L.sr_growth_gfa.argtypes = [C.c_char_p, PU32, C.c_uint32, C.POINTER(GrowthParamsC), i32, C.POINTER(PG)]
+    L.sr_growth_free.argtypes = [PG]; L.sr_growth_free.restype = None
+    L.sr_growth_groups.argtypes = [C.POINTER(C.c_char_p), u64, i32, PU32, PU32, C.POINTER(C.POINTER(C.c_char_p))]
+    L.sr_growth_expected.argtypes = [C.POINTER(u64), C.c_uint32, PD, PD]
+    L.sr_growth_fit.argtypes = [PD, C.c_uint32, PD, PD, PU32]
+    L.sr_growth_report.argtypes = [PG, C.POINTER(vp)]
     PI = C.POINTER(C.c_int)
     L.sr_mirror_map.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                 C.POINTER(C.c_uint32), C.POINTER(u64)]

@@ -82,12 +82,16 @@ static void usage() {
                     "       [--layout graph.lay.tsv] [--layout-svg graph.svg] [--layout-seed N] [--layout-iter-max N]\n"
                     "       [--bin bins.tsv [--bin-width W | --bin-count N]] [--viz graph.png [--viz-width N] [--viz-path-height H]\n"
                     "       [--viz-path-gap G] [--viz-mode path|strand|depth] [--viz-depth-max D]]\n"
+                    "       [--growth growth.tsv [--growth-permutations N] [--growth-seed N] [--growth-group-by path|sample|haplotype]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave", stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt;
+                aligner = "allwave", stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt;
+    sr_growth_params gp;
+    sr_growth_params_default(&gp);
+    int growth_mode = 0;
     unsigned long long bin_width = 0, bin_count = 0, viz_width = 1500;
     sr_viz_params vp;
     sr_viz_params_default(&vp);
@@ -175,6 +179,25 @@ int main(int argc, char **argv) {
             if (m != "path" && m != "strand" && m != "depth") { fprintf(stderr, "Error: --viz-mode takes path, strand or depth\n"); return 1; }
             vp.mode = m == "path" ? SR_VIZ_MODE_PATH : m == "strand" ? SR_VIZ_MODE_STRAND : SR_VIZ_MODE_DEPTH;
         }
+        else if (a == "--growth") growth_out = val("--growth");
+        else if (a == "--growth-permutations" || a == "--growth-seed") {
+            const char *v = val(a.c_str());
+            char *end = nullptr;
+            const unsigned long long n = strtoull(v, &end, 10);
+            growth_opt = a;
+            const bool zero_ok = a == "--growth-seed";
+            if (*v < '0' || *v > '9' || *end != 0 || (n == 0 && !zero_ok)) {
+                fprintf(stderr, "Error: %s needs a %s integer, got '%s'\n", a.c_str(), zero_ok ? "non-negative" : "positive", v);
+                return 1;
+            }
+            (zero_ok ? gp.seed : gp.permutations) = n;
+        }
+        else if (a == "--growth-group-by") {
+            const std::string m = val("--growth-group-by");
+            growth_opt = a;
+            if (m != "path" && m != "sample" && m != "haplotype") { fprintf(stderr, "Error: --growth-group-by takes path, sample or haplotype\n"); return 1; }
+            growth_mode = m == "path" ? 0 : m == "sample" ? 1 : 2;
+        }
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
             const char *v = val("--inversion-min-size");
@@ -228,6 +251,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Error: %s is an option of %s: give both\n", (b ? bin_opt : viz_opt).c_str(), b ? "--bin" : "--viz");
         return 1;
     }
+    if (!growth_opt.empty() && growth_out.empty()) { fprintf(stderr, "Error: %s is an option of --growth: give both\n", growth_opt.c_str()); return 1; }
     if (bin_width && bin_count) { fprintf(stderr, "Error: --bin-width and --bin-count exclude each other\n"); return 1; }
     if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
     if (compact_dev && no_compact) { fprintf(stderr, "Error: --compact-on device and --no-compact exclude each other\n"); return 1; }
@@ -388,7 +412,7 @@ int main(int argc, char **argv) {
     o << gfa;
     std::vector<std::string> pnames;                         // names of the P lines, as the library's parser reads them
     std::vector<const char *> pn;
-    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty()) {
+    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty() || !growth_out.empty()) {
         for (const char *q = gfa; *q;) {
             const char *eol = strchr(q, '\n');
             if (!eol) eol = q + strlen(q);
@@ -464,6 +488,21 @@ int main(int argc, char **argv) {
         printf("%s written to %s\n", pass == 0 ? "Bins" : "Visualization", dst.c_str());
         if (verbose) printf("Bin stage: %llu us on device %d\n", (unsigned long long)pb->bin_us, device);
         sr_path_bins_free(pb);
+    }
+    if (!growth_out.empty()) {                               // the growth curves of the text just written
+        std::vector<uint32_t> group_of(pn.size() ? pn.size() : 1);
+        uint32_t n_groups = 0;
+        sr_growth *gr = nullptr;
+        char *report = nullptr;
+        if (sr_growth_groups(pn.data(), pn.size(), growth_mode, group_of.data(), &n_groups, nullptr) ||
+            sr_growth_gfa(gfa, group_of.data(), n_groups, &gp, device, &gr)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_free(gfa); return 1; }
+        if (sr_growth_report(gr, &report)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_growth_free(gr); sr_free(gfa); return 1; }
+        std::ofstream go(growth_out, std::ios::binary);
+        go << report;
+        sr_free(report);
+        printf("Growth written to %s\n", growth_out.c_str());
+        if (verbose) printf("Growth stage: %llu us on device %d\n", (unsigned long long)gr->growth_us, device);
+        sr_growth_free(gr);
     }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());

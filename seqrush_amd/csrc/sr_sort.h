@@ -46,5 +46,9 @@ int sr_graph_stats_run(const SrGraph &g, int device, void *stream, sr_graph_stat
 // the path-by-bin tables of a parsed graph (sr_bin.hip), with the same meaning of device and stream; *out as
 // sr_path_bins_gfa returns it
 int sr_graph_bins_run(const SrGraph &g, const sr_bin_params &prm, int device, void *stream, sr_path_bins **out);
+// the growth curves of a parsed graph (sr_growth.hip), with the same meaning of device and stream; *out as sr_growth_gfa
+// returns it
+int sr_graph_growth_run(const SrGraph &g, const uint32_t *group_of, uint32_t n_groups, const sr_growth_params &prm, int device, void *stream,
+                        sr_growth **out);
 int sr_fail(int code, const std::string &msg);     // sr_host.cpp: sets sr_last_error()
 void sr_sort_note_write_ms(double ms);              // slot [3] of sr_sort_stats(), also added to the stage's wall time [9]

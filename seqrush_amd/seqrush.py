@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, check, SeqRushError)
+                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, check, SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -66,6 +66,10 @@ class Args:
     viz_path_gap: int = 1
     viz_mode: str = "path"                  # path | strand | depth
     viz_depth_max: int = 4
+    growth: Optional[str] = None            # added: --growth FILE: pangenome growth curves of the final GFA as TSV
+    growth_permutations: int = 1000         # added: --growth-permutations N
+    growth_seed: int = 9399220              # added: --growth-seed N
+    growth_group_by: str = "path"           # added: --growth-group-by path | sample | haplotype
 
 
 @dataclasses.dataclass
@@ -812,7 +816,130 @@ def write_bins(text: str, args: "Args"):
             print(f"Bin stage: {us} us on device {args.device}")
 
 
-LAYOUT_STATS = ("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
+SR_GROWTH_DEVICE_HOST = -1
+GROWTH_KERNELS = ("presence", "histogram", "ranks", "growth")
+GROWTH_GROUP_BY = ("path", "sample", "haplotype")
+
+
+def growth_groups(names, mode="path"):
+    """groups of paths from their names -> (group_of: uint32 [paths], group names).  mode "path": every path its own
+    group; "sample" / "haplotype": the PanSN prefix before the first / second '#' (a name without that many is its own
+    key); groups are numbered by first appearance"""
+    if mode not in GROWTH_GROUP_BY:
+        raise SeqRushError(-1, f"group_by must be one of {', '.join(GROWTH_GROUP_BY)}, not {mode!r}")
+    L = _lib.load()
+    names = list(names)
+    arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+    group_of = np.zeros(max(1, len(names)), dtype=np.uint32)
+    n = C.c_uint32()
+    out = C.POINTER(C.c_char_p)()
+    check(L.sr_growth_groups(C.cast(arr, C.POINTER(C.c_char_p)), len(names), GROWTH_GROUP_BY.index(mode),
+                             group_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n), C.byref(out)))
+    group_names = [out[i].decode() for i in range(n.value)]
+    L.sr_free(C.cast(out, C.c_void_p))
+    return group_of[:len(names)].copy(), group_names
+
+
+def growth_expected(bp_by_groups):
+    """closed-form E pan(k), E core(k), k = 1..G, over all orders of the groups -> two float64 arrays [G]"""
+    bp = np.ascontiguousarray(bp_by_groups, dtype=np.uint64)
+    G = len(bp) - 1
+    pan, core = np.zeros(max(G, 1)), np.zeros(max(G, 1))
+    check(_lib.load().sr_growth_expected(bp.ctypes.data_as(C.POINTER(C.c_uint64)), G, _pd(pan), _pd(core)))
+    return pan[:G], core[:G]
+
+
+def growth_fit(pan_exp):
+    """Heaps' law fit of new(k) = pan_exp(k) - pan_exp(k - 1) ~ kappa k^-alpha -> (alpha, kappa, points); points < 2: no fit"""
+    pe = np.ascontiguousarray(pan_exp, dtype=np.float64)
+    a, k, n = C.c_double(), C.c_double(), C.c_uint32()
+    check(_lib.load().sr_growth_fit(_pd(pe), len(pe), C.byref(a), C.byref(k), C.byref(n)))
+    return a.value, k.value, n.value
+
+
+class Growth:
+    """an owned sr_growth: the growth curves of a GFA text.  group_by names the grouping of the
+    text's P lines; group_of / n_groups give one directly instead"""
+
+    def __init__(self, text: str, device: int = 0, group_by: str = "path", permutations: int = 1000, seed: int = 9399220,
+                 group_of=None, n_groups: Optional[int] = None):
+        for k, v in (("permutations", permutations), ("seed", seed)):
+            if not 0 <= int(v) < 2 ** 64:
+                raise SeqRushError(-1, f"{k} must be in 0 .. 2^64 - 1")
+        self.L = _lib.load()
+        self.p = C.POINTER(GrowthC)()
+        self.group_names = None
+        if group_of is None and group_by != "path":
+            group_of, self.group_names = growth_groups(_path_names(text), group_by)
+        elif group_by not in GROWTH_GROUP_BY:
+            raise SeqRushError(-1, f"group_by must be one of {', '.join(GROWTH_GROUP_BY)}, not {group_by!r}")
+        ptr, G = None, 0
+        if group_of is not None:
+            group_of = np.ascontiguousarray(group_of, dtype=np.uint32)
+            G = int(n_groups) if n_groups is not None else (int(group_of.max()) + 1 if len(group_of) else 0)
+            keep = group_of if len(group_of) else np.zeros(1, dtype=np.uint32)
+            ptr = keep.ctypes.data_as(C.POINTER(C.c_uint32))
+        prm = GrowthParamsC(int(seed), int(permutations))
+        check(self.L.sr_growth_gfa(text.encode(), ptr, G, C.byref(prm), int(device), C.byref(self.p)))
+
+    def close(self):
+        if self.p:
+            self.L.sr_growth_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def as_dict(self) -> dict:
+        s = self.p.contents
+        R, G = int(s.permutations), int(s.groups)
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].astype(dt, copy=True)
+        d = {k: int(getattr(s, k)) for k in ("length", "paths", "groups", "permutations", "exhaustive", "variant", "seed", "growth_us")}
+        d["pan"], d["core"] = arr(s.pan, R * G, np.uint64).reshape(R, G), arr(s.core, R * G, np.uint64).reshape(R, G)
+        d["perm"] = arr(s.perm, R * G, np.uint32).reshape(R, G)
+        d["bp_by_groups"] = arr(s.bp_by_groups, G + 1, np.uint64)
+        d["kernel_us"] = dict(zip(GROWTH_KERNELS, (int(v) for v in s.kernel_us)))
+        return d
+
+    def report(self) -> str:
+        out = C.c_void_p()
+        check(self.L.sr_growth_report(self.p, C.byref(out)))
+        return _take_text(out)
+
+
+def growth(text: str, device: int = 0, group_by: str = "path", permutations: int = 1000, seed: int = 9399220, **groups) -> dict:
+    """growth curves of any GFA with S / L / P lines and numeric node ids.  device >= 0: HIP kernels
+    on that device, -1: the host twin (the same integers).  -> dict: length, paths, groups, permutations (run), exhaustive,
+    variant, seed; pan / core (uint64 [permutations, groups]: base pairs on at least one / on all of the first k groups of
+    each permutation), perm (uint32, the group at each rank), bp_by_groups (uint64 [groups + 1]); growth_us, kernel_us"""
+    with Growth(text, device, group_by, permutations, seed, **groups) as g:
+        return g.as_dict()
+
+
+def growth_report(text: str, device: int = 0, group_by: str = "path", permutations: int = 1000, seed: int = 9399220, **groups) -> str:
+    """the TSV report of growth(): expectations, the Heaps' law fit and mean / sd / min / max over the permutations per k,
+    formatted by the library (the only place where a float is formed)"""
+    with Growth(text, device, group_by, permutations, seed, **groups) as g:
+        return g.report()
+
+
+def write_growth(text: str, args: "Args"):
+    """the --growth stage of both Python front ends on the final GFA text"""
+    with Growth(text, args.device, args.growth_group_by, args.growth_permutations, args.growth_seed) as g:
+        with open(args.growth, "w") as fh:
+            fh.write(g.report())
+        us = int(g.p.contents.growth_us)
+    print(f"Growth written to {args.growth}")
+    if args.verbose:
+        print(f"Growth stage: {us} us on device {args.device}")
+
+
+LAYOUT_STATS =("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
 
 
 def _layout_params(params) -> LayoutParamsC:
@@ -1157,6 +1284,8 @@ class SeqRush:
             write_layout(text, args)
         if args.bin or args.viz:
             write_bins(text, args)
+        if args.growth:
+            write_growth(text, args)
 
 
 def run_seqrush(args: Args):
