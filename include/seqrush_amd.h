@@ -307,8 +307,13 @@ int sr_base_cone_reach(int e1, int e2, int two, int levels_left);
  * primaries (the workspace report's "mirror_partners"). */
 int sr_mirror_map(const uint32_t *query_idx, const uint32_t *target_idx, uint64_t count, const uint32_t *batch_first,
                   uint32_t nbatch, uint32_t workgroups, uint32_t *mirror_out, uint64_t *partners_out);
-/* per pair of the loaded list: the orientation scores of the last alignment stage (forward; reverse complement, INT32_MAX
- * where it was not searched to the end); either pointer may be NULL */
+/* per pair of the loaded list: what the orientation search of the last alignment stage found (orientation penalties; F, R =
+ * the forward and the reverse-complement score).  Only the winner's score is exact:
+ *   reverse strand chosen (R < F): rev = R, fwd = -1 (the forward orientation was not searched to the end)
+ *   forward strand chosen:         fwd = F, rev = INT32_MAX (the reverse orientation was not searched to the end)
+ * except that a pair the orientation kernel decides by its bounds alone (2-bit symbols, penalties 0,1,1,1: the alignment
+ * along diagonal 0 closed by one end gap costs less than the 8-mer lower bound of R) reports that diagonal-0 upper bound
+ * of F in fwd, not F itself; the values order the alignment queue.  Either pointer may be NULL */
 int sr_ctx_orientation_scores(sr_ctx *c, int32_t *fwd, int32_t *rev);
 /* host twins of the kernel's tie rules (csrc/sr_mirror_rule.h).  Backtrace, M step: off[1..9] = candidate offsets of the tags
  * I1o I1e I2o I2e D1o D1e D2o D2e MISMS (< 0: none; off[0] unused) -> the tag picked by this pair's order (transposed = 0)
