@@ -256,6 +256,20 @@ int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap);
 /* "NAME<TAB>meaning when unset<TAB>what it does" lines of every environment variable the load path reads; the ones that
  * are set are listed under "knobs" in sr_ctx_workspace_report() */
 const char *sr_knobs_doc(void);
+/* Tail launch of the blocked alignment kernel.  sr_ctx_tail_deferred: secondaries the main launches handed
+ * to their wide tail launch since the counters were last reset (summed over the batches of the pass; <= counter mirror_ties).
+ * The workspace report's "tail_threads" is the tail launch's shape, 0 = the load has none. */
+int sr_ctx_tail_deferred(sr_ctx *c, uint64_t *out);
+/* Per-workgroup timeline of the last main launch of the instrumented instance (SR_PROFILE_TICKS=1), 4 words per workgroup:
+ * 100 MHz ticks of its first dequeue, of the start of its last alignment and of its exit, and alignments run | (1 << 32 when
+ * the last one was a secondary taken over from its own primary).  Returns the workgroups written (<= cap_wg), 0 when the load
+ * does not run the instrumented instance, or a negative sr_status. */
+int sr_ctx_tail_timeline(sr_ctx *c, uint64_t *out, uint32_t cap_wg);
+/* The tail launch's threads per workgroup for a plan: the widest instance of the blocked kernel wider than main_threads whose
+ * LDS (static tables + four copies of max_words words) fits the 128 KB window, 0 = none.  forced > 0 (SR_TAIL_THREADS): the
+ * widest instance <= forced instead.  Pure (host only). */
+int sr_tail_shape(int impl, int block_levels, int wave_build, int off16, int ring_u16, int symbol_bits, int two_piece,
+                  int main_threads, uint32_t max_words, int forced);
 
 /* -------- iterative mode (`seqrush --iterative`, align_and_unite_iterative src/seqrush.rs:867-1132) ---------------
  * Tree entries ({i<j} picked by the k-NN selection of -x tree:, row-major) are aligned and united first; then the random

@@ -44,6 +44,7 @@ EXPORTS = [
     "sr_path_bins_gfa", "sr_path_bins_free", "sr_path_bins_tsv", "sr_viz_params_default", "sr_path_bins_rgb", "sr_path_bins_png",
     "sr_growth_params_default", "sr_growth_gfa", "sr_growth_free", "sr_growth_groups", "sr_growth_expected", "sr_growth_fit",
     "sr_growth_report",
+    "sr_ctx_tail_deferred", "sr_ctx_tail_timeline", "sr_tail_shape",
 ]
 
 
@@ -234,6 +235,9 @@ def load():
     L.sr_ctx_counters_ext.argtypes = [vp, C.POINTER(u64)]
     L.sr_ctx_counters_all.argtypes = [vp, C.POINTER(u64), C.c_uint32]
     L.sr_knobs_doc.restype = C.c_char_p
+    L.sr_ctx_tail_deferred.argtypes = [vp, C.POINTER(u64)]
+    L.sr_ctx_tail_timeline.argtypes = [vp, C.POINTER(u64), C.c_uint32]
+    L.sr_tail_shape.argtypes = [i32] * 8 + [C.c_uint32, i32]
     L.sr_ctx_load_pairs.argtypes = [vp, PS, PP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64]
     L.sr_ctx_pairs.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]
     L.sr_ctx_num_batches.argtypes = [vp]; L.sr_ctx_num_batches.restype = C.c_uint32

@@ -53,6 +53,9 @@ __device__ __forceinline__ int kjob_width(int plen, int tlen) { return (plen + t
 template <typename OT, int NT, bool TWO, int B, int E1, int E2, bool PROF = false, int X = 0, int OE1 = 0, typename RT = OT>
 __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAlignArgs a) {
     const int tid = threadIdx.x;
+    // tail launch (DESIGN.md 4.3): nothing was deferred -> the workgroup leaves before it touches a row or a barrier.  (Uniform:
+    // nothing in a tail launch writes tail_count; the main launch that did ended before this one began.)
+    if (a.tail_mode == SR_TAIL_RUN && *a.tail_count == 0u) return;
     GP<RT> bring = (GP<RT>)(RT *)a.bring + (size_t)blockIdx.x * a.bring_wg_stride;
     GP<OT> bhist = (GP<OT>)(OT *)a.bhist + (size_t)blockIdx.x * a.bhist_wg_stride;
     GP<int> lists = (GP<int>)a.bseg + (size_t)blockIdx.x * 2 * SR_BFS_MAXSEG * SR_BFS_SEGREC;
@@ -62,6 +65,9 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
     unsigned long long t_ori = 0, t_bp = 0, t_base = 0, t_all = 0, tb_bt = 0, tb_emit = 0;
     unsigned long long tq_pass = 0, tq_bar = 0, tq_ctl = 0, tq_ph2 = 0, tq_tail = 0, tq_rec = 0;
     unsigned row_ld = 0, row_st = 0;                     // per pair, in lane accesses (flushed to the wave's sums in LDS per pair)
+    // PROF, thread 0: the workgroup's timeline (a.timeline, 4 words per workgroup): first dequeue, start of the last alignment,
+    // alignments run, whether the last one came from mir_next
+    unsigned long long tl_first = 0, tl_last = 0, tl_n = 0, tl_mir = 0;
     const int depth = a.kdepth;
     // ring: chunk-major rows (see KRows); rows = 5 components x depth levels + NULL row + U row
     const int depth2 = a.kdepth2;
@@ -118,11 +124,21 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         if (tid == 0) {
             int pr = k_sh.mir_next;
             k_sh.mir_next = -1;
-            while (pr < 0) {
+            const bool from_mir = pr >= 0;
+            if (a.tail_mode == SR_TAIL_RUN) {
+                // tail launch: the deferred secondaries, by batch-relative index, each an ordinary pair (no order[], no skip)
+                const uint32_t i = atomicAdd(a.tail_head, 1u);
+                pr = i < *a.tail_count ? (int)a.tail_list[i] : (int)a.npairs;
+            } else while (pr < 0) {
                 pr = (int)atomicAdd(a.queue_head, 1u);
                 if (pr >= (int)a.npairs) { pr = (int)a.npairs; break; }
                 if (a.order) pr = (int)a.order[pr];          // cost-sorted dequeue order (longest pairs first)
                 if (a.mirror && a.mirror[pr] != SR_MIRROR_NONE && (a.mirror[pr] & SR_MIRROR_SECONDARY)) pr = -1;   // its primary's business
+            }
+            if (PROF) {
+                const unsigned long long now = KTICK();
+                if (tl_n == 0) tl_first = now;
+                if (pr < (int)a.npairs) { tl_last = now; tl_n++; tl_mir = from_mir ? 1ull : 0ull; }
             }
             b_sh.pair = pr;
             b_sh.err = 0; b_sh.cig_cnt = 0; b_sh.score_acc = 0; k_sh.pend_op = -1; k_sh.pend_len = 0;
@@ -626,7 +642,17 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                         if (!a.pre_oriented) { a.is_reverse[mir] = 0; a.ori_fwd[mir] = fwd; a.ori_rev[mir] = rev; }
                     }
                 }
-            } else if (tid == 0) { k_sh.mir_next = (int)mir; k_sh.mir_ties += 1ull; }
+            } else if (tid == 0) {
+                // aligned after all.  By this workgroup, next -- unless the queue is dry (or SR_TAIL=all): then nothing else would
+                // start on this CU any more, and the secondary goes on the list of the wide tail launch that follows
+                k_sh.mir_ties += 1ull;
+                bool defer = false;
+                if (a.tail_list && a.tail_mode != SR_TAIL_RUN)
+                    defer = a.tail_mode == SR_TAIL_DEFER_ALL ||
+                            __hip_atomic_load(a.queue_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= a.npairs;
+                if (defer) { a.tail_list[atomicAdd(a.tail_count, 1u)] = mir; atomicAdd(a.tail_deferred, 1u); }
+                else k_sh.mir_next = (int)mir;
+            }
         }
         if (a.fuse_unite) {
             // unite the bases of the match runs (what sr_unite_kernel does for a pair, sr_uf.hip); same filter: aligned, and
@@ -678,6 +704,10 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         if (k_sh.mir_pairs) atomicAdd(&a.counters[38], k_sh.mir_pairs);
         if (k_sh.mir_ties) atomicAdd(&a.counters[39], k_sh.mir_ties);
         atomicAdd(&a.counters[46], k_sh.base_tiles); atomicAdd(&a.counters[47], k_sh.base_cells);
+        if (PROF && a.timeline) {
+            unsigned long long *tl = a.timeline + 4ull * blockIdx.x;
+            tl[0] = tl_first; tl[1] = tl_last; tl[2] = KTICK(); tl[3] = tl_n | (tl_mir << 32);
+        }
         if (PROF) {
             if (!a.pre_oriented) atomicAdd(&a.counters[6], t_ori);    // ([6] holds sr_orient_kernel's cells otherwise)
             atomicAdd(&a.counters[7], t_bp);

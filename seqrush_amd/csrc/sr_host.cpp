@@ -55,7 +55,10 @@ static const SrKnob SR_KNOBS[] = {
     {"SR_NO_KBITS", "off", "no q-gram bound in the orientation kernel"},
     {"SR_NO_MIRROR", "off", "1 = no pair has a mirror partner: (q, t) and (t, q) are both aligned (A/B runs, tests)"},
     {"SR_NO_FUSED_UNITE", "off", "sr_ctx_run launches sr_unite_kernel per batch instead of uniting inside the blocked alignment kernel"},
-    {"SR_PROFILE_TICKS", "0", "1 = launch the instrumented instance (100 MHz tick counters)"},
+    {"SR_PROFILE_TICKS", "0", "1 = launch the instrumented instance (100 MHz tick counters, per-workgroup timeline)"},
+    {"SR_TAIL", "on", "0 = no tail launch: a tied secondary is always aligned by its primary's workgroup (A/B runs); all = every such secondary is deferred to the tail launch (tests)"},
+    {"SR_TAIL_THREADS", "widest instance wider than the main launch", "threads per workgroup of the tail launch among the existing instances: 256 | 512 | 1024 (tests)"},
+    {"SR_TAIL_ROUNDS", "8", "a batch defers only when its alignments are at most this many times the launch's workgroups"},
     {"SR_FORCE_INT32", "off", "tests: 32-bit offsets (and the 16-bit ring of 32-bit searches) whatever the sequence length"},
     {"SR_TEST_BASE_LEVELS", "off", "tests: cap on the levels a base case is given at first (forces the re-queue path)"},
     {"SR_BOUNDS_DETAIL", "off", "1 = (bounds-checked build) keep the first offending access in counters[40..43]"},
@@ -235,6 +238,10 @@ static int32_t max_score_for_divergence(const sr_params &p, uint64_t seq_len, do
     return std::max(mismatch_score + gap_score, p.mismatch_penalty * 2);
 }
 
+// A tied secondary is deferred to the tail launch only in batches of at most this many rounds of alignments per workgroup:
+// beyond, the solo alignment at the end is a few per cent of the launch at most (SR_TAIL_ROUNDS)
+#define SR_TAIL_ROUNDS_DEFAULT 8
+
 // ------------------------------------------------------------------ context
 struct sr_ctx {
     int device = 0;
@@ -268,6 +275,12 @@ struct sr_ctx {
     int32_t *d_max_score = nullptr;
     uint32_t *d_mirror = nullptr;                  // [np] SrAlignArgs::mirror (blocked kernel, 2-bit symbols), nullptr = none
     uint64_t mirror_partners = 0;                  // primaries of the rank's list
+    // tail launch of the blocked kernel: shape (0 = none), its workgroups per CU, SR_TAIL=all, the rounds rule
+    int tail_threads = 0, tail_wg_per_cu = 1, tail_rounds = SR_TAIL_ROUNDS_DEFAULT, tail_cus = 0;
+    bool tail_all = false;
+    std::vector<uint32_t> batch_partners;          // [nbatch] primaries per batch
+    uint32_t *d_tail_list = nullptr, *d_tail_deferred = nullptr;
+    unsigned long long *d_timeline = nullptr;      // instrumented instance: [nwg][4] (sr_ctx_tail_timeline)
     // kernel timing: [kind] -> one event pair per batch (kinds: 0 align, 1 unite, 4 orientation) or a single pair (2, 3)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
     int ev_used[5] = {0, 0, 0, 0, 0};
@@ -324,6 +337,7 @@ static void free_dev(sr_ctx *c) {
     c->d_nodes = c->d_minarr = c->d_labels = c->d_counters = nullptr;
     c->d_error = nullptr; c->d_queue = nullptr; c->d_oqueue = nullptr; c->d_order = nullptr; c->d_cbase = nullptr;
     c->d_bases = nullptr; c->d_max_score = nullptr; c->d_mirror = nullptr; c->mirror_partners = 0; c->onwg = 0;
+    c->tail_threads = 0; c->tail_all = false; c->batch_partners.clear(); c->d_tail_list = c->d_tail_deferred = nullptr; c->d_timeline = nullptr;
     c->d_okeys = c->d_okeys2 = nullptr; c->d_ovals = nullptr; c->d_otemp = nullptr; c->otemp_bytes = 0;
     c->loaded = false; c->from_paf = false; c->aligned_batch_valid = false;
     for (int k = 0; k < 5; k++) c->ev_used[k] = 0;
@@ -591,6 +605,7 @@ struct SeqDev { uint32_t *words = nullptr; uint64_t *woff[4] = {nullptr, nullptr
 struct Plan {
     // kernel + launch shape
     int impl = 1, kblock = 0, wg_per_cu = 4, cus = 256, lazy_id = 0, ring_u16 = 0, bbase_jobs = 16;
+    int tail_threads = 0;                 // shape of the tail launch, 0 = none
     bool wave_wg = false;
     uint32_t max_words = 0;
     size_t osz = 2, rsz = 2;
@@ -884,6 +899,36 @@ extern "C" int sr_mirror_bp_pick_host(const int *val, const int *dist, const int
     return n > 0 && sr_mirror_bp_tie(best, best_t) ? 1 : 0;
 }
 
+// static tables of the alignment kernels (upper estimates; the blocked kernel's scan arrays of the fused unite grow with the
+// workgroup: 25 024 / 28 144 / 34 384 bytes at 256 / 512 / 1024 threads with the second key table of breakpoint detection)
+static size_t align_static_lds(bool wave_wg, int impl, int nthreads) {
+    return (size_t)(wave_wg ? 6 : impl != 2 ? 28 : nthreads >= 1024 ? 34 : nthreads >= 512 ? 28 : 25) * 1024;
+}
+// Shape of the tail launch: threads per workgroup of the widest blocked instance srk_align dispatches for the plan that is
+// wider than the main launch and whose LDS fits by plan_kernel's tests (static tables + four sequence copies inside the
+// 128 KB window); 0 = no tail launch.  Instances (sr_align_blk.hip): 10-level blocks on int16 rows -- 1 024 threads for the
+// two-piece 2-bit build, 512 for all; 32-bit searches on the uint16 ring -- 512; everything has 256.  The one-wave builds,
+// the 5-level instances and 32-bit rows have nothing wider.  forced (SR_TAIL_THREADS) > 0: the widest instance <= forced,
+// whatever the main launch has.  Pure: exported as sr_tail_shape for the tests.
+static int tail_shape(int impl, int kblock, int wave_wg, int off16, int ring_u16, int symbits, int two, int main_threads,
+                      uint32_t max_words, int forced) {
+    if (impl != 2 || kblock != 10 || wave_wg) return 0;
+    if (!off16 && !ring_u16 && forced < 256) return 0;                     // 32-bit rows: the 256-thread build only
+    static const int shapes[3] = {1024, 512, 256};
+    for (int nt : shapes) {
+        if (forced > 0 ? nt > forced : nt <= main_threads) continue;
+        if (nt == 1024 && !(off16 && symbits == 2 && two)) continue;
+        if (nt == 512 && !(off16 || ring_u16)) continue;
+        if ((size_t)max_words * 16 + 16 + align_static_lds(false, 2, nt) > 128 * 1024) continue;
+        return nt;
+    }
+    return 0;
+}
+extern "C" int sr_tail_shape(int impl, int kblock, int wave_wg, int off16, int ring_u16, int symbits, int two, int main_threads,
+                             uint32_t max_words, int forced) {
+    return tail_shape(impl, kblock, wave_wg, off16, ring_u16, symbits, two, main_threads, max_words, forced);
+}
+
 // kernel choice and workgroup shape.  impl 2 = score-blocked wave-tiled kernel (when this build has an instance for the
 // penalties), impl 1 = level-synchronous kernel (any penalties; rings deeper than 32 levels take its wide instance)
 static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const SrPen &ori, uint64_t maxlen, uint32_t np, Plan &pl) {
@@ -924,11 +969,7 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     if (impl == 2 && c->nthreads == 128 && kblock == 10 && !(bits == 2 && c->off16)) kblock = 5;   // (no 128-thread 10-level instance there)
     pl.wave_wg = impl == 2 && (c->nthreads == 64 || (c->nthreads == 128 && kblock == 10));   // lean builds: 16 / 8 pairs per CU
     if (pl.wave_wg) pl.wg_per_cu = c->nthreads == 64 ? 16 : 8;
-    // static tables of the kernel (upper estimates; the blocked kernel's scan arrays of the fused unite grow with the
-    // workgroup: 25 024 / 28 144 / 34 384 bytes at 256 / 512 / 1024 threads with the second key table of breakpoint detection)
-    auto static_lds = [&](int nthreads) -> size_t {
-        return (size_t)(pl.wave_wg ? 6 : impl != 2 ? 28 : nthreads >= 1024 ? 34 : nthreads >= 512 ? 28 : 25) * 1024;
-    };
+    auto static_lds = [&](int nthreads) -> size_t { return align_static_lds(pl.wave_wg, impl, nthreads); };
     const size_t lds_per_wg = c->lds_bytes + static_lds(c->nthreads);
     pl.wg_per_cu = (int)std::min<size_t>((size_t)pl.wg_per_cu, std::max<size_t>(1, (160 * 1024) / lds_per_wg));
     // long sequences: the four LDS copies leave room for two workgroups per CU (C5: 50 KB each) -- give each 8 waves, or
@@ -947,6 +988,10 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     pl.rsz = pl.ring_u16 ? 2 : pl.osz;                 // bytes per ring cell (the base-case history keeps osz)
     pl.bbase_jobs = pl.wave_wg ? (c->nthreads == 64 ? 4 : 8) : 16;
     if (const char *e = knob("SR_BFS_BASE_JOBS")) pl.bbase_jobs = std::max(1, std::min(16, atoi(e)));
+    // the tail launch; whether a load has partners at all is alloc_workspace's business
+    const char *tl = knob("SR_TAIL"), *tt = knob("SR_TAIL_THREADS");
+    pl.tail_threads = (tl && !strcmp(tl, "0")) ? 0
+                      : tail_shape(impl, kblock, pl.wave_wg, c->off16, pl.ring_u16, bits, pen.two, c->nthreads, pl.max_words, tt ? std::max(1, atoi(tt)) : 0);
     return SR_OK;
 }
 
@@ -1000,6 +1045,8 @@ static int plan_workspace(const sr_ctx *c, const SrPen &pen, const SrPen &ori, u
     pl.hist_nul_w = impl == 2 ? (uint64_t)pl.hist_w + 256 : (uint64_t)pl.bbase_jobs * (uint64_t)pl.hist_w;
     pl.bhist_wg = impl == 2 ? ((pl.hist_cap + pl.hist_nul_w + 256 + 1024 + 7) & ~7ULL)      // data, NULL row, trash cells, slack
                             : ((uint64_t)pl.hist_levels * 5 + 1) * pl.hist_nul_w + 1024;
+    // (The tail launch of the blocked kernel reuses slots 0 .. grid - 1 at another thread count: nothing above or below
+    // depends on the threads of a workgroup -- bbase_jobs does only for the one-wave builds, which have no tail launch.)
     pl.bseg_wg = 2ULL * SR_BFS_MAXSEG * SR_BFS_SEGREC * 4;          // bytes
     pl.bbt_wg = (uint64_t)pl.bbase_jobs * SR_BFS_BTCAP * 4;        // bytes
     pl.bcl_wg = 0;                 // (round 3: breakpoint detection keeps a band per unit in LDS instead of a candidate list in global memory)
@@ -1118,8 +1165,35 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
         if (!knob("SR_NO_MIRROR")) c->mirror_partners = mirror_map(c->pair_q.data(), c->pair_t.data(), c->batch_first.data(), nbatch, (uint32_t)nwg, mirror.data());
         DEV_UPLOAD(c->d_mirror, uint32_t, mirror);
     }
+    // primaries per batch: the tail launch's grid and the capacity of its list
+    c->batch_partners.assign(nbatch, 0);
+    uint32_t max_partners = 0;
+    for (uint32_t b = 0; b < nbatch && !mirror.empty(); b++) {
+        for (uint32_t i = c->batch_first[b]; i < c->batch_first[b + 1]; i++)
+            if (mirror[i] != SR_MIRROR_NONE && !(mirror[i] & SR_MIRROR_SECONDARY)) c->batch_partners[b]++;
+        max_partners = std::max(max_partners, c->batch_partners[b]);
+    }
     HIPCHK(hipStreamSynchronize(c->stream));   // the uploads above have read their host vectors (pq, pt, cb, order, mirror)
-    if ((r = dev_alloc(c, &d, sizeof(uint32_t)))) return r; c->d_queue = (uint32_t *)d;
+    // queue_head, and behind it the tail launch's tail_count and tail_head: one memset per batch resets the three
+    if ((r = dev_alloc(c, &d, 4 * sizeof(uint32_t)))) return r; c->d_queue = (uint32_t *)d;
+    c->tail_threads = c->mirror_partners > 0 ? pl.tail_threads : 0;
+    pl.tail_threads = c->tail_threads;
+    if (c->tail_threads) {
+        // workgroups per CU of the tail shape: 16 waves per CU (the kernel's register budget: 4 per SIMD), and its LDS
+        c->tail_wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)1024 / c->tail_threads,
+                                                                      (160 * 1024) / (c->lds_bytes + align_static_lds(false, 2, c->tail_threads))));
+        const char *tl = knob("SR_TAIL"), *tr = knob("SR_TAIL_ROUNDS");
+        c->tail_all = tl && !strcmp(tl, "all");
+        c->tail_rounds = tr ? std::max(0, atoi(tr)) : SR_TAIL_ROUNDS_DEFAULT;
+        c->tail_cus = pl.cus;
+        if ((r = dev_alloc(c, &d, (size_t)max_partners * 4))) return r; c->d_tail_list = (uint32_t *)d;
+        if ((r = dev_alloc(c, &d, sizeof(uint32_t)))) return r; c->d_tail_deferred = (uint32_t *)d;
+        HIPCHK(hipMemsetAsync(c->d_tail_deferred, 0, sizeof(uint32_t), c->stream));
+    }
+    if (impl == 2 && knob("SR_PROFILE_TICKS") && atoi(knob("SR_PROFILE_TICKS")) != 0) {
+        if ((r = dev_alloc(c, &d, (size_t)nwg * 4 * 8))) return r; c->d_timeline = (unsigned long long *)d;
+        HIPCHK(hipMemsetAsync(c->d_timeline, 0, (size_t)nwg * 4 * 8, c->stream));
+    }
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bring_wg * rsz))) return r; a.bring = d;
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bhist_wg * osz))) return r; a.bhist = d;
     // (tests: the kernels must not depend on what the row workspaces held before -- poison them with plausible offsets)
@@ -1210,6 +1284,8 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     u.pair_q = d_pq; u.pair_t = d_pt; u.npairs = np; u.seqlen = sd.len; u.seq_goff = sd.goff;
     a.fuse_unite = 0; a.uf_nodes = c->d_nodes; a.seq_goff = sd.goff; a.max_score = c->d_max_score; a.min_match_len = p->min_match_len;
     a.mirror = c->d_mirror;
+    // (tail_list is set per batch, enqueue_align_batch: NULL unless the batch defers)
+    a.tail_count = c->d_queue + 1; a.tail_head = c->d_queue + 2; a.tail_deferred = c->d_tail_deferred; a.timeline = c->d_timeline;
     c->fuse_unite = impl == 2 && !knob("SR_NO_FUSED_UNITE");
     u.is_reverse = a.is_reverse; u.score = a.score; u.max_score = c->d_max_score;
     u.cigar_ops = a.cigar_ops; u.cigar_base = c->d_cbase; u.cigar_cnt = a.cigar_cnt;
@@ -1232,14 +1308,14 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
              "\"base_history_bytes_per_workgroup\": %llu, \"workspace_bytes\": %llu, \"cigar_arena_bytes\": %llu, "
              "\"orientation_ring_bytes\": %llu, \"union_find_bytes\": %llu, \"device_free_bytes_at_load\": %zu, \"kernel_build\": \"%s\", "
              "\"ring_depth_m\": %d, \"ring_depth_id\": %d, \"fused_unite\": %d, \"wave_build\": %d, \"level_kernel_wide\": %d, "
-             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"knobs\": ",
+             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"tail_threads\": %d, \"knobs\": ",
              np, pl.nbatch, pk.sm.bits, pl.osz, pl.impl == 2 ? pl.rsz : pl.osz, pl.impl, pl.impl == 2 ? pl.kblock : 1, pen.two ? 1 : 0, pl.lazy_id,
              pl.nwg, c->nthreads, pl.wg_per_cu, c->lds_bytes,
              (unsigned long long)(pl.bring_wg * pl.rsz), (unsigned long long)(pl.bhist_wg * pl.osz),
              (unsigned long long)((uint64_t)pl.nwg * pl.per_wg_bytes), (unsigned long long)(pl.arena_ops * 4), (unsigned long long)pl.oring_bytes,
              (unsigned long long)(3ULL * c->uf_size * 8), pl.free_b, srk_align_blk_build_tag(), pl.kdepth, pl.kdepth2, c->fuse_unite ? 1 : 0,
              pl.wave_wg ? 1 : 0, (pl.impl == 1 && pl.ring_scope + 1 > 32) ? 1 : 0, c->aa.profile_ticks, oroute, srk_source_digest(),
-             (unsigned long long)c->mirror_partners);
+             (unsigned long long)c->mirror_partners, c->tail_threads);
     c->workspace_report = std::string(buf) + knobs_json() + "}";
 }
 
@@ -1338,7 +1414,14 @@ static int enqueue_align_batch(sr_ctx *c, uint32_t b, bool fuse_unite = false) {
     SrAlignArgs a;
     batch_args(c, b, &a, nullptr);
     a.fuse_unite = fuse_unite ? 1 : 0;
-    HIPCHK(hipMemsetAsync(c->d_queue, 0, sizeof(uint32_t), c->stream));
+    // Tail launch: the batch defers when it has partners and its alignments (pairs minus secondaries) are at most
+    // tail_rounds x the launch's workgroups -- beyond, one solo alignment at the end is noise (SR_TAIL=all: always)
+    const int main_wg = std::min<int>(c->nwg, (int)a.npairs);
+    const uint32_t partners = c->tail_threads && b < c->batch_partners.size() ? c->batch_partners[b] : 0;
+    const bool defer = partners > 0 && (c->tail_all || (uint64_t)(a.npairs - partners) <= (uint64_t)c->tail_rounds * (uint64_t)main_wg);
+    a.tail_list = defer ? c->d_tail_list : nullptr;
+    a.tail_mode = defer && c->tail_all ? SR_TAIL_DEFER_ALL : SR_TAIL_MAIN;
+    HIPCHK(hipMemsetAsync(c->d_queue, 0, (c->tail_threads ? 3 : 1) * sizeof(uint32_t), c->stream));
     hipEvent_t *e0, *e1;
     int r;
     if (c->onwg > 0 && a.npairs > 0) {           // which = 4: the orientation kernel
@@ -1357,8 +1440,16 @@ static int enqueue_align_batch(sr_ctx *c, uint32_t b, bool fuse_unite = false) {
     if ((r = ev_get(c, 0, c->ev_used[0], &e0, &e1))) return r;
     HIPCHK(hipEventRecord(*e0, c->stream));
     if (a.npairs > 0) {
-        r = srk_align(&a, std::min<int>(c->nwg, (int)a.npairs), c->lds_bytes, c->off16, c->nthreads, c->stream);
+        r = srk_align(&a, main_wg, c->lds_bytes, c->off16, c->nthreads, c->stream);
         if (r) return fail(SR_ERR_HIP, std::string("align kernel launch failed: ") + hipGetErrorString((hipError_t)r));
+        if (defer) {
+            // the same kernel at the tail shape, one workgroup per CU slot, on workspace slots 0 .. grid - 1 of the main launch
+            // (the kernel boundary orders the list); an empty list makes every workgroup return at once
+            const int grid = (int)std::min<uint64_t>({(uint64_t)c->tail_cus * (uint64_t)c->tail_wg_per_cu, (uint64_t)c->nwg, (uint64_t)partners});
+            a.tail_mode = SR_TAIL_RUN; a.timeline = nullptr;
+            r = srk_align(&a, grid, c->lds_bytes, c->off16, c->tail_threads, c->stream);
+            if (r) return fail(SR_ERR_HIP, std::string("align kernel tail launch failed: ") + hipGetErrorString((hipError_t)r));
+        }
     }
     HIPCHK(hipEventRecord(*e1, c->stream));
     c->ev_used[0]++;
@@ -1386,6 +1477,7 @@ static int begin_pass(sr_ctx *c, bool reset_counters) {
     HIPCHK(hipSetDevice(c->device));
     if (reset_counters) {
         HIPCHK(hipMemsetAsync(c->d_counters, 0, SR_NCOUNTERS * sizeof(unsigned long long), c->stream));
+        if (c->d_tail_deferred) HIPCHK(hipMemsetAsync(c->d_tail_deferred, 0, sizeof(uint32_t), c->stream));
         c->ev_used[0] = c->ev_used[4] = 0;
     }
     return SR_OK;
@@ -1522,6 +1614,30 @@ extern "C" int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap) {
     HIPCHK(hipStreamSynchronize(c->stream));
     const uint32_t n = std::min<uint32_t>(cap, SR_NCOUNTERS);
     HIPCHK(hipMemcpy(out, c->d_counters, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return (int)n;
+}
+
+// secondaries the alignment kernel handed to its tail launch since the counters were last reset (all batches of the pass)
+extern "C" int sr_ctx_tail_deferred(sr_ctx *c, uint64_t *out) {
+    if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
+    *out = 0;
+    if (!c->d_tail_deferred) return SR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint32_t v = 0;
+    HIPCHK(hipMemcpy(&v, c->d_tail_deferred, sizeof(v), hipMemcpyDeviceToHost));
+    *out = v;
+    return SR_OK;
+}
+// per-workgroup timeline of the last main launch of the instrumented instance (SR_PROFILE_TICKS=1): 4 words per workgroup
+// (SrAlignArgs::timeline); returns the number of workgroups written (<= cap_wg), 0 without the instrumented instance
+extern "C" int sr_ctx_tail_timeline(sr_ctx *c, uint64_t *out, uint32_t cap_wg) {
+    if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
+    if (!c->d_timeline) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint32_t n = std::min<uint32_t>(cap_wg, (uint32_t)c->nwg);
+    HIPCHK(hipMemcpy(out, c->d_timeline, (size_t)n * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return (int)n;
 }
 

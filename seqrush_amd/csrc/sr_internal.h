@@ -108,6 +108,16 @@ struct SrAlignArgs {
     // impl 2: [npairs] the (t, q) of the same batch that goes with (q, t) -- index inside the batch, SR_MIRROR_SECONDARY marks
     // the one that is skipped in the queue, SR_MIRROR_NONE = no partner (sr_mirror_rule.h); NULL = none at all
     const uint32_t *mirror;
+    // impl 2, tail launch: a primary that must hand its secondary to an alignment after the queue ran dry puts
+    // it on tail_list (batch-relative index) instead of aligning it on its own four waves; a second, wide launch of the same
+    // kernel (tail_mode = SR_TAIL_RUN) takes the list as its queue.  tail_list == NULL: no deferral, the behaviour without it
+    uint32_t *tail_list;            // [partners of the largest batch]
+    uint32_t *tail_count;           // entries on the list (reset per batch together with queue_head and tail_head)
+    uint32_t *tail_head;            // the tail launch's dequeue position
+    uint32_t *tail_deferred;        // deferred secondaries of the pass (not reset per batch; sr_ctx_tail_deferred)
+    int tail_mode;                  // SR_TAIL_MAIN / SR_TAIL_RUN / SR_TAIL_DEFER_ALL
+    unsigned long long *timeline;   // instrumented instance: [workgroup][4] first dequeue, start of the last alignment, exit
+                                    // (100 MHz ticks), alignments | last-from-mir_next << 32; NULL = none
     // outputs
     uint8_t *is_reverse;       // [npairs]
     int32_t *score;            // [npairs]
@@ -119,6 +129,9 @@ struct SrAlignArgs {
     int *error_flag;
 };
 #define SR_NCOUNTERS 48
+enum { SR_TAIL_MAIN = 0,        // main launch: defer a fallback secondary when the queue is dry
+       SR_TAIL_RUN = 1,         // tail launch: the list is the queue
+       SR_TAIL_DEFER_ALL = 2 }; // main launch, SR_TAIL=all: defer every fallback secondary (tests)
 
 struct SrUniteArgs {
     const uint32_t *pair_q, *pair_t;

@@ -502,6 +502,22 @@ class Context:
                     hist_bytes_loaded=int(out[44]), hist_bytes_stored=int(out[45]), base_tiles=int(out[46]),
                     base_level_diagonals=int(out[47]))
 
+    def tail_deferred(self) -> int:
+        """secondaries handed to the tail launch in the last pass (sr_ctx_tail_deferred; syncs)"""
+        v = C.c_uint64()
+        check(self.L.sr_ctx_tail_deferred(self._h, C.byref(v)))
+        return int(v.value)
+
+    def tail_timeline(self):
+        """[workgroups, 4] uint64 of the instrumented instance's last main launch (sr_ctx_tail_timeline): ticks of the first
+        dequeue, of the start of the last alignment, of the exit; alignments | last-was-own-secondary << 32"""
+        cap = int(self.workspace_report().get("workgroups", 0))
+        out = np.zeros((max(cap, 1), 4), dtype=np.uint64)
+        n = self.L.sr_ctx_tail_timeline(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), cap)
+        if n < 0:
+            check(n)
+        return out[:n]
+
     def close(self):
         if self._h:
             self.L.sr_ctx_destroy(self._h)
