@@ -250,7 +250,9 @@ int sr_ctx_counters_ext(sr_ctx *c, uint64_t out[32]);
 /* every slot (48 since ABI 2 / round 4): [32..35] tile stamps of the diagnostic build (cycles waiting for a tile's first
  * rows, cycles in its levels, tiles, extension-loop iterations), [36] bytes of wavefront rows that stayed in LDS
  * (LDS-resident histories of small base cases), [37] base cases searched again with the worst-case history region,
- * [40..43] first offending access of the bounds-checked build (pair, level, row offset, extent), rest reserved.
+ * [40..43] first offending access of the bounds-checked build (pair, level, row offset, extent), [48..51] replay of tied
+ * secondaries (52 slots): tied primaries with a tie-sensitive depth-0 search, ties in base cases only, secondaries replayed,
+ * searches they took from records; rest reserved.
  * Returns the number of slots written (<= cap) or a negative sr_status. */
 int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap);
 /* "NAME<TAB>meaning when unset<TAB>what it does" lines of every environment variable the load path reads; the ones that
@@ -339,6 +341,14 @@ int sr_mirror_bt_rank_transposed(int tag);
 int sr_mirror_bt_tie_host(const int *off);
 int sr_mirror_bp_pick_host(const int *val, const int *dist, const int *comp, const int *diag, int n, int value_bias,
                            int *pick_out, int *pick_t_out);
+/* Replay of a tied secondary from its primary's breakpoints (csrc/sr_mirror_rule.h; SR_MIRROR_REPLAY=0 switches
+ * it off, the workspace report has "mirror_replay").  Host twins: ints per breakpoint record (level, pb pe tb te cb ce, bv bh
+ * bcomp bsf bsr, tie bit, cells lo/hi, passes); the transposed record; the kernel's walk of one recursion level -- nrec records
+ * in list order, nseg segments under search of six ints (pb pe tb te cb ce) in list order -> match_out[i] = index of the
+ * untied record of `level` that is segment i's transpose, -1 = the segment is searched; returns the number matched. */
+int sr_replay_record_ints(void);
+void sr_replay_transpose_host(const int *rec, int *out);
+int sr_replay_match_host(const int *recs, int nrec, const int *segs, int nseg, int level, int *match_out);
 
 /* -------- inversion patching (`--patch-inversions`; src/inversion_aware_seqrush.rs:118-255, src/cigar_analysis.rs:23-147) ----
  * After each batch's alignment kernel the device scans every CIGAR for two-sided gaps between match ops (qgap / tgap =

@@ -45,6 +45,7 @@ EXPORTS = [
     "sr_growth_params_default", "sr_growth_gfa", "sr_growth_free", "sr_growth_groups", "sr_growth_expected", "sr_growth_fit",
     "sr_growth_report",
     "sr_ctx_tail_deferred", "sr_ctx_tail_timeline", "sr_tail_shape",
+    "sr_replay_record_ints", "sr_replay_transpose_host", "sr_replay_match_host",
 ]
 
 
@@ -335,6 +336,9 @@ def load():
     L.sr_mirror_bt_rank_transposed.argtypes = [i32]
     L.sr_mirror_bt_tie_host.argtypes = [PI]
     L.sr_mirror_bp_pick_host.argtypes = [PI, PI, PI, PI, i32, i32, PI, PI]
+    L.sr_replay_record_ints.argtypes = []
+    L.sr_replay_transpose_host.argtypes = [PI, PI]; L.sr_replay_transpose_host.restype = None
+    L.sr_replay_match_host.argtypes = [PI, i32, PI, i32, i32, PI]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

@@ -78,7 +78,8 @@ __device__ __forceinline__ SrPen load_bpen(int sel) {
 }
 
 // segment list record (global, SR_BFS_SEGREC ints)
-enum { SL_PB = 0, SL_PE, SL_TB, SL_TE, SL_CB, SL_CE, SL_REM, SL_KIND, SL_BV, SL_BH, SL_BCOMP, SL_BSF, SL_BSR };
+enum { SL_PB = 0, SL_PE, SL_TB, SL_TE, SL_CB, SL_CE, SL_REM, SL_KIND, SL_BV, SL_BH, SL_BCOMP, SL_BSF, SL_BSR,
+       SL_SOLVED, SL_PASSES };       // (blocked kernel, replaying pair: breakpoint taken from a record; passes its search took)
 enum { SK_TRIVIAL = 0, SK_BASE = 1, SK_BP = 2 };
 
 __device__ __forceinline__ int seg_kind(int plen, int tlen, int score_rem) {

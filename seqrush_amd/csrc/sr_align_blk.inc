@@ -98,6 +98,8 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
 #endif
             k_sh.dg_steps = k_sh.dg_nbase = k_sh.dg_nbp = k_sh.dg_npass = 0; k_sh.base_tiles = k_sh.base_cells = 0;
             k_sh.mir_next = -1; k_sh.mir_pairs = k_sh.mir_ties = 0;
+            k_sh.rp_record = k_sh.rp_on = k_sh.rp_ready = 0; k_sh.rp_nrec = 0;
+            k_sh.rp_replays = k_sh.rp_cached = k_sh.rp_tie_top = k_sh.rp_tie_base = 0;
             b_sh.geom.brow = a.brow; b_sh.geom.ring_scope = a.ring_scope; b_sh.geom.ring_hot = a.ring_hot;
             b_sh.geom.bbase_jobs = a.bbase_jobs; b_sh.geom.hist_w = a.hist_w; b_sh.geom.hist_levels = a.hist_levels;
             b_sh.geom.urow = urow;
@@ -140,6 +142,15 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                 if (tl_n == 0) tl_first = now;
                 if (pr < (int)a.npairs) { tl_last = now; tl_n++; tl_mir = from_mir ? 1ull : 0ull; }
             }
+            // replay (sr_mirror_rule.h): a secondary that follows its primary on this workgroup takes breakpoints from the primary's
+            // records when the primary's end said they suit it; a primary that has a partner writes records
+            k_sh.rp_on = (from_mir && k_sh.rp_ready) ? 1 : 0;
+            k_sh.rp_ready = 0; k_sh.rp_record = 0;
+            if (a.brec && !from_mir && a.tail_mode != SR_TAIL_RUN && a.mirror && pr < (int)a.npairs) {
+                const uint32_t m = a.mirror[pr];
+                if (m != SR_MIRROR_NONE && !(m & SR_MIRROR_SECONDARY)) { k_sh.rp_record = 1; k_sh.rp_nrec = 0; }
+            }
+            k_sh.rp_level = 0; k_sh.rp_rd = 0; k_sh.rp_top_tie = 0; k_sh.rp_seg_tie = 0;
             b_sh.pair = pr;
             b_sh.err = 0; b_sh.cig_cnt = 0; b_sh.score_acc = 0; k_sh.pend_op = -1; k_sh.pend_len = 0;
             k_sh.mir_tie = 0;
@@ -241,19 +252,63 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             const int rem = (a.mem_mode == 3) ? INT_MAX : -1;
             cur[SL_REM] = rem; cur[SL_KIND] = seg_kind(plen, tlen, rem);
             b_sh.list_n = 1;
+            if (is_rev) k_sh.rp_on = 0;                      // (a reverse-strand secondary is not the transpose of anything recorded)
+            if (k_sh.rp_on) k_sh.rp_replays += 1ull;
         }
         __syncthreads();
         for (;;) {                                           // one iteration per recursion level
             const int n_cur = RFL(b_sh.list_n);
             bool any_bp = false;
             int pos = 0;
+            if (RFL(k_sh.rp_on) != 0 && tid == 0) {
+                // Replay: the level's segments under search against the primary's records of the level, both in list order
+                // (two-pointer walk, sr_mirror_rule.h).  A segment whose transposed record exists and has no tie bit gets the
+                // transposed breakpoint and the search's tallies and is not searched; every other one is searched as ever.
+                GP<int> recs = (GP<int>)a.brec + (size_t)blockIdx.x * (SR_BPREC_MAX * SR_BPREC_INTS);
+                const int nrec = min(k_sh.rp_nrec, SR_BPREC_MAX), lvl = k_sh.rp_level;
+                int rd = k_sh.rp_rd;
+                unsigned long long cells = 0ull, cached = 0ull;
+                while (rd < nrec && recs[rd * SR_BPREC_INTS + SR_BR_LEVEL] < lvl) rd++;
+                for (int p = 0; p < n_cur; p++) {
+                    GP<int> e = cur + (size_t)p * SR_BFS_SEGREC;
+                    if (e[SL_KIND] != SK_BP) continue;
+                    int solved = 0;
+                    while (rd < nrec) {
+                        GP<int> r = recs + rd * SR_BPREC_INTS;
+                        if (r[SR_BR_LEVEL] != lvl) break;
+                        const int c = sr_replay_cmp(r, e);
+                        if (c > 0) break;
+                        rd++;
+                        if (c < 0) continue;
+                        if (r[SR_BR_TIE] == 0 && sr_replay_same(r, e)) {
+                            e[SL_BV] = sr_bprec_t(r, SR_BR_BV); e[SL_BH] = sr_bprec_t(r, SR_BR_BH); e[SL_BCOMP] = sr_bprec_t(r, SR_BR_BCOMP);
+                            e[SL_BSF] = r[SR_BR_BSF]; e[SL_BSR] = r[SR_BR_BSR]; e[SL_PASSES] = r[SR_BR_PASSES];
+                            cells += ((unsigned long long)(unsigned)r[SR_BR_CELLS_HI] << 32) | (unsigned long long)(unsigned)r[SR_BR_CELLS_LO];
+                            cached += 1ull; solved = 1;
+                        }
+                        break;
+                    }
+                    e[SL_SOLVED] = solved;
+                }
+                k_sh.rp_rd = rd; b_sh.cells += cells; k_sh.rp_cached += cached;
+            }
             while (pos < n_cur && RFL(b_sh.err) == 0) {      // chunks of <= SR_BFS_MAXACT segments
                 __syncthreads();
                 if (tid == 0) {
-                    int na = 0, p = pos, base = 0;
-                    for (; p < n_cur && na < SR_BFS_MAXACT; p++) {
+                    // (a replaying pair keeps the chunks it would have had: its solved segments take a place in the chunk and are
+                    // not activated, so that the levels counted per pass, chunk by chunk, come out as without the replay)
+                    int na = 0, p = pos, base = 0, ntot = 0, maxp = 0;
+                    const bool rp_on = k_sh.rp_on != 0, rp_rec = k_sh.rp_record != 0;
+                    for (; p < n_cur && ntot < SR_BFS_MAXACT; p++) {
                         GP<int> e = cur + (size_t)p * SR_BFS_SEGREC;
                         if (e[SL_KIND] != SK_BP) continue;
+                        ntot++;
+                        if (rp_on && e[SL_SOLVED] != 0) { maxp = max(maxp, e[SL_PASSES]); continue; }
+                        k_sh.sg_tie[na] = 0; k_sh.sg_sur[na] = 0; k_sh.sg_done[na] = 0;
+                        if (rp_rec) {                           // the two aligners' cell sums start at 0: what they hold when the search ends is its own
+                            b_sh.cells += k_sh.cells_l[2 * na] + k_sh.cells_l[2 * na + 1];
+                            k_sh.cells_l[2 * na] = 0ull; k_sh.cells_l[2 * na + 1] = 0ull;
+                        }
                         BSeg &sg = b_sh.seg[na];
                         sg.pb = e[SL_PB]; sg.pe = e[SL_PE]; sg.tb = e[SL_TB]; sg.te = e[SL_TE]; sg.cb = e[SL_CB]; sg.ce = e[SL_CE];
                         sg.score_f = sg.score_r = 0; sg.last_fwd = 0; sg.f_ak = sg.r_ak = 0; sg.phase = 1;
@@ -266,13 +321,19 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                         na++;
                     }
                     b_sh.nact = na; b_sh.next_pos = p; b_sh.njobs = 2 * na; b_sh.nrunning = na;
+                    k_sh.rp_ntot = ntot; k_sh.rp_maxp = maxp; k_sh.rp_npass0 = k_sh.dg_npass;
                 }
                 __syncthreads();
                 const int nact = RFL(b_sh.nact);
                 pos = RFL(b_sh.next_pos);
-                if (nact == 0) break;
+                if (RFL(k_sh.rp_ntot) == 0) break;
                 any_bp = true;
-                if (tid == 0) k_sh.dg_nbp += (unsigned long long)nact;
+                if (tid == 0) k_sh.dg_nbp += (unsigned long long)k_sh.rp_ntot;
+                if (nact == 0) {
+                    // every segment of the chunk has its breakpoint: no pass; the levels its searches would have counted
+                    if (tid == 0) k_sh.dg_steps += 2ull * (unsigned long long)k_sh.rp_ntot * B * (unsigned long long)k_sh.rp_maxp;
+                    continue;
+                }
                 const unsigned long long tb0 = KTICK();
                 const int njobs = 2 * nact;
                 for (int s0i = 0; RFL(b_sh.nrunning) > 0; s0i += B) {
@@ -380,9 +441,33 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     const int bh = sg.bp_off_f, bv = sg.bp_off_f - sg.bp_k_f;
                     if (sg.phase != 3 || sg.bp_score == INT_MAX) atomicOr(&b_sh.err, SR_DEV_ERR_SCORE_BOUND);
                     else if (bv < 0 || bv > sp || bh < 0 || bh > st) atomicOr(&b_sh.err, SR_DEV_ERR_BREAKPOINT);
-                    else { e[SL_BV] = bv; e[SL_BH] = bh; e[SL_BCOMP] = sg.bp_comp; e[SL_BSF] = sg.bp_score_f; e[SL_BSR] = sg.bp_score_r; }
+                    else {
+                        e[SL_BV] = bv; e[SL_BH] = bh; e[SL_BCOMP] = sg.bp_comp; e[SL_BSF] = sg.bp_score_f; e[SL_BSR] = sg.bp_score_r;
+                        // a primary that has a partner keeps the search for its secondary (sr_mirror_rule.h: the breakpoint record)
+                        const int ri = k_sh.rp_nrec + tid;
+                        if (k_sh.rp_record != 0 && ri < SR_BPREC_MAX) {
+                            GP<int> r = (GP<int>)a.brec + (size_t)blockIdx.x * (SR_BPREC_MAX * SR_BPREC_INTS) + ri * SR_BPREC_INTS;
+                            const unsigned long long cs = k_sh.cells_l[2 * tid] + k_sh.cells_l[2 * tid + 1] - (unsigned long long)(long long)k_sh.sg_sur[tid];
+                            r[SR_BR_LEVEL] = k_sh.rp_level;
+                            r[SR_BR_PB] = sg.pb; r[SR_BR_PE] = sg.pe; r[SR_BR_TB] = sg.tb; r[SR_BR_TE] = sg.te; r[SR_BR_CB] = sg.cb; r[SR_BR_CE] = sg.ce;
+                            r[SR_BR_BV] = bv; r[SR_BR_BH] = bh; r[SR_BR_BCOMP] = sg.bp_comp; r[SR_BR_BSF] = sg.bp_score_f; r[SR_BR_BSR] = sg.bp_score_r;
+                            r[SR_BR_TIE] = k_sh.sg_tie[tid];
+                            r[SR_BR_CELLS_LO] = (int)(unsigned)cs; r[SR_BR_CELLS_HI] = (int)(unsigned)(cs >> 32);
+                            r[SR_BR_PASSES] = k_sh.sg_done[tid] / B + 1;
+                        }
+                    }
+                    if (k_sh.sg_tie[tid] != 0) { k_sh.rp_seg_tie = 1; if (k_sh.rp_level == 0) k_sh.rp_top_tie = 1; }
                 }
                 __syncthreads();
+                if (tid == 0) {
+                    if (k_sh.rp_record != 0) k_sh.rp_nrec += nact;       // (read by the lanes above, before the barrier)
+                    if (k_sh.rp_on != 0) {
+                        // the chunk as it would have run: all its segments for the passes of its longest search
+                        const unsigned long long ran = k_sh.dg_npass - k_sh.rp_npass0;
+                        const unsigned long long all = max(ran, (unsigned long long)k_sh.rp_maxp);
+                        k_sh.dg_steps += 2ull * B * ((unsigned long long)k_sh.rp_ntot * all - (unsigned long long)nact * ran);
+                    }
+                }
                 t_bp += KTICK() - tb0;
             }
             __syncthreads();
@@ -411,6 +496,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     }
                 }
                 b_sh.list_n = m;
+                k_sh.rp_level += 1;
             }
             __syncthreads();
             { GP<int> tmp = cur; cur = nxt; nxt = tmp; }
@@ -646,12 +732,21 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                 // aligned after all.  By this workgroup, next -- unless the queue is dry (or SR_TAIL=all): then nothing else would
                 // start on this CU any more, and the secondary goes on the list of the wide tail launch that follows
                 k_sh.mir_ties += 1ull;
+                if (p_tie != 0) {                                // where the tie sits: the depth-0 search / in no search at all
+                    if (k_sh.rp_top_tie != 0) k_sh.rp_tie_top += 1ull;
+                    else if (k_sh.rp_seg_tie == 0) k_sh.rp_tie_base += 1ull;
+                }
+                // Replay: the primary kept its searches, ended well on the forward strand, and its depth-0 search decided nothing
+                // by a tie -- the secondary takes the breakpoints of all untied searches from the records and is short: it runs
+                // here, next, dry queue or not.  (SR_TAIL=all keeps deferring every tied secondary to a full alignment.)
+                const bool replay = k_sh.rp_record != 0 && p_err == 0 && !is_rev && k_sh.rp_top_tie == 0 &&
+                                    !(a.pre_oriented && a.is_reverse[mir] != 0) && a.tail_mode != SR_TAIL_DEFER_ALL;
                 bool defer = false;
-                if (a.tail_list && a.tail_mode != SR_TAIL_RUN)
+                if (!replay && a.tail_list && a.tail_mode != SR_TAIL_RUN)
                     defer = a.tail_mode == SR_TAIL_DEFER_ALL ||
                             __hip_atomic_load(a.queue_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= a.npairs;
                 if (defer) { a.tail_list[atomicAdd(a.tail_count, 1u)] = mir; atomicAdd(a.tail_deferred, 1u); }
-                else k_sh.mir_next = (int)mir;
+                else { k_sh.mir_next = (int)mir; k_sh.rp_ready = replay ? 1 : 0; }
             }
         }
         if (a.fuse_unite) {
@@ -703,6 +798,10 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
         if (k_sh.dg_redo) atomicAdd(&a.counters[37], k_sh.dg_redo);
         if (k_sh.mir_pairs) atomicAdd(&a.counters[38], k_sh.mir_pairs);
         if (k_sh.mir_ties) atomicAdd(&a.counters[39], k_sh.mir_ties);
+        if (k_sh.rp_tie_top) atomicAdd(&a.counters[48], k_sh.rp_tie_top);
+        if (k_sh.rp_tie_base) atomicAdd(&a.counters[49], k_sh.rp_tie_base);
+        if (k_sh.rp_replays) atomicAdd(&a.counters[50], k_sh.rp_replays);
+        if (k_sh.rp_cached) atomicAdd(&a.counters[51], k_sh.rp_cached);
         atomicAdd(&a.counters[46], k_sh.base_tiles); atomicAdd(&a.counters[47], k_sh.base_cells);
         if (PROF && a.timeline) {
             unsigned long long *tl = a.timeline + 4ull * blockIdx.x;

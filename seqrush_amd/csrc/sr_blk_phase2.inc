@@ -281,7 +281,7 @@ __device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t>
                     if (key != ~0ull) {
                         const int val = (int)(key >> 42) - gapmax;
                         if (val < sg.bp_score) {
-                            if (sr_mirror_bp_tie(key, key_t)) k_sh.mir_tie = 1;     // the transposed pair would have split elsewhere
+                            if (sr_mirror_bp_tie(key, key_t)) { k_sh.mir_tie = 1; k_sh.sg_tie[sa] = 1; }     // the transposed pair would have split elsewhere
                             const int ord = (int)((key >> 32) & 1023ull), i = ord / 5, rank = ord - i * 5;
                             const int c = (rank == 0) ? SR_C_D2 : (rank == 1) ? SR_C_I2 : (rank == 2) ? SR_C_D1 : (rank == 3) ? SR_C_I1 : SR_C_M;
                             const int k0 = (int)(unsigned)(key & 0xffffffffull) - (1 << 30), k1 = kinv - k0;
@@ -312,6 +312,7 @@ __device__ __forceinline__ void blk_phase2(const KRows<OT, ST> &RR, GP<uint32_t>
                 const int last = min(avail, max(f, r));
                 const long long sur = blk_surplus(pen, 2 * sa, last, avail) + blk_surplus(pen, 2 * sa + 1, last, avail);
                 atomicAdd(&b_sh.cells, (unsigned long long)(-sur));
+                k_sh.sg_sur[sa] = (int)sur; k_sh.sg_done[sa] = s0;        // (the search's own tallies: its breakpoint record)
             }
         }
         if (tid < 64) KPRIO_LO();

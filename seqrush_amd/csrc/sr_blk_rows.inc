@@ -39,6 +39,15 @@ struct KShared {
     int mir_tie, mir_next;
     unsigned long long mir_snap[4];
     unsigned long long mir_pairs, mir_ties;    // secondaries emitted by symmetry / aligned after all -> counters[38], [39]
+    // replay of a tied secondary (sr_mirror_rule.h, DESIGN.md 4.3).  Per segment of the chunk: a tie-sensitive accepted call,
+    // the surplus cells stage W took off, the first level of the block in which its search ended
+    int sg_tie[SR_BFS_MAXACT], sg_sur[SR_BFS_MAXACT], sg_done[SR_BFS_MAXACT];
+    int rp_record, rp_on, rp_ready;    // the pair in hand: writes records / takes breakpoints from them; the records suit mir_next
+    int rp_level, rp_nrec, rp_rd;      // recursion level, records written, the walk's position in them
+    int rp_top_tie, rp_seg_tie;        // the pair's depth-0 search / any of its searches was tie-sensitive
+    int rp_ntot, rp_maxp;              // chunk of a replaying pair: its segments solved ones included, most passes a solved one took
+    unsigned long long rp_npass0;      // dg_npass when the chunk began
+    unsigned long long rp_replays, rp_cached, rp_tie_top, rp_tie_base;   // -> counters[50], [51], [48], [49]
     int redo_from;                     // base cases: first job of the batch that outgrew the levels it was given (BJ_MAX: none)
     int pend_op, pend_len;             // CIGAR emission: the run being built (not yet stored)
     unsigned long long row_w[4][16];   // per wave, lane accesses of its tiles' row loads / stores (summed when the kernel ends); [2..3]: the base-case histories' share

@@ -54,6 +54,7 @@ static const SrKnob SR_KNOBS[] = {
     {"SR_ORIENT_LEVELS", "off", "orientation level by level even for the default penalties"},
     {"SR_NO_KBITS", "off", "no q-gram bound in the orientation kernel"},
     {"SR_NO_MIRROR", "off", "1 = no pair has a mirror partner: (q, t) and (t, q) are both aligned (A/B runs, tests)"},
+    {"SR_MIRROR_REPLAY", "on", "0 = a tied secondary is aligned in full: its primary keeps no breakpoint records and none is matched (A/B runs, tests)"},
     {"SR_NO_FUSED_UNITE", "off", "sr_ctx_run launches sr_unite_kernel per batch instead of uniting inside the blocked alignment kernel"},
     {"SR_PROFILE_TICKS", "0", "1 = launch the instrumented instance (100 MHz tick counters, per-workgroup timeline)"},
     {"SR_TAIL", "on", "0 = no tail launch: a tied secondary is always aligned by its primary's workgroup (A/B runs); all = every such secondary is deferred to the tail launch (tests)"},
@@ -612,6 +613,7 @@ struct Plan {
     // per-workgroup workspace (cells unless stated)
     int ring_scope = 0, ring_hot = 0, hist_levels = 0, hist_w = 0, brow = 0, kdepth = 0, kdepth2 = 0;
     uint64_t bring_wg = 0, bhist_wg = 0, hist_cap = 0, hist_nul_w = 0, bseg_wg = 0, bbt_wg = 0, bcl_wg = 0, per_wg_bytes = 0;
+    uint64_t brec_wg = 0, brec_bytes = 0;          // replay: bytes of a workgroup's breakpoint records; of all (0: the load keeps none)
     // memory budget
     size_t free_b = 0;
     uint64_t arena_ops = 0, left = 0, max_reserve = 4;
@@ -898,9 +900,36 @@ extern "C" int sr_mirror_bp_pick_host(const int *val, const int *dist, const int
     }
     return n > 0 && sr_mirror_bp_tie(best, best_t) ? 1 : 0;
 }
+// replay (sr_mirror_rule.h): the transposed record; the kernel's walk of one level -- nrec records of SR_BPREC_INTS ints in
+// list order (any levels; those of `level` are used), nseg segments under search of six ints (pb pe tb te cb ce) in list
+// order -> match_out[i] = index of the record whose breakpoint segment i takes, -1 = it is searched; returns the matches
+extern "C" int sr_replay_record_ints(void) { return SR_BPREC_INTS; }
+extern "C" void sr_replay_transpose_host(const int *rec, int *out) {
+    for (int f = 0; f < SR_BPREC_INTS; f++) out[f] = sr_bprec_t(rec, f);
+}
+extern "C" int sr_replay_match_host(const int *recs, int nrec, const int *segs, int nseg, int level, int *match_out) {
+    int rd = 0, n = 0;
+    while (rd < nrec && recs[rd * SR_BPREC_INTS + SR_BR_LEVEL] < level) rd++;
+    for (int p = 0; p < nseg; p++) {
+        const int *e = segs + 6 * p;
+        match_out[p] = -1;
+        while (rd < nrec) {
+            const int *r = recs + rd * SR_BPREC_INTS;
+            if (r[SR_BR_LEVEL] != level) break;
+            const int c = sr_replay_cmp(r, e);
+            if (c > 0) break;
+            rd++;
+            if (c < 0) continue;
+            if (r[SR_BR_TIE] == 0 && sr_replay_same(r, e)) { match_out[p] = rd - 1; n++; }
+            break;
+        }
+    }
+    return n;
+}
 
 // static tables of the alignment kernels (upper estimates; the blocked kernel's scan arrays of the fused unite grow with the
-// workgroup: 25 024 / 28 144 / 34 384 bytes at 256 / 512 / 1024 threads with the second key table of breakpoint detection)
+// workgroup: 25 296 / 28 416 / 34 656 bytes at 256 / 512 / 1024 threads with the second key table of breakpoint detection and
+// the replay's per-segment state)
 static size_t align_static_lds(bool wave_wg, int impl, int nthreads) {
     return (size_t)(wave_wg ? 6 : impl != 2 ? 28 : nthreads >= 1024 ? 34 : nthreads >= 512 ? 28 : 25) * 1024;
 }
@@ -1049,8 +1078,11 @@ static int plan_workspace(const sr_ctx *c, const SrPen &pen, const SrPen &ori, u
     // depends on the threads of a workgroup -- bbase_jobs does only for the one-wave builds, which have no tail launch.)
     pl.bseg_wg = 2ULL * SR_BFS_MAXSEG * SR_BFS_SEGREC * 4;          // bytes
     pl.bbt_wg = (uint64_t)pl.bbase_jobs * SR_BFS_BTCAP * 4;        // bytes
+    // breakpoint records of a primary (replay, sr_mirror_rule.h); allocated only by loads that have partners (load_device)
+    pl.brec_wg = impl == 2 ? (uint64_t)SR_BPREC_MAX * SR_BPREC_INTS * 4 : 0;
     pl.bcl_wg = 0;                 // (round 3: breakpoint detection keeps a band per unit in LDS instead of a candidate list in global memory)
-    pl.per_wg_bytes = pl.bring_wg * pl.rsz + pl.bhist_wg * pl.osz + pl.bseg_wg + pl.bbt_wg + pl.bcl_wg * 4 + (impl == 2 ? 32 * SR_BLK_MAK_SLOTS * 4 : 0);
+    pl.per_wg_bytes = pl.bring_wg * pl.rsz + pl.bhist_wg * pl.osz + pl.bseg_wg + pl.bbt_wg + pl.bcl_wg * 4 + (impl == 2 ? 32 * SR_BLK_MAK_SLOTS * 4 : 0) +
+                      pl.brec_wg;       // (budgeted for every blocked load; a load without partners leaves it unallocated)
     (void)c;
     return SR_OK;
 }
@@ -1206,6 +1238,14 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     }
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bseg_wg))) return r; a.bseg = (int *)d;
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bbt_wg))) return r; a.bbt = (uint32_t *)d;
+    {   // replay of tied secondaries: only where there are partners (SR_MIRROR_REPLAY=0: the kernel without it)
+        const char *rpk = knob("SR_MIRROR_REPLAY");
+        pl.brec_bytes = 0;
+        if (impl == 2 && c->mirror_partners > 0 && pl.brec_wg && !(rpk && atoi(rpk) == 0)) {
+            pl.brec_bytes = (uint64_t)nwg * pl.brec_wg;
+            if ((r = dev_alloc(c, &d, pl.brec_bytes))) return r; a.brec = (int *)d;
+        }
+    }
     if (pl.bcl_wg) { if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bcl_wg * 4))) return r; a.bcl = (uint32_t *)d; a.bcl_wg_stride = pl.bcl_wg; }
     if (impl == 2) { if ((r = dev_alloc(c, &d, (uint64_t)nwg * 32 * SR_BLK_MAK_SLOTS * 4))) return r; a.bmak = (int *)d; }
     // orientation as its own kernel, one pair per wave (sr_orient.hip); SR_PREORIENT=0 keeps it in the alignment kernel.
@@ -1296,7 +1336,7 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
 
 static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const Plan &pl) {
     const uint32_t np = (uint32_t)c->pair_q.size();
-    char buf[1800];
+    char buf[2048];
     // which build the launchers take (srk_align: lean wave build / wide level kernel; srk_orient: blocked or level by level)
     const SrPen &ori = c->aa.ori;
     const char *oroute = c->onwg == 0 ? "in-kernel"
@@ -1308,14 +1348,14 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
              "\"base_history_bytes_per_workgroup\": %llu, \"workspace_bytes\": %llu, \"cigar_arena_bytes\": %llu, "
              "\"orientation_ring_bytes\": %llu, \"union_find_bytes\": %llu, \"device_free_bytes_at_load\": %zu, \"kernel_build\": \"%s\", "
              "\"ring_depth_m\": %d, \"ring_depth_id\": %d, \"fused_unite\": %d, \"wave_build\": %d, \"level_kernel_wide\": %d, "
-             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"tail_threads\": %d, \"knobs\": ",
+             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"tail_threads\": %d, \"mirror_replay\": %d, \"replay_record_bytes\": %llu, \"knobs\": ",
              np, pl.nbatch, pk.sm.bits, pl.osz, pl.impl == 2 ? pl.rsz : pl.osz, pl.impl, pl.impl == 2 ? pl.kblock : 1, pen.two ? 1 : 0, pl.lazy_id,
              pl.nwg, c->nthreads, pl.wg_per_cu, c->lds_bytes,
              (unsigned long long)(pl.bring_wg * pl.rsz), (unsigned long long)(pl.bhist_wg * pl.osz),
              (unsigned long long)((uint64_t)pl.nwg * pl.per_wg_bytes), (unsigned long long)(pl.arena_ops * 4), (unsigned long long)pl.oring_bytes,
              (unsigned long long)(3ULL * c->uf_size * 8), pl.free_b, srk_align_blk_build_tag(), pl.kdepth, pl.kdepth2, c->fuse_unite ? 1 : 0,
              pl.wave_wg ? 1 : 0, (pl.impl == 1 && pl.ring_scope + 1 > 32) ? 1 : 0, c->aa.profile_ticks, oroute, srk_source_digest(),
-             (unsigned long long)c->mirror_partners, c->tail_threads);
+             (unsigned long long)c->mirror_partners, c->tail_threads, pl.brec_bytes ? 1 : 0, (unsigned long long)pl.brec_bytes);
     c->workspace_report = std::string(buf) + knobs_json() + "}";
 }
 
@@ -1607,7 +1647,7 @@ extern "C" int sr_ctx_counters_ext(sr_ctx *c, uint64_t out[32]) {
     HIPCHK(hipMemcpy(out, c->d_counters, 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return SR_OK;
 }
-// every slot the device keeps (SR_NCOUNTERS = 48 since round 4); returns the number of slots written (<= cap) or a negative status
+// every slot the device keeps (SR_NCOUNTERS = 52: 48 since round 4, [48..51] the replay's); returns the number of slots written (<= cap) or a negative status
 extern "C" int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap) {
     if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
     HIPCHK(hipSetDevice(c->device));

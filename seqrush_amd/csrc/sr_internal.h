@@ -116,6 +116,9 @@ struct SrAlignArgs {
     uint32_t *tail_head;            // the tail launch's dequeue position
     uint32_t *tail_deferred;        // deferred secondaries of the pass (not reset per batch; sr_ctx_tail_deferred)
     int tail_mode;                  // SR_TAIL_MAIN / SR_TAIL_RUN / SR_TAIL_DEFER_ALL
+    // impl 2, replay (sr_mirror_rule.h): per workgroup SR_BPREC_MAX breakpoint records of SR_BPREC_INTS ints, written
+    // by a primary that has a partner and read by its secondary when the same workgroup aligns it next; NULL = no replay
+    int *brec;
     unsigned long long *timeline;   // instrumented instance: [workgroup][4] first dequeue, start of the last alignment, exit
                                     // (100 MHz ticks), alignments | last-from-mir_next << 32; NULL = none
     // outputs
@@ -128,7 +131,7 @@ struct SrAlignArgs {
     unsigned long long *counters; // [SR_NCOUNTERS]
     int *error_flag;
 };
-#define SR_NCOUNTERS 48
+#define SR_NCOUNTERS 52
 enum { SR_TAIL_MAIN = 0,        // main launch: defer a fallback secondary when the queue is dry
        SR_TAIL_RUN = 1,         // tail launch: the list is the queue
        SR_TAIL_DEFER_ALL = 2 }; // main launch, SR_TAIL=all: defer every fallback secondary (tests)

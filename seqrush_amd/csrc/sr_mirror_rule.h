@@ -64,3 +64,46 @@ SR_MIR_HD inline bool sr_mirror_bp_tie(unsigned long long key, unsigned long lon
     const int k = (int)(unsigned)(key & 0xffffffffull) - (1 << 30), k_t = (1 << 30) - (int)(unsigned)(key_t & 0xffffffffull);
     return c != c_t || k != k_t;
 }
+
+// ---- replay of a tied secondary from its primary's breakpoints (DESIGN.md 4.3 "Replay") -------------------------------
+// A breakpoint search is a function of its segment (pb, pe, tb, te, begin / end component) alone.  By the symmetry above the
+// search of the transposed segment finds the transposed breakpoint -- bv <-> bh, component I <-> D, the same two scores --
+// unless one of its accepted overlap calls was tie-sensitive (rule 2).  A primary that has a partner therefore keeps one
+// record per search; the secondary, when the same workgroup aligns it next, takes the breakpoint of every segment whose
+// transposed record exists and carries no tie bit, and searches the others.  Base cases are always recomputed (rule 1).
+// Record: SR_BPREC_INTS ints, appended level by level in list order.
+#define SR_BPREC_INTS 16
+#define SR_BPREC_MAX 2048            // records a workgroup keeps per primary (later searches are not recorded: searched again)
+enum { SR_BR_LEVEL = 0, SR_BR_PB, SR_BR_PE, SR_BR_TB, SR_BR_TE, SR_BR_CB, SR_BR_CE, SR_BR_BV, SR_BR_BH, SR_BR_BCOMP, SR_BR_BSF,
+       SR_BR_BSR, SR_BR_TIE, SR_BR_CELLS_LO, SR_BR_CELLS_HI, SR_BR_PASSES };
+// component of the transposed pair: I1 <-> D1, I2 <-> D2 (sr_internal.h SR_C_*: M 0, I1 1, I2 2, D1 3, D2 4)
+SR_MIR_HD inline int sr_mirror_comp_t(int c) { return c == 0 ? 0 : (c <= 2 ? c + 2 : c - 2); }
+// field f of the transposed record, read from record r (any pointer-like type): pb/pe <-> tb/te, bv <-> bh, components
+// mapped; level, scores, tie bit and tallies as they are.  An involution.
+template <typename P>
+SR_MIR_HD inline int sr_bprec_t(P r, int f) {
+    switch (f) {
+    case SR_BR_PB: return r[SR_BR_TB];
+    case SR_BR_PE: return r[SR_BR_TE];
+    case SR_BR_TB: return r[SR_BR_PB];
+    case SR_BR_TE: return r[SR_BR_PE];
+    case SR_BR_CB: return sr_mirror_comp_t(r[SR_BR_CB]);
+    case SR_BR_CE: return sr_mirror_comp_t(r[SR_BR_CE]);
+    case SR_BR_BV: return r[SR_BR_BH];
+    case SR_BR_BH: return r[SR_BR_BV];
+    case SR_BR_BCOMP: return sr_mirror_comp_t(r[SR_BR_BCOMP]);
+    default: return r[f];
+    }
+}
+// Two-pointer walk of a level.  Both lists are in list order; the segments under search of one level are disjoint pieces
+// of one monotone path and none is empty, so pb + tb grows strictly along either list (and is the same for a segment and
+// its transpose).  One step compares the record at hand with the segment at hand (its first six ints: pb pe tb te cb ce):
+//   < 0: the record lies before the segment -> next record;  > 0: behind it -> the segment has no record, next segment;
+//   0: same place -> next of both, and the segment is matched iff sr_replay_same().
+template <typename P, typename Q>
+SR_MIR_HD inline int sr_replay_cmp(P rec, Q seg) { return (rec[SR_BR_PB] + rec[SR_BR_TB]) - (seg[0] + seg[2]); }
+template <typename P, typename Q>
+SR_MIR_HD inline bool sr_replay_same(P rec, Q seg) {
+    return sr_bprec_t(rec, SR_BR_PB) == seg[0] && sr_bprec_t(rec, SR_BR_PE) == seg[1] && sr_bprec_t(rec, SR_BR_TB) == seg[2] &&
+           sr_bprec_t(rec, SR_BR_TE) == seg[3] && sr_bprec_t(rec, SR_BR_CB) == seg[4] && sr_bprec_t(rec, SR_BR_CE) == seg[5];
+}

@@ -477,8 +477,8 @@ class Context:
 
     def counters(self):
         """device counters of the last align / unite (include/seqrush_amd.h sr_ctx_counters_all): every name maps to ONE slot"""
-        out = (C.c_uint64 * 48)()
-        n = self.L.sr_ctx_counters_all(self._h, out, 48)
+        out = (C.c_uint64 * 52)()
+        n = self.L.sr_ctx_counters_all(self._h, out, 52)
         if n < 0:
             check(n)
         return dict(row_bytes_loaded=int(out[16]), row_bytes_stored=int(out[17]), tk_recompute=int(out[18]),
@@ -500,7 +500,12 @@ class Context:
                     experiment=[int(out[44]), int(out[45]), int(out[46]), int(out[47])],
                     # blocked kernel: the base-case histories' share of row_bytes_*, base-case tiles and level-diagonals as executed
                     hist_bytes_loaded=int(out[44]), hist_bytes_stored=int(out[45]), base_tiles=int(out[46]),
-                    base_level_diagonals=int(out[47]))
+                    base_level_diagonals=int(out[47]),
+                    # replay of tied secondaries: tied primaries whose depth-0 search was tie-sensitive / whose
+                    # ties all sit in base-case backtraces; secondaries that took breakpoints from their primary's records;
+                    # searches they did not run
+                    mirror_tie_top=int(out[48]), mirror_tie_base_only=int(out[49]), mirror_replays=int(out[50]),
+                    replay_cached_searches=int(out[51]))
 
     def tail_deferred(self) -> int:
         """secondaries handed to the tail launch in the last pass (sr_ctx_tail_deferred; syncs)"""
