@@ -104,6 +104,29 @@ enum { SRO_MEM_HIGH = 0, SRO_MEM_ULTRALOW = 3 };   /* lib_wfa2 MemoryMode */
 int sro_wfa_align(const uint8_t *pattern, int plen, const uint8_t *text,
                   int tlen, const sro_penalties *pen, int memory_mode,
                   uint8_t **cigar, int *cigar_len, int *score);
+/* The SRO_MEM_ULTRALOW alignment with a trace (tests/test_tie_lattice_host.py): the same CIGAR and score,
+ * plus one record per call of the recursion, in recursion order (a search, then everything under its first half, then
+ * everything under its second).  The tie bits say whether the TRANSPOSED pair (text as pattern) would have decided
+ * otherwise at the only two places where the rules see the order of the two sequences; they are computed here by a
+ * plain restatement of the transposed pair's order, independent of csrc/sr_mirror_rule.h:
+ *   search:    a second breakpoint goes through the same sequence of overlap calls, walking the components I2 D2 I1 D1 M
+ *              and the diagonals downwards; tie = the two final breakpoints name another (component, diagonal);
+ *   base case: tie = in some M step of the backtrace the tag priority MISMS > I2e > I2o > I1e > I1o > D2e > D2o > D1e
+ *              > D1o picks another tag.
+ * Coordinates are the pair's (pb pe: pattern, tb te: text; bv bh: the breakpoint, so the halves are [pb, bv) x [tb, bh)
+ * and [bv, pe) x [bh, te)); cig_b cig_e: the slice of the raw CIGAR a base case or a trivial segment wrote. */
+enum { SRO_TRACE_SEARCH = 0, SRO_TRACE_BASE = 1, SRO_TRACE_TRIVIAL = 2 };
+typedef struct {
+    int32_t kind, depth, pb, pe, tb, te, cb, ce;
+    int32_t bv, bh, comp, score_f, score_r;    /* search */
+    int32_t tie;
+    int32_t cig_b, cig_e;                      /* base case, trivial segment */
+} sro_trace_rec;
+/* recs may hold cap records; *nrec = the number of calls (records past cap are counted, not written).  plen, tlen > 0. */
+int sro_wfa_align_traced(const uint8_t *pattern, int plen, const uint8_t *text,
+                         int tlen, const sro_penalties *pen, uint8_t **cigar,
+                         int *cigar_len, int *score, sro_trace_rec *recs, int cap,
+                         int *nrec);
 /* Score only; max_score<0 = unbounded, else returns INT32_MAX in *score when
  * the optimal score exceeds max_score. */
 int sro_wfa_score(const uint8_t *pattern, int plen, const uint8_t *text,

@@ -432,10 +432,21 @@ static int bt_best(int32_t *best_off, int *best_type, int32_t off, int type) {
     return 1;
 }
 
+/* Traced variant only (sro_wfa_align_traced): the same choice under the priority the transposed pair gives the tags,
+ * written in this pair's terms -- MISMS > I2e > I2o > I1e > I1o > D2e > D2o > D1e > D1o (its D is this pair's I). */
+static int bt_rank_t(int type) { return type == BT_MISMS ? type : (type <= BT_I2_EXT ? type + 4 : type - 4); }
+static void bt_best_t(int32_t *best_off, int *best_type, int32_t off, int type) {
+    if (off < 0) return;
+    if (off > *best_off || (off == *best_off && bt_rank_t(type) > bt_rank_t(*best_type))) {
+        *best_off = off; *best_type = type;
+    }
+}
+
 /* Full-memory WFA on view w between components cb -> ce.  Appends the raw
- * CIGAR (forward order) to out.  Returns score or <0 on failure. */
+ * CIGAR (forward order) to out.  Returns score or <0 on failure.
+ * tie1 (traced variant, else NULL): set when some M step of the backtrace picks another tag under bt_best_t. */
 static int wfa_full(const view_t *w, const sro_penalties *pen, int cb, int ce,
-                    cig_t *out, uint64_t *cells) {
+                    cig_t *out, uint64_t *cells, int *tie1) {
     wfa_t a;
     const arena_mark mark = arena_get_mark();
     wfa_init(&a, w, pen, 0);
@@ -456,6 +467,7 @@ static int wfa_full(const view_t *w, const sro_penalties *pen, int cb, int ce,
     if (!found) { wfa_free(&a); arena_release(mark); return -1; }
     const int score = s;
     /* backtrace (WFA2 wavefront_backtrace_affine semantics) */
+#define BT_CAND(o, tag) do { const int32_t o_ = (o); bt_best(&bo, &bty, o_, tag); if (tie1) bt_best_t(&bo_t, &bty_t, o_, tag); } while (0)
     cig_t r = {0, 0, 0};   /* reversed */
     int k = k_end, comp = ce;
     int32_t off = tlen;
@@ -470,23 +482,25 @@ static int wfa_full(const view_t *w, const sro_penalties *pen, int cb, int ce,
                 break;
             }
             int32_t bo = WF_NULL; int bty = 0;
+            int32_t bo_t = WF_NULL; int bty_t = 0;
             const level_t *Lx = wfa_level(&a, s - a.x);
             const level_t *Lo1 = wfa_level(&a, s - a.o1 - a.e1);
             const level_t *Le1 = wfa_level(&a, s - a.e1);
             const uint32_t lim = (uint32_t)IMIN(tlen, plen + k);
-            bt_best(&bo, &bty, bnd(lv_get(Lx, SRO_M, k) + 1, lim), BT_MISMS);
-            bt_best(&bo, &bty, bnd(lv_get(Lo1, SRO_M, k - 1) + 1, lim), BT_I1_OPEN);
-            bt_best(&bo, &bty, bnd(lv_get(Le1, SRO_I1, k - 1) + 1, lim), BT_I1_EXT);
-            bt_best(&bo, &bty, bnd(lv_get(Lo1, SRO_M, k + 1), lim), BT_D1_OPEN);
-            bt_best(&bo, &bty, bnd(lv_get(Le1, SRO_D1, k + 1), lim), BT_D1_EXT);
+            BT_CAND(bnd(lv_get(Lx, SRO_M, k) + 1, lim), BT_MISMS);
+            BT_CAND(bnd(lv_get(Lo1, SRO_M, k - 1) + 1, lim), BT_I1_OPEN);
+            BT_CAND(bnd(lv_get(Le1, SRO_I1, k - 1) + 1, lim), BT_I1_EXT);
+            BT_CAND(bnd(lv_get(Lo1, SRO_M, k + 1), lim), BT_D1_OPEN);
+            BT_CAND(bnd(lv_get(Le1, SRO_D1, k + 1), lim), BT_D1_EXT);
             if (a.two) {
                 const level_t *Lo2 = wfa_level(&a, s - a.o2 - a.e2);
                 const level_t *Le2 = wfa_level(&a, s - a.e2);
-                bt_best(&bo, &bty, bnd(lv_get(Lo2, SRO_M, k - 1) + 1, lim), BT_I2_OPEN);
-                bt_best(&bo, &bty, bnd(lv_get(Le2, SRO_I2, k - 1) + 1, lim), BT_I2_EXT);
-                bt_best(&bo, &bty, bnd(lv_get(Lo2, SRO_M, k + 1), lim), BT_D2_OPEN);
-                bt_best(&bo, &bty, bnd(lv_get(Le2, SRO_D2, k + 1), lim), BT_D2_EXT);
+                BT_CAND(bnd(lv_get(Lo2, SRO_M, k - 1) + 1, lim), BT_I2_OPEN);
+                BT_CAND(bnd(lv_get(Le2, SRO_I2, k - 1) + 1, lim), BT_I2_EXT);
+                BT_CAND(bnd(lv_get(Lo2, SRO_M, k + 1), lim), BT_D2_OPEN);
+                BT_CAND(bnd(lv_get(Le2, SRO_D2, k + 1), lim), BT_D2_EXT);
             }
+            if (tie1 && bty_t != bty) *tie1 = 1;
             if (bty == 0 || bo > off) { ok = 0; break; }
             cig_push(&r, 'M', off - bo);
             off = bo;
@@ -533,6 +547,7 @@ static int wfa_full(const view_t *w, const sro_penalties *pen, int cb, int ce,
         }
         if (s < 0) { ok = 0; break; }
     }
+#undef BT_CAND
     if (ok) {
         for (int i = r.n - 1; i >= 0; i--) cig_push(out, r.b[i], 1);
     }
@@ -615,8 +630,65 @@ static void bialign_overlap(const wfa_t *a0, const wfa_t *a1, int score_0,
     }
 }
 
+/* Traced variant only: the same two functions as the transposed pair walks them, in this pair's terms -- components in
+ * the order I2 D2 I1 D1 M (its D is this pair's I), diagonals from min_hi down to max_lo (its k is this pair's -k, for
+ * either aligner).  Fed the same sequence of calls as bp, a second bp_t ends on the candidate the transposed pair's
+ * search accepts. */
+static void bp_check_t(const level_t *L0, const level_t *L1, int comp, int plen,
+                       int tlen, int score_0, int score_1, int gap_open,
+                       int bp_forward, bp_t *bp) {
+    const int kinv = tlen - plen;
+    int lo_0 = L0->lo, hi_0 = L0->hi;
+    int lo_1 = kinv - L1->hi, hi_1 = kinv - L1->lo;
+    if (hi_1 < lo_0 || hi_0 < lo_1) return;
+    int min_hi = IMIN(hi_0, hi_1), max_lo = IMAX(lo_0, lo_1);
+    for (int k_0 = min_hi; k_0 >= max_lo; k_0--) {
+        const int k_1 = kinv - k_0;
+        const int32_t o0 = L0->c[comp][k_0 + L0->off0];
+        const int32_t o1 = L1->c[comp][k_1 + L1->off0];
+        if (o0 < 0 || o1 < 0) continue;
+        if (o0 + o1 >= tlen && score_0 + score_1 - gap_open < bp->score) {
+            if (bp_forward) {
+                bp->score_f = score_0; bp->score_r = score_1;
+                bp->k_f = k_0; bp->k_r = k_1; bp->off_f = o0; bp->off_r = o1;
+            } else {
+                bp->score_f = score_1; bp->score_r = score_0;
+                bp->k_f = k_1; bp->k_r = k_0; bp->off_f = o1; bp->off_r = o0;
+            }
+            bp->score = score_0 + score_1 - gap_open;
+            bp->comp = comp;
+            return;
+        }
+    }
+}
+
+static void bialign_overlap_t(const wfa_t *a0, const wfa_t *a1, int score_0,
+                              int score_1, int bp_forward, bp_t *bp) {
+    const level_t *L0 = wfa_level(a0, score_0);
+    if (!L0) return;
+    const int plen = a0->w.plen, tlen = a0->w.tlen;
+    for (int i = 0; i < a0->scope; i++) {
+        const int score_i = score_1 - i;
+        if (score_i < 0) break;
+        const level_t *Li = wfa_level(a1, score_i);
+        if (a0->two && Li) {
+            if (score_0 + score_i - a0->o2 < bp->score) {
+                bp_check_t(L0, Li, SRO_I2, plen, tlen, score_0, score_i, a0->o2, bp_forward, bp);
+                bp_check_t(L0, Li, SRO_D2, plen, tlen, score_0, score_i, a0->o2, bp_forward, bp);
+            }
+        }
+        if (Li && score_0 + score_i - a0->o1 < bp->score) {
+            bp_check_t(L0, Li, SRO_I1, plen, tlen, score_0, score_i, a0->o1, bp_forward, bp);
+            bp_check_t(L0, Li, SRO_D1, plen, tlen, score_0, score_i, a0->o1, bp_forward, bp);
+        }
+        if (score_0 + score_i >= bp->score) continue;
+        if (Li) bp_check_t(L0, Li, SRO_M, plen, tlen, score_0, score_i, 0, bp_forward, bp);
+    }
+}
+
+/* bpt (traced variant, else NULL): the transposed pair's walk over the same calls */
 static int bialign_find_breakpoint(const view_t *w, const sro_penalties *pen,
-                                   int cb, int ce, bp_t *bp, uint64_t *cells) {
+                                   int cb, int ce, bp_t *bp, uint64_t *cells, bp_t *bpt) {
     wfa_t F, R;
     view_t wr = *w; wr.rev = 1;
     const arena_mark mark = arena_get_mark();
@@ -629,6 +701,7 @@ static int bialign_find_breakpoint(const view_t *w, const sro_penalties *pen,
     long smax = 2L * ((long)F.o1 + (long)F.e1 * plen + (long)F.o1 + (long)F.e1 * tlen) + 1024;
     int score_f = 0, score_r = 0;
     bp->score = INT_MAX;
+    if (bpt) bpt->score = INT_MAX;
     wfa_level0(&F, cb);
     wfa_level0(&R, ce);
     int f_max_ak = level_max_ak(wfa_level(&F, 0));
@@ -653,12 +726,14 @@ static int bialign_find_breakpoint(const view_t *w, const sro_penalties *pen,
             const int min_score_r = (score_r > scope - 1) ? score_r - (scope - 1) : 0;
             if (score_f + min_score_r - gap_opening >= bp->score) break;
             bialign_overlap(&F, &R, score_f, score_r, 1, bp);
+            if (bpt) bialign_overlap_t(&F, &R, score_f, score_r, 1, bpt);
             ++score_r;
             wfa_step(&R, score_r);
         }
         const int min_score_f = (score_f > scope - 1) ? score_f - (scope - 1) : 0;
         if (min_score_f + score_r - gap_opening >= bp->score) break;
         bialign_overlap(&R, &F, score_r, score_f, 0, bp);
+        if (bpt) bialign_overlap_t(&R, &F, score_r, score_f, 0, bpt);
         ++score_f;
         wfa_step(&F, score_f);
         last_wf_forward = 1;
@@ -672,29 +747,54 @@ static int bialign_find_breakpoint(const view_t *w, const sro_penalties *pen,
     return status;
 }
 
+/* records of the traced variant (sr_oracle.h): one per bialign call, in recursion order; past the capacity they are
+ * counted and not written */
+typedef struct { sro_trace_rec *r; int cap, n; } trace_t;
+static sro_trace_rec *trace_new(trace_t *tr, int kind, int depth, int pb, int pe, int tb, int te, int cb, int ce) {
+    static _Thread_local sro_trace_rec spill;
+    sro_trace_rec *x = tr->n < tr->cap ? &tr->r[tr->n] : &spill;
+    tr->n++;
+    memset(x, 0, sizeof(*x));
+    x->kind = kind; x->depth = depth; x->pb = pb; x->pe = pe; x->tb = tb; x->te = te; x->cb = cb; x->ce = ce;
+    return x;
+}
+
 static int bialign(const uint8_t *p, int pb, int pe, const uint8_t *t, int tb,
                    int te, const sro_penalties *pen, int cb, int ce,
-                   int score_remaining, cig_t *out, uint64_t *cells, int depth) {
+                   int score_remaining, cig_t *out, uint64_t *cells, int depth, trace_t *tr) {
     const int plen = pe - pb, tlen = te - tb;
-    if (tlen == 0) { cig_push(out, 'D', plen); return 0; }
-    if (plen == 0) { cig_push(out, 'I', tlen); return 0; }
+    if (tlen == 0 || plen == 0) {
+        sro_trace_rec *x = tr ? trace_new(tr, SRO_TRACE_TRIVIAL, depth, pb, pe, tb, te, cb, ce) : NULL;
+        if (x) x->cig_b = out->n;
+        if (tlen == 0) cig_push(out, 'D', plen); else cig_push(out, 'I', tlen);
+        if (x) x->cig_e = out->n;
+        return 0;
+    }
     view_t w = { p + pb, t + tb, plen, tlen, 0 };
     if (score_remaining <= SRO_BIALIGN_FALLBACK_MIN_SCORE ||
         IMAX(plen, tlen) <= SRO_BIALIGN_FALLBACK_MIN_LENGTH || depth > 60) {
-        int sc = wfa_full(&w, pen, cb, ce, out, cells);
+        sro_trace_rec *x = tr ? trace_new(tr, SRO_TRACE_BASE, depth, pb, pe, tb, te, cb, ce) : NULL;
+        if (x) x->cig_b = out->n;
+        int sc = wfa_full(&w, pen, cb, ce, out, cells, x ? &x->tie : NULL);
+        if (x) x->cig_e = out->n;
         return sc < 0 ? sc : 0;
     }
-    bp_t bp;
-    int st = bialign_find_breakpoint(&w, pen, cb, ce, &bp, cells);
+    sro_trace_rec *x = tr ? trace_new(tr, SRO_TRACE_SEARCH, depth, pb, pe, tb, te, cb, ce) : NULL;
+    bp_t bp, bpt;
+    int st = bialign_find_breakpoint(&w, pen, cb, ce, &bp, cells, x ? &bpt : NULL);
     if (st < 0) return st;
     const int bh = bp.off_f;
     const int bv = bp.off_f - bp.k_f;
     if (bv < 0 || bv > plen || bh < 0 || bh > tlen) return -3;
+    if (x) {
+        x->bv = pb + bv; x->bh = tb + bh; x->comp = bp.comp; x->score_f = bp.score_f; x->score_r = bp.score_r;
+        x->tie = bpt.comp != bp.comp || bpt.k_f != bp.k_f;
+    }
     st = bialign(p, pb, pb + bv, t, tb, tb + bh, pen, cb, bp.comp, bp.score_f,
-                 out, cells, depth + 1);
+                 out, cells, depth + 1, tr);
     if (st < 0) return st;
     st = bialign(p, pb + bv, pe, t, tb + bh, te, pen, bp.comp, ce, bp.score_r,
-                 out, cells, depth + 1);
+                 out, cells, depth + 1, tr);
     return st;
 }
 
@@ -752,13 +852,31 @@ int sro_wfa_align(const uint8_t *pattern, int plen, const uint8_t *text,
         st = 0;
     } else if (memory_mode == SRO_MEM_ULTRALOW) {
         st = bialign(pattern, 0, plen, text, 0, tlen, pen, SRO_M, SRO_M,
-                     INT_MAX, &out, &cells, 0);
+                     INT_MAX, &out, &cells, 0, NULL);
     } else {
         view_t w = { pattern, text, plen, tlen, 0 };
-        st = wfa_full(&w, pen, SRO_M, SRO_M, &out, &cells);
+        st = wfa_full(&w, pen, SRO_M, SRO_M, &out, &cells, NULL);
         if (st >= 0) st = 0;
     }
     g_last_cells = cells;
+    if (st < 0) { free(out.b); return st; }
+    if (score) *score = sro_cigar_score(out.b, out.n, pattern, plen, text, tlen, pen);
+    if (cigar) { *cigar = out.b ? out.b : (uint8_t *)malloc(1); } else free(out.b);
+    if (cigar_len) *cigar_len = out.n;
+    return 0;
+}
+
+int sro_wfa_align_traced(const uint8_t *pattern, int plen, const uint8_t *text,
+                         int tlen, const sro_penalties *pen, uint8_t **cigar,
+                         int *cigar_len, int *score, sro_trace_rec *recs, int cap,
+                         int *nrec) {
+    if (!pen_valid(pen) || plen <= 0 || tlen <= 0 || cap < 0 || !nrec) return -1;
+    cig_t out = {0, 0, 0};
+    uint64_t cells = 0;
+    trace_t tr = { recs, recs ? cap : 0, 0 };
+    int st = bialign(pattern, 0, plen, text, 0, tlen, pen, SRO_M, SRO_M, INT_MAX, &out, &cells, 0, &tr);
+    g_last_cells = cells;
+    *nrec = tr.n;
     if (st < 0) { free(out.b); return st; }
     if (score) *score = sro_cigar_score(out.b, out.n, pattern, plen, text, tlen, pen);
     if (cigar) { *cigar = out.b ? out.b : (uint8_t *)malloc(1); } else free(out.b);

@@ -99,3 +99,13 @@ class OracleOnce:
 @functools.lru_cache(maxsize=None)
 def oracle_once(name, kw=()):
     return OracleOnce(SETS[name](), dict(kw))
+
+
+def resolve(inp, kw):
+    """inp: a name of SETS, or (key, records, function of the sorted parameter tuple -> the oracle's answers) for an input
+    that lives elsewhere (tests/tie_inputs.py) -> (key, record list, OracleOnce under kw)"""
+    kt = tuple(sorted(kw.items()))
+    if isinstance(inp, str):
+        return inp, SETS[inp](), oracle_once(inp, kt)
+    key, recs, oracle = inp
+    return key, list(recs), oracle(kt)

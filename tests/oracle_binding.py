@@ -58,6 +58,13 @@ class Alignment(C.Structure):
                 ("target_start", C.c_uint64), ("target_end", C.c_uint64)]
 
 
+class TraceRec(C.Structure):
+    """sro_trace_rec (oracle/sr_oracle.h)"""
+    _fields_ = [(f, C.c_int32) for f in ("kind", "depth", "pb", "pe", "tb", "te", "cb", "ce", "bv", "bh", "comp", "score_f",
+                                         "score_r", "tie", "cig_b", "cig_e")]
+
+
+TRACE_SEARCH, TRACE_BASE, TRACE_TRIVIAL = 0, 1, 2
 MEM_HIGH, MEM_ULTRALOW = 0, 3
 M, I1, I2, D1, D2 = range(5)
 
@@ -99,6 +106,9 @@ def lib():
     L.sro_parse_sparsification.argtypes = [C.c_char_p, C.POINTER(Sparsification)]
     L.sro_wfa_align.argtypes = [C.c_char_p, i32, C.c_char_p, i32, C.POINTER(Penalties), i32,
                                 C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(i32), C.POINTER(i32)]
+    L.sro_wfa_align_traced.argtypes = [C.c_char_p, i32, C.c_char_p, i32, C.POINTER(Penalties),
+                                       C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(i32), C.POINTER(i32),
+                                       C.POINTER(TraceRec), i32, C.POINTER(i32)]
     L.sro_wfa_score.argtypes = [C.c_char_p, i32, C.c_char_p, i32, C.POINTER(Penalties), i32,
                                 C.POINTER(i32)]
     L.sro_wfa_last_cells.restype = u64
@@ -169,6 +179,24 @@ def wfa_align(pattern: bytes, text: bytes, pen: Penalties, mode=MEM_ULTRALOW):
     out = bytes(cig[: n.value])
     L._libc.free(C.cast(cig, C.c_void_p))
     return out, sc.value
+
+
+def wfa_align_traced(pattern: bytes, text: bytes, pen: Penalties, cap=512):
+    """the ultralow-memory alignment with its trace -> (raw cigar bytes, score, [record dicts in recursion order])"""
+    L = lib()
+    while True:
+        cig = C.POINTER(C.c_uint8)(); n = C.c_int(); sc = C.c_int(); nrec = C.c_int()
+        recs = (TraceRec * cap)()
+        st = L.sro_wfa_align_traced(pattern, len(pattern), text, len(text), C.byref(pen), C.byref(cig), C.byref(n),
+                                    C.byref(sc), recs, cap, C.byref(nrec))
+        if st != 0:
+            raise RuntimeError(f"sro_wfa_align_traced failed: {st}")
+        out = bytes(cig[: n.value])
+        L._libc.free(C.cast(cig, C.c_void_p))
+        if nrec.value <= cap:
+            names = [f for f, _ in TraceRec._fields_]
+            return out, sc.value, [{f: getattr(recs[i], f) for f in names} for i in range(nrec.value)]
+        cap = nrec.value
 
 
 def wfa_score(pattern: bytes, text: bytes, pen: Penalties, max_score=-1):

@@ -44,11 +44,11 @@ def three_ways(mp, name, kw, env, fused=True):
     """the input with the replay (mirroring on), with SR_MIRROR_REPLAY=0 and with SR_NO_MIRROR=1 under the same knobs: all equal
     to the oracle (tm.on_and_off) and to each other, the oracle-counted counters too -> (replay, no_replay, no_mirror)"""
     clear(mp)
-    o = mi.oracle_once(name, tuple(sorted(kw.items())))
-    on, off = tm.on_and_off(mp, mi.SETS[name](), kw, env, o, fused)
+    name, recs, o = mi.resolve(name, kw)                     # a name of mi.SETS, or (key, records, oracle function)
+    on, off = tm.on_and_off(mp, recs, kw, env, o, fused)
     clear(mp)
     tm.set_env(mp, dict(tm.MIRROR_ON, **dict(env, SR_MIRROR_REPLAY="0")))
-    r0 = tm.run_ctx(mi.SETS[name](), kw, fused)
+    r0 = tm.run_ctx(recs, kw, fused)
     clear(mp)
     same_results(on, r0, "replay against SR_MIRROR_REPLAY=0")
     assert r0["rep"]["mirror_replay"] == 0 and r0["rep"]["knobs"].get("SR_MIRROR_REPLAY") == "0"

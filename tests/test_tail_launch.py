@@ -67,11 +67,11 @@ def run_tail(mp, recs, kw, env, fused=True, pairs=None, batches=False):
 def baseline(mp, name, kw, env, fused=True):
     """the input under env with SR_TAIL=0, mirroring on and off: both equal to the oracle (tm.on_and_off asserts it).
     Computed once per (input, parameters, knobs) and shared unchanged"""
+    name, recs, o = mi.resolve(name, kw)                     # a name of mi.SETS, or (key, records, oracle function)
     key = (name, tuple(sorted(kw.items())), tuple(sorted(env.items())), fused)
     if key not in _BASE:
         clear(mp)
-        o = mi.oracle_once(name, tuple(sorted(kw.items())))
-        on, off = tm.on_and_off(mp, mi.SETS[name](), kw, dict(env, SR_TAIL="0"), o, fused)
+        on, off = tm.on_and_off(mp, recs, kw, dict(env, SR_TAIL="0"), o, fused)
         assert on["rep"]["tail_threads"] == 0 and on["rep"]["knobs"].get("SR_TAIL") == "0"
         _BASE[key] = (on, o)
     return _BASE[key]
@@ -90,7 +90,8 @@ def same(r, on):
 
 def tail_case(mp, name, kw, env, tail_env, fused=True):
     on, o = baseline(mp, name, kw, env, fused)
-    r = run_tail(mp, mi.SETS[name](), kw, dict(env, **tail_env), fused)
+    name, recs, _ = mi.resolve(name, kw)
+    r = run_tail(mp, recs, kw, dict(env, **tail_env), fused)
     same(r, on)
     print(name, kw, env, tail_env, "tail_threads", r["rep"]["tail_threads"], "mirror_pairs", r["cnt"]["mirror_pairs"], "mirror_ties",
           r["cnt"]["mirror_ties"], "deferred", r["deferred"])
