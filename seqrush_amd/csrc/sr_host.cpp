@@ -2698,6 +2698,11 @@ extern "C" int sr_ctx_load_paf(sr_ctx *c, const sr_seqset *seqs, const sr_params
         if (my % p->shard_count != p->shard_rank) continue;
         const uint32_t q = iq->second, t = it->second;
         const bool rc = fld[4] == "-";
+        // a patch of --patch-inversions (sr:Z:inv, written by sr_append_paf_tagged) carries forward-strand query coordinates
+        // like any PAF record; the replay takes the start of a '-' record in reverse-complement space, so turn it round
+        // (a whole-sequence record, the only '-' record the reference writes, reads the same both ways)
+        for (size_t i = 12; rc && i < fld.size(); i++)
+            if (fld[i] == "sr:Z:inv" && qe <= c->len[iq->second]) { qb = c->len[iq->second] - qe; break; }
         if (qb > 0xffffffffULL || tb > 0xffffffffULL) { rc_err = fail(SR_ERR_INVALID, "PAF start coordinate out of range"); break; }
         const uint8_t *Q = seqs->bases + seqs->offsets[q], *T = seqs->bases + seqs->offsets[t];
         const uint64_t len1 = c->len[q], len2 = c->len[t];

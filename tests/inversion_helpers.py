@@ -81,8 +81,13 @@ def _snps(s: bytes, start: int, length: int, every: int) -> bytes:
     return bytes(b)
 
 
+EXTRA = {}     # name -> generator of [(name, bytes)]: inputs that live in another module (mode_tie_inputs.py)
+
+
 @functools.lru_cache(maxsize=None)
 def inputs(name):
+    if name in EXTRA:
+        return tuple(EXTRA[name]())
     # (seed and length chosen so that the main alignment shows the inversion as ONE two-sided gap: on most inputs the few
     # bases that match by chance at the centre of an inverted segment split it into two one-sided gaps, which the rule skips)
     a = synth.to_bytes(synth.base_sequence(500, 7110))

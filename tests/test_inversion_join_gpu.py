@@ -50,6 +50,8 @@ def finish(ctx, patch=True, keep=False, via_align_all=False):
     ctx.sync()
     out = dict(labels=ctx.download_labels(), batches=ctx.num_batches, kernel=ctx.align_kernel,
                symbol_bits=ctx.workspace_report()["symbol_bits"])
+    # what the mirrored main pass did (test_modes_mirrored_gpu.py)
+    out.update(rep=ctx.workspace_report(), cnt=ctx.counters(), deferred=ctx.tail_deferred(), pairs=ctx.pairs())
     out["gfa"], out["nodes"], _ = ctx.build_gfa(compact=False)
     if patch:
         out["stats"] = ctx.inversion_stats()

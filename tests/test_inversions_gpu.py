@@ -40,6 +40,8 @@ def run_product(name, scores="0,5,8,2,24,1", k=ih.K, d=None, min_size=0, patch=T
     ctx.sync()
     out = dict(labels=ctx.download_labels(), pairs=ctx.pairs(), batches=ctx.num_batches, kernel=ctx.align_kernel,
                symbol_bits=ctx.workspace_report()["symbol_bits"])
+    # what the mirrored main pass did (test_modes_mirrored_gpu.py)
+    out.update(rep=ctx.workspace_report(), cnt=ctx.counters(), deferred=ctx.tail_deferred())
     out["gfa"], out["nodes"], _ = ctx.build_gfa(compact=False)
     out["gfa_compact"] = ctx.build_gfa(compact=True)[0]
     if patch:
