@@ -702,6 +702,56 @@ int sr_growth_fit(const double *pan_exp, uint32_t groups, double *alpha, double 
  * permutations run, from sums kept in 128-bit integers. */
 int sr_growth_report(const sr_growth *g, char **text);
 
+/* -------- variant sites (`--vcf FILE`) -------------------------------------------------------------
+ * Where the paths of a graph differ from one of them, the reference R (`vg deconstruct`), of any GFA with S / L / P lines and
+ * numeric node ids as the parser of sr_sort_gfa reads it.  refseq = the oriented sequence of R (a reverse handle reads its
+ * node reversed and complemented by the project's rule).  A node R visits exactly once is an anchor, with its interval
+ * [ref_pos, ref_end) of refseq and its orientation on R; a step of any path on an anchor is an anchor step, of strand
+ * orientation xor ref_or.  Two anchor steps i < j of a path with none between them are colinear iff the strands are equal
+ * and the intervals follow each other on that strand; then [a, b) is the reference between them and the allele is what the
+ * path has between them, read on the reference's strand.  A pair that is not colinear is a break (breaks[path]); a
+ * colinear pair with a == b and an empty allele yields nothing; one with b - a or the allele above max_allele_len (0: no
+ * limit) is counted in skipped[path]; every other is a traversal.  Traversals with the same (a, b) form a site: allele 0 is
+ * refseq[a:b], the other distinct alleles are numbered from 1 by (length, bytes); a site without one is not reported.
+ * gt[site * paths + path] = the allele of the path's first traversal of the site, else 0 if a run of reference-adjacent
+ * anchor steps of the path covers [a - 1, b + 1), else -1.  The column of R is included.
+ * device >= 0: HIP kernels on that device (sr_variants.hip); SR_VARIANTS_DEVICE_HOST: plain loops on the host that compare
+ * allele bytes directly.  Both give the same integers and bytes; the device groups alleles by a 64-bit hash ANDed with
+ * hash_mask and then compares bytes, and no result depends on hashes not colliding (hash_collision_sites counts the
+ * reported sites where they did; always 0 on the host).  Limits of the graph as for the statistics, a reference of < 2^31
+ * bases; sites x paths above 2^26: SR_ERR_UNSUPPORTED.  An unknown ref_name or a node without a sequence: SR_ERR_INVALID.  An empty graph, one without
+ * a path or a reference without steps gives no site and no error. */
+#define SR_VARIANTS_DEVICE_HOST (-1)
+typedef struct {
+    const char *ref_name;       /* the reference path; NULL (default): the first path */
+    uint64_t max_allele_len;    /* default 10000; 0: no limit */
+    uint64_t hash_mask;         /* default all ones; fewer bits force collisions (tests) */
+    uint64_t reserved;          /* 0 */
+} sr_variant_params;
+void sr_variant_params_default(sr_variant_params *p);
+typedef struct {
+    uint64_t ref_path, ref_len, paths, anchors, traversals, sites, hash_collision_sites;
+    uint64_t *breaks, *skipped;                         /* [paths] */
+    uint64_t *site_start, *site_end;                    /* [sites] a and b, ascending by (a, b) */
+    uint32_t *site_alleles;                             /* [sites] ALT alleles of the site (>= 1) */
+    uint64_t *allele_off;                               /* [sum of site_alleles + 1] into alleles: the ALT alleles of site 0 in order, then site 1 ... */
+    char *alleles;
+    int32_t *gt;                                        /* [sites * paths] */
+    char *ref_seq;                                      /* [ref_len] refseq */
+    int32_t variant, reserved;                          /* variant: 0 the host loops, 1 the device kernels */
+    uint64_t variants_us, kernel_us[6];                 /* the stage; anchors, scan, emit, hash, sort and classes, genotypes */
+} sr_variants;
+int sr_variants_gfa(const char *gfa_in, const sr_variant_params *p, int device, sr_variants **out);
+void sr_variants_free(sr_variants *v);
+/* The VCF text, the only place its bytes are formed; names = the names of the paths in file order; *text is malloc'ed
+ * (sr_free).  VCFv4.2: fileformat, source, contig (ID = the name of R, its length; left out without a path), one
+ * ##seqrush_amd=<anchors,traversals,sites,breaks,skipped> line (breaks and skipped summed over the paths), INFO AC and AN,
+ * FORMAT GT, and every path except R in file order as a haploid sample.  One record per site: POS = a + 1 and REF =
+ * refseq[a:b] if b > a and no ALT allele is empty, else padded with the base before the site (POS = a, REF =
+ * refseq[a-1:b], every ALT with refseq[a-1] in front).  ID, QUAL, FILTER are `.`; AC counts the samples per ALT allele, AN
+ * those whose GT is not `.`. */
+int sr_variants_vcf(const sr_variants *v, const char *const *names, char **text);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

@@ -66,6 +66,11 @@ def main(argv=None):
     ap.add_argument("--growth-seed", type=int, default=None, metavar="N", help="seed of the sampled orders (default 9399220)")
     ap.add_argument("--growth-group-by", choices=("path", "sample", "haplotype"), default=None,
                     help="path: every path a genome; sample / haplotype: paths grouped by their PanSN prefix")
+    ap.add_argument("--vcf", default=None, metavar="FILE",
+                    help="write the variant sites of the final GFA against one of its paths (`vg deconstruct`) to FILE as VCF")
+    ap.add_argument("--vcf-ref", default=None, metavar="NAME", help="the reference path (default: the first path)")
+    ap.add_argument("--vcf-max-allele-len", type=int, default=None, metavar="N",
+                    help="traversals with a longer allele or reference span are skipped (default 10000; 0: no limit)")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -102,6 +107,16 @@ def main(argv=None):
         low = 0 if flag == "--growth-seed" else 1
         if flag != "--growth-group-by" and not low <= v <= 2 ** 64 - 1:
             print(f"Error: {flag} needs a {'non-negative' if low == 0 else 'positive'} integer, got '{v}'", file=sys.stderr)
+            return 1
+    for flag in ("--vcf-ref", "--vcf-max-allele-len"):
+        v = getattr(ns, flag.lstrip("-").replace("-", "_"))
+        if v is None:
+            continue
+        if ns.vcf is None:
+            print(f"Error: {flag} is an option of --vcf: give both", file=sys.stderr)
+            return 1
+        if flag == "--vcf-max-allele-len" and not 0 <= v <= 2 ** 64 - 1:
+            print(f"Error: {flag} needs a non-negative integer, got '{v}'", file=sys.stderr)
             return 1
     if ns.bin_width is not None and ns.bin_count is not None:
         print("Error: --bin-width and --bin-count exclude each other", file=sys.stderr)
@@ -144,7 +159,8 @@ def main(argv=None):
                 viz_path_height=ns.viz_path_height or 10, viz_path_gap=1 if ns.viz_path_gap is None else ns.viz_path_gap,
                 viz_mode=ns.viz_mode or "path", viz_depth_max=ns.viz_depth_max or 4, growth=ns.growth,
                 growth_permutations=ns.growth_permutations or 1000,
-                growth_seed=9399220 if ns.growth_seed is None else ns.growth_seed, growth_group_by=ns.growth_group_by or "path")
+                growth_seed=9399220 if ns.growth_seed is None else ns.growth_seed, growth_group_by=ns.growth_group_by or "path", vcf=ns.vcf, vcf_ref=ns.vcf_ref,
+                vcf_max_allele_len=10000 if ns.vcf_max_allele_len is None else ns.vcf_max_allele_len)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

@@ -44,6 +44,7 @@ EXPORTS = [
     "sr_path_bins_gfa", "sr_path_bins_free", "sr_path_bins_tsv", "sr_viz_params_default", "sr_path_bins_rgb", "sr_path_bins_png",
     "sr_growth_params_default", "sr_growth_gfa", "sr_growth_free", "sr_growth_groups", "sr_growth_expected", "sr_growth_fit",
     "sr_growth_report",
+    "sr_variant_params_default", "sr_variants_gfa", "sr_variants_free", "sr_variants_vcf",
     "sr_ctx_tail_deferred", "sr_ctx_tail_timeline", "sr_tail_shape",
     "sr_replay_record_ints", "sr_replay_transpose_host", "sr_replay_match_host",
 ]
@@ -168,6 +169,22 @@ class GrowthC(C.Structure):
                 ("pan", C.POINTER(C.c_uint64)), ("core", C.POINTER(C.c_uint64)), ("perm", C.POINTER(C.c_uint32)),
                 ("bp_by_groups", C.POINTER(C.c_uint64)), ("growth_us", C.c_uint64), ("kernel_us", C.c_uint64 * 4),
                 ("seed", C.c_uint64)]
+
+
+class VariantParamsC(C.Structure):
+    """sr_variant_params (include/seqrush_amd.h, variant sites)"""
+    _fields_ = [("ref_name", C.c_char_p), ("max_allele_len", C.c_uint64), ("hash_mask", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class VariantsC(C.Structure):
+    """sr_variants"""
+    _fields_ = [("ref_path", C.c_uint64), ("ref_len", C.c_uint64), ("paths", C.c_uint64), ("anchors", C.c_uint64),
+                ("traversals", C.c_uint64), ("sites", C.c_uint64), ("hash_collision_sites", C.c_uint64),
+                ("breaks", C.POINTER(C.c_uint64)), ("skipped", C.POINTER(C.c_uint64)),
+                ("site_start", C.POINTER(C.c_uint64)), ("site_end", C.POINTER(C.c_uint64)), ("site_alleles", C.POINTER(C.c_uint32)),
+                ("allele_off", C.POINTER(C.c_uint64)), ("alleles", C.POINTER(C.c_char)), ("gt", C.POINTER(C.c_int32)),
+                ("ref_seq", C.POINTER(C.c_char)), ("variant", C.c_int32), ("reserved", C.c_int32),
+                ("variants_us", C.c_uint64), ("kernel_us", C.c_uint64 * 6)]
 
 
 class AlignmentsC(C.Structure):
@@ -328,6 +345,11 @@ def load():
     L.sr_growth_expected.argtypes = [C.POINTER(u64), C.c_uint32, PD, PD]
     L.sr_growth_fit.argtypes = [PD, C.c_uint32, PD, PD, PU32]
     L.sr_growth_report.argtypes = [PG, C.POINTER(vp)]
+    PV = C.POINTER(VariantsC)
+    L.sr_variant_params_default.argtypes = [C.POINTER(VariantParamsC)]; L.sr_variant_params_default.restype = None
+    L.sr_variants_gfa.argtypes = [C.c_char_p, C.POINTER(VariantParamsC), i32, C.POINTER(PV)]
+    L.sr_variants_free.argtypes = [PV]; L.sr_variants_free.restype = None
+    L.sr_variants_vcf.argtypes = [PV, C.POINTER(C.c_char_p), C.POINTER(vp)]
     PI = C.POINTER(C.c_int)
     L.sr_mirror_map.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                 C.POINTER(C.c_uint32), C.POINTER(u64)]

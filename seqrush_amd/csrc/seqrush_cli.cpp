@@ -83,12 +83,15 @@ static void usage() {
                     "       [--bin bins.tsv [--bin-width W | --bin-count N]] [--viz graph.png [--viz-width N] [--viz-path-height H]\n"
                     "       [--viz-path-gap G] [--viz-mode path|strand|depth] [--viz-depth-max D]]\n"
                     "       [--growth growth.tsv [--growth-permutations N] [--growth-seed N] [--growth-group-by path|sample|haplotype]]\n"
+                    "       [--vcf graph.vcf [--vcf-ref NAME] [--vcf-max-allele-len N]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave", stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt;
+                aligner = "allwave", stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt, vcf_out, vcf_opt, vcf_ref;
+    sr_variant_params vcp;
+    sr_variant_params_default(&vcp);
     sr_growth_params gp;
     sr_growth_params_default(&gp);
     int growth_mode = 0;
@@ -198,6 +201,16 @@ int main(int argc, char **argv) {
             if (m != "path" && m != "sample" && m != "haplotype") { fprintf(stderr, "Error: --growth-group-by takes path, sample or haplotype\n"); return 1; }
             growth_mode = m == "path" ? 0 : m == "sample" ? 1 : 2;
         }
+        else if (a == "--vcf") vcf_out = val("--vcf");
+        else if (a == "--vcf-ref") { vcf_ref = val("--vcf-ref"); vcf_opt = a; }
+        else if (a == "--vcf-max-allele-len") {
+            const char *v = val("--vcf-max-allele-len");
+            char *end = nullptr;
+            const unsigned long long n = strtoull(v, &end, 10);
+            vcf_opt = a;
+            if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: %s needs a non-negative integer, got '%s'\n", a.c_str(), v); return 1; }
+            vcp.max_allele_len = n;
+        }
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
             const char *v = val("--inversion-min-size");
@@ -252,6 +265,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (!growth_opt.empty() && growth_out.empty()) { fprintf(stderr, "Error: %s is an option of --growth: give both\n", growth_opt.c_str()); return 1; }
+    if (!vcf_opt.empty() && vcf_out.empty()) { fprintf(stderr, "Error: %s is an option of --vcf: give both\n", vcf_opt.c_str()); return 1; }
     if (bin_width && bin_count) { fprintf(stderr, "Error: --bin-width and --bin-count exclude each other\n"); return 1; }
     if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
     if (compact_dev && no_compact) { fprintf(stderr, "Error: --compact-on device and --no-compact exclude each other\n"); return 1; }
@@ -412,7 +426,7 @@ int main(int argc, char **argv) {
     o << gfa;
     std::vector<std::string> pnames;                         // names of the P lines, as the library's parser reads them
     std::vector<const char *> pn;
-    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty() || !growth_out.empty()) {
+    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty() || !growth_out.empty() || !vcf_out.empty()) {
         for (const char *q = gfa; *q;) {
             const char *eol = strchr(q, '\n');
             if (!eol) eol = q + strlen(q);
@@ -503,6 +517,19 @@ int main(int argc, char **argv) {
         printf("Growth written to %s\n", growth_out.c_str());
         if (verbose) printf("Growth stage: %llu us on device %d\n", (unsigned long long)gr->growth_us, device);
         sr_growth_free(gr);
+    }
+    if (!vcf_out.empty()) {                                  // the variant sites of the text just written
+        sr_variants *va = nullptr;
+        char *vcf = nullptr;
+        if (!vcf_ref.empty()) vcp.ref_name = vcf_ref.c_str();
+        if (sr_variants_gfa(gfa, &vcp, device, &va)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_free(gfa); return 1; }
+        if (sr_variants_vcf(va, pn.data(), &vcf)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_variants_free(va); sr_free(gfa); return 1; }
+        std::ofstream vo(vcf_out, std::ios::binary);
+        vo << vcf;
+        sr_free(vcf);
+        printf("VCF written to %s\n", vcf_out.c_str());
+        if (verbose) printf("Variants stage: %llu us on device %d\n", (unsigned long long)va->variants_us, device);
+        sr_variants_free(va);
     }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());

@@ -50,5 +50,9 @@ int sr_graph_bins_run(const SrGraph &g, const sr_bin_params &prm, int device, vo
 // returns it
 int sr_graph_growth_run(const SrGraph &g, const uint32_t *group_of, uint32_t n_groups, const sr_growth_params &prm, int device, void *stream,
                         sr_growth **out);
+// the variant sites of a parsed graph against one of its paths (sr_variants.hip), with the same meaning of device and
+// stream; names = the path names the parser returned (the reference is chosen by name); *out as sr_variants_gfa returns it
+int sr_graph_variants_run(const SrGraph &g, const std::vector<std::string> &names, const sr_variant_params &prm, int device, void *stream,
+                          sr_variants **out);
 int sr_fail(int code, const std::string &msg);     // sr_host.cpp: sets sr_last_error()
 void sr_sort_note_write_ms(double ms);              // slot [3] of sr_sort_stats(), also added to the stage's wall time [9]

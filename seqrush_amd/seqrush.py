@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, check, SeqRushError)
+                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, check, SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -70,6 +70,9 @@ class Args:
     growth_permutations: int = 1000         # added: --growth-permutations N
     growth_seed: int = 9399220              # added: --growth-seed N
     growth_group_by: str = "path"           # added: --growth-group-by path | sample | haplotype
+    vcf: Optional[str] = None               # added: --vcf FILE: variant sites of the final GFA against one path as VCF
+    vcf_ref: Optional[str] = None           # added: --vcf-ref NAME: the reference path (default: the first)
+    vcf_max_allele_len: int = 10000         # added: --vcf-max-allele-len N (0: no limit)
 
 
 @dataclasses.dataclass
@@ -960,6 +963,93 @@ def write_growth(text: str, args: "Args"):
         print(f"Growth stage: {us} us on device {args.device}")
 
 
+SR_VARIANTS_DEVICE_HOST = -1
+VARIANTS_KERNELS = ("anchors", "scan", "emit", "hash", "sort_classes", "genotypes")
+
+
+class Variants:
+    """an owned sr_variants: the variant sites of a GFA text against one of its paths"""
+
+    def __init__(self, text: str, device: int = 0, ref: Optional[str] = None, max_allele_len: int = 10000,
+                 hash_mask: int = 2 ** 64 - 1):
+        for k, v in (("max_allele_len", max_allele_len), ("hash_mask", hash_mask)):
+            if not 0 <= int(v) < 2 ** 64:
+                raise SeqRushError(-1, f"{k} must be in 0 .. 2^64 - 1")
+        self.L = _lib.load()
+        self.p = C.POINTER(VariantsC)()
+        self.names = _path_names(text)
+        prm = VariantParamsC(None if ref is None else ref.encode(), int(max_allele_len), int(hash_mask), 0)
+        check(self.L.sr_variants_gfa(text.encode(), C.byref(prm), int(device), C.byref(self.p)))
+
+    def close(self):
+        if self.p:
+            self.L.sr_variants_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def as_dict(self) -> dict:
+        s = self.p.contents
+        P, NS = int(s.paths), int(s.sites)
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].astype(dt, copy=True)
+        d = {k: int(getattr(s, k)) for k in ("ref_path", "ref_len", "paths", "anchors", "traversals", "sites", "hash_collision_sites",
+                                             "variant", "variants_us")}
+        d["breaks"], d["skipped"] = arr(s.breaks, P, np.uint64), arr(s.skipped, P, np.uint64)
+        d["site_start"], d["site_end"] = arr(s.site_start, NS, np.uint64), arr(s.site_end, NS, np.uint64)
+        d["site_alleles"] = arr(s.site_alleles, NS, np.uint32)
+        n_alt = int(d["site_alleles"].sum())
+        off = arr(s.allele_off, n_alt + 1, np.uint64)
+        arena = C.string_at(s.alleles, int(off[-1]))
+        flat = [arena[int(off[k]):int(off[k + 1])] for k in range(n_alt)]
+        d["alleles"], k = [], 0
+        for n in d["site_alleles"]:
+            d["alleles"].append(flat[k:k + int(n)])
+            k += int(n)
+        d["gt"] = arr(s.gt, NS * P, np.int32).reshape(NS, P)
+        d["ref_seq"] = C.string_at(s.ref_seq, int(s.ref_len))
+        d["kernel_us"] = dict(zip(VARIANTS_KERNELS, (int(v) for v in s.kernel_us)))
+        return d
+
+    def vcf(self) -> str:
+        arr = (C.c_char_p * max(1, len(self.names)))(*[n.encode() for n in self.names])
+        out = C.c_void_p()
+        check(self.L.sr_variants_vcf(self.p, C.cast(arr, C.POINTER(C.c_char_p)), C.byref(out)))
+        return _take_text(out)
+
+
+def variants(text: str, device: int = 0, ref: Optional[str] = None, max_allele_len: int = 10000, hash_mask: int = 2 ** 64 - 1) -> dict:
+    """variant sites of any GFA with S / L / P lines and numeric node ids against its path `ref` (default: the first;
+    DESIGN.md section 15).  device >= 0: HIP kernels on that device, -1: the host twin (the same integers and bytes).  ->
+    dict: ref_path, ref_len, ref_seq, paths, anchors, traversals, sites, hash_collision_sites; breaks / skipped (uint64
+    [paths]); site_start / site_end (uint64 [sites]), site_alleles, alleles (per site the list of its ALT alleles, bytes);
+    gt (int32 [sites, paths], -1 = no call); variants_us, kernel_us"""
+    with Variants(text, device, ref, max_allele_len, hash_mask) as v:
+        return v.as_dict()
+
+
+def variants_vcf(text: str, device: int = 0, ref: Optional[str] = None, max_allele_len: int = 10000, hash_mask: int = 2 ** 64 - 1) -> str:
+    """the VCF text of variants(), formatted by the library"""
+    with Variants(text, device, ref, max_allele_len, hash_mask) as v:
+        return v.vcf()
+
+
+def write_vcf(text: str, args: "Args"):
+    """the --vcf stage of both Python front ends on the final GFA text"""
+    with Variants(text, args.device, args.vcf_ref, args.vcf_max_allele_len) as v:
+        with open(args.vcf, "w") as fh:
+            fh.write(v.vcf())
+        us = int(v.p.contents.variants_us)
+    print(f"VCF written to {args.vcf}")
+    if args.verbose:
+        print(f"Variants stage: {us} us on device {args.device}")
+
+
 LAYOUT_STATS =("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
 
 
@@ -1307,6 +1397,8 @@ class SeqRush:
             write_bins(text, args)
         if args.growth:
             write_growth(text, args)
+        if args.vcf:
+            write_vcf(text, args)
 
 
 def run_seqrush(args: Args):
