@@ -252,7 +252,8 @@ int sr_ctx_counters_ext(sr_ctx *c, uint64_t out[32]);
  * (LDS-resident histories of small base cases), [37] base cases searched again with the worst-case history region,
  * [40..43] first offending access of the bounds-checked build (pair, level, row offset, extent), [48..51] replay of tied
  * secondaries (52 slots): tied primaries with a tie-sensitive depth-0 search, ties in base cases only, secondaries replayed,
- * searches they took from records; rest reserved.
+ * searches they took from records; [52..53] rotating tile priority (54 slots): workgroups of the main launches that took a
+ * rank on their CU, the largest arrival count of a CU; rest reserved.
  * Returns the number of slots written (<= cap) or a negative sr_status. */
 int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap);
 /* "NAME<TAB>meaning when unset<TAB>what it does" lines of every environment variable the load path reads; the ones that
@@ -267,6 +268,15 @@ int sr_ctx_tail_deferred(sr_ctx *c, uint64_t *out);
  * the last one was a secondary taken over from its own primary).  Returns the workgroups written (<= cap_wg), 0 when the load
  * does not run the instrumented instance, or a negative sr_status. */
 int sr_ctx_tail_timeline(sr_ctx *c, uint64_t *out, uint32_t cap_wg);
+/* Rotating tile priority of the blocked alignment kernel.  sr_ctx_prio_timeline: the instrumented instance's
+ * second record of the same launch, 4 words per workgroup: tick of the end of its first alignment, its rank among the
+ * workgroups of its CU, the CU's index in the arrival table, its arrival count there; returns as sr_ctx_tail_timeline.
+ * sr_tile_prio_role_host: the rule the kernel runs (s_setprio level 0..3 of a workgroup's tile code from its rank, the epoch =
+ * 100 MHz real-time counter >> sr_tile_prio_epoch_shift(), and the workgroups per CU; 1 per CU: always 0).  Pure (host only).
+ * The workspace report carries "tile_prio" (0 under SR_TILE_PRIO=0 or with one workgroup per CU) and "prio_epoch_shift". */
+int sr_ctx_prio_timeline(sr_ctx *c, uint64_t *out, uint32_t cap_wg);
+int sr_tile_prio_role_host(uint32_t rank, uint32_t epoch, uint32_t wg_per_cu);
+int sr_tile_prio_epoch_shift(void);
 /* The tail launch's threads per workgroup for a plan: the widest instance of the blocked kernel wider than main_threads whose
  * LDS (static tables + four copies of max_words words) fits the 128 KB window, 0 = none.  forced > 0 (SR_TAIL_THREADS): the
  * widest instance <= forced instead.  Pure (host only). */

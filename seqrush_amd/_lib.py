@@ -47,6 +47,7 @@ EXPORTS = [
     "sr_variant_params_default", "sr_variants_gfa", "sr_variants_free", "sr_variants_vcf",
     "sr_ctx_tail_deferred", "sr_ctx_tail_timeline", "sr_tail_shape",
     "sr_replay_record_ints", "sr_replay_transpose_host", "sr_replay_match_host",
+    "sr_ctx_prio_timeline", "sr_tile_prio_role_host", "sr_tile_prio_epoch_shift",
 ]
 
 
@@ -255,6 +256,9 @@ def load():
     L.sr_knobs_doc.restype = C.c_char_p
     L.sr_ctx_tail_deferred.argtypes = [vp, C.POINTER(u64)]
     L.sr_ctx_tail_timeline.argtypes = [vp, C.POINTER(u64), C.c_uint32]
+    L.sr_ctx_prio_timeline.argtypes = [vp, C.POINTER(u64), C.c_uint32]
+    L.sr_tile_prio_role_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.sr_tile_prio_epoch_shift.argtypes = []
     L.sr_tail_shape.argtypes = [i32] * 8 + [C.c_uint32, i32]
     L.sr_ctx_load_pairs.argtypes = [vp, PS, PP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64]
     L.sr_ctx_pairs.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]

@@ -66,8 +66,9 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
     unsigned long long tq_pass = 0, tq_bar = 0, tq_ctl = 0, tq_ph2 = 0, tq_tail = 0, tq_rec = 0;
     unsigned row_ld = 0, row_st = 0;                     // per pair, in lane accesses (flushed to the wave's sums in LDS per pair)
     // PROF, thread 0: the workgroup's timeline (a.timeline, 4 words per workgroup): first dequeue, start of the last alignment,
-    // alignments run, whether the last one came from mir_next
-    unsigned long long tl_first = 0, tl_last = 0, tl_n = 0, tl_mir = 0;
+    // alignments run, whether the last one came from mir_next; and (a.prio_timeline, 4 more words) the end of its first alignment, its
+    // rank on the CU, the CU's table index and its arrival count there
+    unsigned long long tl_first = 0, tl_last = 0, tl_n = 0, tl_mir = 0, tl_end1 = 0;
     const int depth = a.kdepth;
     // ring: chunk-major rows (see KRows); rows = 5 components x depth levels + NULL row + U row
     const int depth2 = a.kdepth2;
@@ -103,6 +104,24 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             b_sh.geom.brow = a.brow; b_sh.geom.ring_scope = a.ring_scope; b_sh.geom.ring_hot = a.ring_hot;
             b_sh.geom.bbase_jobs = a.bbase_jobs; b_sh.geom.hist_w = a.hist_w; b_sh.geom.hist_levels = a.hist_levels;
             b_sh.geom.urow = urow;
+            // rank among the workgroups of this CU (sr_prio_rule.h): arrival count of the CU the hardware ids name.  Reads only:
+            // HW_REG_XCC_ID (20) bits [3:0]; HW_REG_HW_ID (4) bits [15:8] = CU_ID, SH_ID, SE_ID
+            unsigned p_rank = 0, p_idx = 0, p_arr = 0;
+            if (a.cu_arrivals) {
+                const unsigned xcc = (unsigned)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
+                const unsigned cu = (unsigned)__builtin_amdgcn_s_getreg(4 | (8 << 6) | (7 << 11));
+                p_idx = sr_prio_table_index(xcc, cu);
+                p_arr = atomicAdd(&a.cu_arrivals[p_idx], 1u);
+                p_rank = p_arr % (unsigned)max(a.prio_wg, 1);
+                atomicAdd(&a.counters[52], 1ull);
+                atomicMax(&a.counters[53], (unsigned long long)p_arr + 1ull);
+            }
+            k_sh.prio_rank = (int)p_rank; k_sh.prio_role = 0;
+            k_sh.prio_wg = (a.tile_prio && a.cu_arrivals && a.prio_wg > 1) ? a.prio_wg : 0;
+            if (PROF && a.prio_timeline) {
+                unsigned long long *tp = a.prio_timeline + 4ull * blockIdx.x;
+                tp[0] = 0ull; tp[1] = p_rank; tp[2] = p_idx; tp[3] = p_arr;
+            }
         }
         __syncthreads();
     }
@@ -140,6 +159,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             if (PROF) {
                 const unsigned long long now = KTICK();
                 if (tl_n == 0) tl_first = now;
+                if (tl_n == 1 && tl_end1 == 0) tl_end1 = now;      // the first alignment ended (its own emitted secondary included)
                 if (pr < (int)a.npairs) { tl_last = now; tl_n++; tl_mir = from_mir ? 1ull : 0ull; }
             }
             // replay (sr_mirror_rule.h): a secondary that follows its primary on this workgroup takes breakpoints from the primary's
@@ -807,6 +827,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
             unsigned long long *tl = a.timeline + 4ull * blockIdx.x;
             tl[0] = tl_first; tl[1] = tl_last; tl[2] = KTICK(); tl[3] = tl_n | (tl_mir << 32);
         }
+        if (PROF && a.prio_timeline) a.prio_timeline[4ull * blockIdx.x] = tl_end1;
         if (PROF) {
             if (!a.pre_oriented) atomicAdd(&a.counters[6], t_ori);    // ([6] holds sr_orient_kernel's cells otherwise)
             atomicAdd(&a.counters[7], t_bp);

@@ -1,6 +1,7 @@
 // sr_blk_pass.inc -- blocked kernel (sr_align_blk.inc), part 3: a pass over a block of levels -- reach and tile windows
 // (kreach, kwindow), the pass tables (blk_setup), the tile queue (blk_pass), the I/D recompute pass (blk_recompute).
 #include "sr_base_cone.h"       // backward cone of a base case (shared with the host twin)
+#include "sr_prio_rule.h"       // rotating tile priority of co-resident workgroups (shared with the host twin)
 // reach() with compile-time gap-extends (the host guarantees pen.e1 == E1, pen.e2 == E2): no runtime division
 template <bool TWO, int E1, int E2>
 __device__ __forceinline__ int kreach(const SrPen &p, int s, int begin) {
@@ -39,8 +40,29 @@ __device__ __forceinline__ void kwindow(const SrPen &pen, const BJob &b, int s0,
 // Sections that one wave (or one lane) runs while the workgroup's other waves wait at the barrier are the pair's critical
 // path, and the SIMD they run on is shared with three waves of other workgroups that are usually in their tiles: raised
 // issue priority (s_setprio) lets the lone wave through first; back to 0 before the barrier.
+// The tile code does not run at 0 but at the workgroup's role of the pass (sr_prio_rule.h): the waves of the workgroups of a
+// CU share the SIMDs one each, issue is arbitrated by priority, then by age, and the workgroups are persistent -- at equal
+// priority the workgroup dispatched last would be served last for the whole launch.  s_setprio takes an immediate and
+// ignores EXEC: a switch over a wave-uniform value (scalar branches), never a lane condition.
+__device__ __forceinline__ void kprio_role() {
+    switch (RFL(k_sh.prio_role)) {
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    case 3: __builtin_amdgcn_s_setprio(3); break;
+    default: __builtin_amdgcn_s_setprio(0); break;
+    }
+}
+// wave 0, once per pass (blk_setup): the role of the next pass from the workgroup's rank and the real-time counter.  The
+// counter is the same on every CU, so co-resident workgroups change roles together.  Rule off: no clock read, role stays 0.
+__device__ __forceinline__ void kprio_epoch() {
+    const int wg = RFL(k_sh.prio_wg);
+    if (wg > 1) {
+        const unsigned epoch = (unsigned)(__builtin_amdgcn_s_memrealtime() >> SR_PRIO_EPOCH_SHIFT);
+        if (threadIdx.x == 0) k_sh.prio_role = sr_tile_prio_role((unsigned)k_sh.prio_rank, epoch, (unsigned)wg);
+    }
+}
 #define KPRIO_HI() __builtin_amdgcn_s_setprio(3)
-#define KPRIO_LO() __builtin_amdgcn_s_setprio(0)
+#define KPRIO_LO() kprio_role()
 // Tables of one pass (levels s0 .. s0+B-1 of every active aligner): wave 0, one lane per aligner.  The first pass of a batch
 // of searches runs it inside blk_pass; later passes get their tables from the wave-0 section that ends the previous pass
 // (control, or the section after breakpoint detection), so a pass costs one barrier and one serial hop less.
@@ -109,6 +131,7 @@ __device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs) {
     if (tid == 0) k_sh.jtstart[0] = 0;
     if (tid == 63) { k_sh.nband = hincl; k_sh.total_tiles = incl + hincl; k_sh.next_tile = NT / 64; if (BASE) k_sh.base_tiles += (unsigned long long)incl; }
     k_sh.cells_l[tid] += (unsigned long long)cells;      // (tid < 64)
+    kprio_epoch();
 }
 
 template <typename OT, bool TWO, int NT, int B, int E1, int E2, bool PROF, int X = 0, int OE1 = 0, typename ST = OT, bool RING = false, bool BASE = false>
@@ -121,6 +144,7 @@ __device__ __forceinline__ void blk_pass(const KRows<OT, ST> &R, int s0, const S
         __syncthreads();
         if (PROF && threadIdx.x == 0) k_sh.t_setup += KTICK() - tsu0;
     }
+    kprio_role();                                        // every wave: the pass's tiles at the workgroup's role
     const int total = RFL(k_sh.total_tiles);
     const int slot0 = kslots(R, s0);
     // Tiles differ in cost (extension loops, edge tiles): every wave takes its first tile by index and the following

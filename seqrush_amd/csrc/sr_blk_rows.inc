@@ -19,6 +19,9 @@ struct KShared {
     int jgplo[BJ_MAX + 2], jgphi[BJ_MAX + 2];                  // groups the previous block of the aligner covered (U row validity)
     int total_tiles;
     int next_tile;                                     // tile queue of a pass: the next tile nobody has taken yet
+    // rotating tile priority (sr_prio_rule.h): the s_setprio level of the pass's tile code (blk_setup writes it, 0 when the
+    // rule is off), the workgroup's rank on its CU, the workgroups per CU the rule runs with (0: off, nothing reads the clock)
+    int prio_role, prio_rank, prio_wg;
     // batched breakpoint detection (phase 2) of one pass: up to K_P2 segments, <= 2*KB_MAX overlap calls each
     int p2n, p2seg[K_P2];
     unsigned p2mask_lo, p2mask_hi;

@@ -26,6 +26,7 @@
 #include "sr_inv_rule.h"
 #include "sr_base_cone.h"
 #include "sr_mirror_rule.h"
+#include "sr_prio_rule.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -59,6 +60,7 @@ static const SrKnob SR_KNOBS[] = {
     {"SR_PROFILE_TICKS", "0", "1 = launch the instrumented instance (100 MHz tick counters, per-workgroup timeline)"},
     {"SR_TAIL", "on", "0 = no tail launch: a tied secondary is always aligned by its primary's workgroup (A/B runs); all = every such secondary is deferred to the tail launch (tests)"},
     {"SR_TAIL_THREADS", "widest instance wider than the main launch", "threads per workgroup of the tail launch among the existing instances: 256 | 512 | 1024 (tests)"},
+    {"SR_TILE_PRIO", "1", "0 = no rotating tile priority among the workgroups of a CU: all tile code at priority 0, no clock read (A/B runs, tests)"},
     {"SR_TAIL_ROUNDS", "8", "a batch defers only when its alignments are at most this many times the launch's workgroups"},
     {"SR_FORCE_INT32", "off", "tests: 32-bit offsets (and the 16-bit ring of 32-bit searches) whatever the sequence length"},
     {"SR_TEST_BASE_LEVELS", "off", "tests: cap on the levels a base case is given at first (forces the re-queue path)"},
@@ -282,6 +284,11 @@ struct sr_ctx {
     std::vector<uint32_t> batch_partners;          // [nbatch] primaries per batch
     uint32_t *d_tail_list = nullptr, *d_tail_deferred = nullptr;
     unsigned long long *d_timeline = nullptr;      // instrumented instance: [nwg][4] (sr_ctx_tail_timeline)
+    // rotating tile priority (sr_prio_rule.h): arrival counts per CU (reset before every main launch of the blocked kernel), the
+    // instrumented instance's second record [nwg][4] (sr_ctx_prio_timeline)
+    int prio_rounds = SR_TAIL_ROUNDS_DEFAULT;      // a batch rotates only when its alignments are at most this many times its workgroups
+    uint32_t *d_cu_arrivals = nullptr;
+    unsigned long long *d_prio_timeline = nullptr;
     // kernel timing: [kind] -> one event pair per batch (kinds: 0 align, 1 unite, 4 orientation) or a single pair (2, 3)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
     int ev_used[5] = {0, 0, 0, 0, 0};
@@ -339,6 +346,7 @@ static void free_dev(sr_ctx *c) {
     c->d_error = nullptr; c->d_queue = nullptr; c->d_oqueue = nullptr; c->d_order = nullptr; c->d_cbase = nullptr;
     c->d_bases = nullptr; c->d_max_score = nullptr; c->d_mirror = nullptr; c->mirror_partners = 0; c->onwg = 0;
     c->tail_threads = 0; c->tail_all = false; c->batch_partners.clear(); c->d_tail_list = c->d_tail_deferred = nullptr; c->d_timeline = nullptr;
+    c->d_cu_arrivals = nullptr; c->d_prio_timeline = nullptr;
     c->d_okeys = c->d_okeys2 = nullptr; c->d_ovals = nullptr; c->d_otemp = nullptr; c->otemp_bytes = 0;
     c->loaded = false; c->from_paf = false; c->aligned_batch_valid = false;
     for (int k = 0; k < 5; k++) c->ev_used[k] = 0;
@@ -1225,6 +1233,19 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     if (impl == 2 && knob("SR_PROFILE_TICKS") && atoi(knob("SR_PROFILE_TICKS")) != 0) {
         if ((r = dev_alloc(c, &d, (size_t)nwg * 4 * 8))) return r; c->d_timeline = (unsigned long long *)d;
         HIPCHK(hipMemsetAsync(c->d_timeline, 0, (size_t)nwg * 4 * 8, c->stream));
+        if ((r = dev_alloc(c, &d, (size_t)nwg * 4 * 8))) return r; c->d_prio_timeline = (unsigned long long *)d;
+        HIPCHK(hipMemsetAsync(c->d_prio_timeline, 0, (size_t)nwg * 4 * 8, c->stream));
+    }
+    if (impl == 2) {
+        // rotating tile priority: the workgroups per CU the wave budget allows (16 waves per CU: 4 per SIMD); one per CU -- the
+        // 1 024-thread shape -- has nothing to arbitrate and the rule is off, as under SR_TILE_PRIO=0
+        if ((r = dev_alloc(c, &d, SR_PRIO_TABLE * sizeof(uint32_t)))) return r; c->d_cu_arrivals = (uint32_t *)d;
+        HIPCHK(hipMemsetAsync(c->d_cu_arrivals, 0, SR_PRIO_TABLE * sizeof(uint32_t), c->stream));
+        const char *tp = knob("SR_TILE_PRIO");
+        a.prio_wg = std::max(1, std::min(pl.wg_per_cu, 1024 / std::max(64, c->nthreads)));
+        a.tile_prio = (a.prio_wg > 1 && !(tp && atoi(tp) == 0)) ? 1 : 0;
+        const char *trk = knob("SR_TAIL_ROUNDS");
+        c->prio_rounds = trk ? std::max(0, atoi(trk)) : SR_TAIL_ROUNDS_DEFAULT;
     }
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bring_wg * rsz))) return r; a.bring = d;
     if ((r = dev_alloc(c, &d, (uint64_t)nwg * pl.bhist_wg * osz))) return r; a.bhist = d;
@@ -1326,6 +1347,7 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
     a.mirror = c->d_mirror;
     // (tail_list is set per batch, enqueue_align_batch: NULL unless the batch defers)
     a.tail_count = c->d_queue + 1; a.tail_head = c->d_queue + 2; a.tail_deferred = c->d_tail_deferred; a.timeline = c->d_timeline;
+    a.cu_arrivals = c->d_cu_arrivals; a.prio_timeline = c->d_prio_timeline;
     c->fuse_unite = impl == 2 && !knob("SR_NO_FUSED_UNITE");
     u.is_reverse = a.is_reverse; u.score = a.score; u.max_score = c->d_max_score;
     u.cigar_ops = a.cigar_ops; u.cigar_base = c->d_cbase; u.cigar_cnt = a.cigar_cnt;
@@ -1336,7 +1358,7 @@ static int alloc_workspace(sr_ctx *c, const sr_params *p, const PackedSeqs &pk, 
 
 static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const Plan &pl) {
     const uint32_t np = (uint32_t)c->pair_q.size();
-    char buf[2048];
+    char buf[3072];
     // which build the launchers take (srk_align: lean wave build / wide level kernel; srk_orient: blocked or level by level)
     const SrPen &ori = c->aa.ori;
     const char *oroute = c->onwg == 0 ? "in-kernel"
@@ -1348,14 +1370,15 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
              "\"base_history_bytes_per_workgroup\": %llu, \"workspace_bytes\": %llu, \"cigar_arena_bytes\": %llu, "
              "\"orientation_ring_bytes\": %llu, \"union_find_bytes\": %llu, \"device_free_bytes_at_load\": %zu, \"kernel_build\": \"%s\", "
              "\"ring_depth_m\": %d, \"ring_depth_id\": %d, \"fused_unite\": %d, \"wave_build\": %d, \"level_kernel_wide\": %d, "
-             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"tail_threads\": %d, \"mirror_replay\": %d, \"replay_record_bytes\": %llu, \"knobs\": ",
+             "\"profile_ticks\": %d, \"orientation_route\": \"%s\", \"source_digest\": \"%s\", \"mirror_partners\": %llu, \"tail_threads\": %d, \"mirror_replay\": %d, \"replay_record_bytes\": %llu, \"tile_prio\": %d, \"prio_epoch_shift\": %d, \"prio_workgroups_per_cu\": %d, \"knobs\": ",
              np, pl.nbatch, pk.sm.bits, pl.osz, pl.impl == 2 ? pl.rsz : pl.osz, pl.impl, pl.impl == 2 ? pl.kblock : 1, pen.two ? 1 : 0, pl.lazy_id,
              pl.nwg, c->nthreads, pl.wg_per_cu, c->lds_bytes,
              (unsigned long long)(pl.bring_wg * pl.rsz), (unsigned long long)(pl.bhist_wg * pl.osz),
              (unsigned long long)((uint64_t)pl.nwg * pl.per_wg_bytes), (unsigned long long)(pl.arena_ops * 4), (unsigned long long)pl.oring_bytes,
              (unsigned long long)(3ULL * c->uf_size * 8), pl.free_b, srk_align_blk_build_tag(), pl.kdepth, pl.kdepth2, c->fuse_unite ? 1 : 0,
              pl.wave_wg ? 1 : 0, (pl.impl == 1 && pl.ring_scope + 1 > 32) ? 1 : 0, c->aa.profile_ticks, oroute, srk_source_digest(),
-             (unsigned long long)c->mirror_partners, c->tail_threads, pl.brec_bytes ? 1 : 0, (unsigned long long)pl.brec_bytes);
+             (unsigned long long)c->mirror_partners, c->tail_threads, pl.brec_bytes ? 1 : 0, (unsigned long long)pl.brec_bytes,
+             c->aa.tile_prio, SR_PRIO_EPOCH_SHIFT, c->aa.prio_wg);
     c->workspace_report = std::string(buf) + knobs_json() + "}";
 }
 
@@ -1461,6 +1484,11 @@ static int enqueue_align_batch(sr_ctx *c, uint32_t b, bool fuse_unite = false) {
     const bool defer = partners > 0 && (c->tail_all || (uint64_t)(a.npairs - partners) <= (uint64_t)c->tail_rounds * (uint64_t)main_wg);
     a.tail_list = defer ? c->d_tail_list : nullptr;
     a.tail_mode = defer && c->tail_all ? SR_TAIL_DEFER_ALL : SR_TAIL_MAIN;
+    // Rotating tile priority: short lists only, by the tail launch's rule (alignments <= SR_TAIL_ROUNDS x workgroups).  What the
+    // rotation evens out is the end of a round of alignments; a long list (C4: 60 rounds) keeps every CU full until its last
+    // round whoever is served first, and measured 0.7 % slower with the rotation than without.
+    const uint32_t secondaries = b < c->batch_partners.size() ? std::min<uint32_t>(c->batch_partners[b], a.npairs) : 0;
+    if ((uint64_t)(a.npairs - secondaries) > (uint64_t)c->prio_rounds * (uint64_t)main_wg) a.tile_prio = 0;
     HIPCHK(hipMemsetAsync(c->d_queue, 0, (c->tail_threads ? 3 : 1) * sizeof(uint32_t), c->stream));
     hipEvent_t *e0, *e1;
     int r;
@@ -1480,6 +1508,7 @@ static int enqueue_align_batch(sr_ctx *c, uint32_t b, bool fuse_unite = false) {
     if ((r = ev_get(c, 0, c->ev_used[0], &e0, &e1))) return r;
     HIPCHK(hipEventRecord(*e0, c->stream));
     if (a.npairs > 0) {
+        if (a.cu_arrivals) HIPCHK(hipMemsetAsync(a.cu_arrivals, 0, SR_PRIO_TABLE * sizeof(uint32_t), c->stream));
         r = srk_align(&a, main_wg, c->lds_bytes, c->off16, c->nthreads, c->stream);
         if (r) return fail(SR_ERR_HIP, std::string("align kernel launch failed: ") + hipGetErrorString((hipError_t)r));
         if (defer) {
@@ -1487,6 +1516,7 @@ static int enqueue_align_batch(sr_ctx *c, uint32_t b, bool fuse_unite = false) {
             // (the kernel boundary orders the list); an empty list makes every workgroup return at once
             const int grid = (int)std::min<uint64_t>({(uint64_t)c->tail_cus * (uint64_t)c->tail_wg_per_cu, (uint64_t)c->nwg, (uint64_t)partners});
             a.tail_mode = SR_TAIL_RUN; a.timeline = nullptr;
+            a.cu_arrivals = nullptr; a.prio_timeline = nullptr; a.tile_prio = 0;       // (one workgroup per CU slot: no rank, tile code at 0)
             r = srk_align(&a, grid, c->lds_bytes, c->off16, c->tail_threads, c->stream);
             if (r) return fail(SR_ERR_HIP, std::string("align kernel tail launch failed: ") + hipGetErrorString((hipError_t)r));
         }
@@ -1647,7 +1677,7 @@ extern "C" int sr_ctx_counters_ext(sr_ctx *c, uint64_t out[32]) {
     HIPCHK(hipMemcpy(out, c->d_counters, 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return SR_OK;
 }
-// every slot the device keeps (SR_NCOUNTERS = 52: 48 since round 4, [48..51] the replay's); returns the number of slots written (<= cap) or a negative status
+// every slot the device keeps (SR_NCOUNTERS = 54: 48 since round 4, [48..51] the replay's, [52..53] the tile priority's); returns the number of slots written (<= cap) or a negative status
 extern "C" int sr_ctx_counters_all(sr_ctx *c, uint64_t *out, uint32_t cap) {
     if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
     HIPCHK(hipSetDevice(c->device));
@@ -1680,6 +1710,21 @@ extern "C" int sr_ctx_tail_timeline(sr_ctx *c, uint64_t *out, uint32_t cap_wg) {
     HIPCHK(hipMemcpy(out, c->d_timeline, (size_t)n * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return (int)n;
 }
+
+// the instrumented instance's second record of the last main launch, 4 words per workgroup (SrAlignArgs::prio_timeline): tick of
+// the end of the first alignment, rank on the CU, table index of the CU, arrival count; same return value as sr_ctx_tail_timeline
+extern "C" int sr_ctx_prio_timeline(sr_ctx *c, uint64_t *out, uint32_t cap_wg) {
+    if (!c || !c->loaded || !out) return fail(SR_ERR_INVALID, "context not loaded");
+    if (!c->d_prio_timeline) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint32_t n = std::min<uint32_t>(cap_wg, (uint32_t)c->nwg);
+    HIPCHK(hipMemcpy(out, c->d_prio_timeline, (size_t)n * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return (int)n;
+}
+// host twin of the device rule (sr_prio_rule.h): s_setprio level of a workgroup's tile code
+extern "C" int sr_tile_prio_role_host(uint32_t rank, uint32_t epoch, uint32_t wg_per_cu) { return sr_tile_prio_role(rank, epoch, wg_per_cu); }
+extern "C" int sr_tile_prio_epoch_shift(void) { return SR_PRIO_EPOCH_SHIFT; }
 
 extern "C" int sr_ctx_download_uf(sr_ctx *c, uint64_t *parent_out) {
     if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");

@@ -121,6 +121,14 @@ struct SrAlignArgs {
     int *brec;
     unsigned long long *timeline;   // instrumented instance: [workgroup][4] first dequeue, start of the last alignment, exit
                                     // (100 MHz ticks), alignments | last-from-mir_next << 32; NULL = none
+    // impl 2, rotating tile priority (sr_prio_rule.h).  Main launch: thread 0 of every workgroup adds 1 to its CU's
+    // word of cu_arrivals ([SR_PRIO_TABLE], reset before every main launch); the old value modulo prio_wg is the workgroup's rank
+    // among the workgroups of its CU.  NULL (tail launch, level-per-pass kernel): no rank is taken
+    uint32_t *cu_arrivals;
+    int prio_wg;                    // workgroups per CU of the launch as the wave budget allows them (1: the rule is off)
+    int tile_prio;                  // 1: the tile code of a pass runs at sr_tile_prio_role(); 0 (SR_TILE_PRIO=0, prio_wg 1, tail launch): at 0
+    unsigned long long *prio_timeline;   // instrumented instance: [workgroup][4] end of the first alignment (tick), rank, table index,
+                                         // arrival count (sr_ctx_prio_timeline); NULL = none
     // outputs
     uint8_t *is_reverse;       // [npairs]
     int32_t *score;            // [npairs]
@@ -131,7 +139,7 @@ struct SrAlignArgs {
     unsigned long long *counters; // [SR_NCOUNTERS]
     int *error_flag;
 };
-#define SR_NCOUNTERS 52
+#define SR_NCOUNTERS 54
 enum { SR_TAIL_MAIN = 0,        // main launch: defer a fallback secondary when the queue is dry
        SR_TAIL_RUN = 1,         // tail launch: the list is the queue
        SR_TAIL_DEFER_ALL = 2 }; // main launch, SR_TAIL=all: defer every fallback secondary (tests)

@@ -480,8 +480,8 @@ class Context:
 
     def counters(self):
         """device counters of the last align / unite (include/seqrush_amd.h sr_ctx_counters_all): every name maps to ONE slot"""
-        out = (C.c_uint64 * 52)()
-        n = self.L.sr_ctx_counters_all(self._h, out, 52)
+        out = (C.c_uint64 * 54)()
+        n = self.L.sr_ctx_counters_all(self._h, out, 54)
         if n < 0:
             check(n)
         return dict(row_bytes_loaded=int(out[16]), row_bytes_stored=int(out[17]), tk_recompute=int(out[18]),
@@ -508,7 +508,10 @@ class Context:
                     # ties all sit in base-case backtraces; secondaries that took breakpoints from their primary's records;
                     # searches they did not run
                     mirror_tie_top=int(out[48]), mirror_tie_base_only=int(out[49]), mirror_replays=int(out[50]),
-                    replay_cached_searches=int(out[51]))
+                    replay_cached_searches=int(out[51]),
+                    # rotating tile priority: workgroups of the main launches that took a rank on their CU, the
+                    # largest arrival count of a CU in one launch
+                    prio_ranks_taken=int(out[52]), prio_max_cu_arrivals=int(out[53]))
 
     def tail_deferred(self) -> int:
         """secondaries handed to the tail launch in the last pass (sr_ctx_tail_deferred; syncs)"""
@@ -522,6 +525,16 @@ class Context:
         cap = int(self.workspace_report().get("workgroups", 0))
         out = np.zeros((max(cap, 1), 4), dtype=np.uint64)
         n = self.L.sr_ctx_tail_timeline(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), cap)
+        if n < 0:
+            check(n)
+        return out[:n]
+
+    def prio_timeline(self):
+        """[workgroups, 4] uint64, the second record of the same launch (sr_ctx_prio_timeline): tick of the end of the first
+        alignment, rank among the workgroups of the CU, the CU's index in the arrival table, arrival count"""
+        cap = int(self.workspace_report().get("workgroups", 0))
+        out = np.zeros((max(cap, 1), 4), dtype=np.uint64)
+        n = self.L.sr_ctx_prio_timeline(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), cap)
         if n < 0:
             check(n)
         return out[:n]
