@@ -979,7 +979,7 @@ static int plan_kernel(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, const 
     pl.max_words = (uint32_t)((maxlen + pk.per_word - 1) / pk.per_word + 2);
     c->lds_bytes = (size_t)pl.max_words * 3 * 4;          // query fwd / rc + target fwd
     if ((long long)c->lds_bytes > (long long)srk_align_max_lds())
-        return fail(SR_ERR_UNSUPPORTED, "sequences too long to stage in LDS (limit ~ 170 kb per sequence at 2 bits per base)");
+        return fail(SR_ERR_UNSUPPORTED, "sequences too long to stage in LDS (limit 177456 / 88728 / 44364 symbols per sequence at 2 / 4 / 8 bits per symbol)");
     pl.impl = 1;
     pl.kblock = srk_align_blk_supports(&pen, &ori);
     // SR_BLK_LEVELS=5: the generic 5-level instance instead of the exact-penalty 10-level one (A/B runs, tests)
