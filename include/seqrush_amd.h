@@ -324,6 +324,15 @@ int sr_iterative_pair_lists(uint32_t n, const uint8_t *sel, const sr_params *p, 
 /* host twin of the blocked alignment kernel's base-case cone: a level with `levels_left` levels to its job's last one
  * computes the diagonals within this many of the end diagonal tlen - plen (< 0: none) */
 int sr_base_cone_reach(int e1, int e2, int two, int levels_left);
+/* host twin of the blocked alignment kernel's pass tables (csrc/sr_pass_rule.h), organised as the kernel is: per-level ranges
+ * and cells by (aligner, level) lanes, 64 / B aligners per step, then window, tile count and tile prefix per aligner.
+ * pen6 = x, o1, e1, o2, e2, two; jobs = njobs records of 7 ints (active, begin component, plen, tlen, shift, kend, levels
+ * given); base: base cases (ranges and window cut to the backward cone).  klo / khi: [B][njobs], written for active aligners
+ * only; cells / ccells: the aligners' unclipped / clipped cells, ADDED to the arrays; tstart: njobs + 1 entries.  Returns the
+ * lane steps taken, < 0 for arguments no instance has.  sr_pass_tile_own: 4-diagonal groups a tile of a B-level block owns. */
+int sr_pass_tables_host(const int *pen6, int scope, int B, int tight, int base, int s0, int njobs, const int *jobs, int *klo,
+                        int *khi, long long *cells, long long *ccells, int *glo, int *ghi, int *nt, int *tstart);
+int sr_pass_tile_own(int B);
 /* Mirror partners of the blocked alignment kernel: when a batch holds (q, t) and (t, q), the first (q, t) with
  * q < t is the primary and the first (t, q) its secondary; the kernel aligns the primary and writes the secondary's result as
  * the transposed CIGAR unless a tie-break decided something (then it aligns the secondary too).  mirror_out[i] = the

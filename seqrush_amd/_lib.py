@@ -48,6 +48,7 @@ EXPORTS = [
     "sr_ctx_tail_deferred", "sr_ctx_tail_timeline", "sr_tail_shape",
     "sr_replay_record_ints", "sr_replay_transpose_host", "sr_replay_match_host",
     "sr_ctx_prio_timeline", "sr_tile_prio_role_host", "sr_tile_prio_epoch_shift",
+    "sr_pass_tables_host", "sr_pass_tile_own",
 ]
 
 
@@ -293,6 +294,9 @@ def load():
     L.sr_uf_count_components_host.argtypes = [C.POINTER(u64), u64, u64, C.POINTER(u64)]
     L.sr_iterative_stop_host.argtypes = [C.POINTER(u64), u64, u64, C.POINTER(u64)]
     L.sr_base_cone_reach.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    IP, LP = C.POINTER(C.c_int), C.POINTER(C.c_longlong)
+    L.sr_pass_tables_host.argtypes = [IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP, LP, LP, IP, IP, IP, IP]
+    L.sr_pass_tile_own.argtypes = [C.c_int]
     PU32 = C.POINTER(C.POINTER(C.c_uint32))
     L.sr_iterative_pair_lists.argtypes = [C.c_uint32, C.POINTER(C.c_uint8), PP, PU32, PU32, C.POINTER(u64), PU32, PU32,
                                           C.POINTER(u64)]

@@ -374,9 +374,16 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                         //  copy of the thread index, here, once per pass: hoisted out of the pass loop they lived, spilled, across the tiles)
                         const int tid = (int)kopaque_v((unsigned)tid_o);
                         KPRIO_HI();
-                        if (tid < njobs) {
-#pragma unroll
-                            for (int j = 0; j < B; j++) gmak[tid * BFS_MAK_SLOTS + (s0 + j) % depth] = k_sh.jak[j][tid];
+                        {   // max_ak of the block's levels: one (aligner, level) pair per lane, as the pass tables (sr_pass_rule.h);
+                            // one modulo per pass (uniform; B < depth, so + level wraps once); the stores drain under the rest
+                            const int sb = s0 % depth, steps = sr_pass_steps(njobs, B);
+                            for (int st = 0; st < steps; st++) {
+                                int al, j;
+                                if (sr_pass_lane(tid, st, B, al, j) && al < njobs) {
+                                    const int sl = sb + j;
+                                    gmak[al * BFS_MAK_SLOTS + (sl >= depth ? sl - depth : sl)] = k_sh.jak[j][al];
+                                }
+                            }
                         }
                         const unsigned long long qc1 = KTICK();
                         int ph = 0, ph0 = 0;
@@ -387,20 +394,33 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             if (ph == 1) {
                                 int score_f = sg.score_f, score_r = sg.score_r, last_fwd = sg.last_fwd, f_ak = sg.f_ak, r_ak = sg.r_ak;
                                 const int max_ad = sg.max_ad;
-                                for (int j = 0; j < B && ph == 1; j++) {
-                                    const int s = s0 + j;
-                                    const int akf = k_sh.jak[j][2 * tid], akr = k_sh.jak[j][2 * tid + 1];
+                                // the segment's 2 B max antidiagonals in one batch of independent LDS reads (a pair per level):
+                                // the walk over the levels then runs on registers
+                                typedef int __attribute__((ext_vector_type(2), may_alias)) I2;
+                                I2 ak[B];
+#pragma unroll
+                                for (int j = 0; j < B; j++) ak[j] = *(const I2 *)&k_sh.jak[j][2 * tid];
+                                // Per level, in the order of the search: the forward aligner takes the level (score_f = s) and is
+                                // tested against the reverse aligner's previous one, then the reverse aligner takes it and the sum
+                                // of the scores and the antidiagonals are tested again.  Selects, not branches: a level that comes
+                                // after the segment left phase 1 changes nothing (ten nested lane conditions would cost ten
+                                // saved EXEC masks, which this kernel keeps in spilled registers).
+#pragma unroll
+                                for (int j = 0; j < B; j++) {
+                                    const int s = s0 + j;                       // (uniform)
+                                    const bool on = ph == 1;
+                                    const int akf = ak[j].x, akr = ak[j].y;
+                                    const bool both = akf + akr >= max_ad;
                                     if (s == 0) {
-                                        f_ak = akf; r_ak = akr;
-                                        if (f_ak + r_ak >= max_ad) ph = 2;
+                                        f_ak = on ? akf : f_ak; r_ak = on ? akr : r_ak;
+                                        ph = (on && both) ? 2 : ph;
                                     } else {
-                                        score_f = s; f_ak = akf; last_fwd = 1;
-                                        if (f_ak + r_ak >= max_ad) ph = 2;
-                                        else {
-                                            score_r = s; r_ak = akr; last_fwd = 0;
-                                            if ((long long)score_f + score_r > smax) ph = 4;
-                                            else if (f_ak + r_ak >= max_ad) ph = 2;
-                                        }
+                                        const bool fwd_hit = akf + r_ak >= max_ad;     // forward at s, reverse still at s - 1
+                                        const bool rev = on && !fwd_hit;
+                                        const bool over = (long long)s + s > smax;     // score_f + score_r, both s
+                                        score_f = on ? s : score_f; f_ak = on ? akf : f_ak; last_fwd = on ? (fwd_hit ? 1 : 0) : last_fwd;
+                                        score_r = rev ? s : score_r; r_ak = rev ? akr : r_ak;
+                                        ph = on ? (fwd_hit ? 2 : (over ? 4 : (both ? 2 : 1))) : ph;
                                     }
                                 }
                                 sg.score_f = score_f; sg.score_r = score_r; sg.last_fwd = last_fwd; sg.f_ak = f_ak; sg.r_ak = r_ak;
@@ -418,7 +438,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             if (tid < nact && ph != 1) { b_sh.job[2 * tid].active = 0; b_sh.job[2 * tid + 1].active = 0; }
                             if (tid == 0) b_sh.nrunning = __popcll(run);
                             // (the lanes' stores to job[].active above are read by other lanes below: same wave, LDS in order)
-                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs);   // tables of the next pass
+                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs, tid);   // tables of the next pass
                         }
                         KPRIO_LO();
                     }
@@ -437,12 +457,13 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                     if ((RFL(k_sh.p2mask_lo) | RFL(k_sh.p2mask_hi)) != 0u) {
                         blk_phase2<OT, TWO, NT, B, E1, E2, RT, PROF>(RR, clist, gmak, pen, s0, nact, gap_opening);
                         if (tid < 64) {
+                            const int tid = (int)kopaque_v((unsigned)tid_o);
                             KPRIO_HI();
                             const int ph = (tid < nact) ? b_sh.seg[tid].phase : 0;
                             const unsigned long long run = __ballot(ph == 1 || ph == 2);
                             if (tid < nact && ph != 1 && ph != 2) { b_sh.job[2 * tid].active = 0; b_sh.job[2 * tid + 1].active = 0; }
                             if (tid == 0) b_sh.nrunning = __popcll(run);
-                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs);   // tables of the next pass
+                            if (run != 0ull) blk_setup<TWO, NT, B, E1, E2, KTIGHT>(s0 + B, pen, njobs, tid);   // tables of the next pass
                             KPRIO_LO();
                         }
                     }
@@ -583,13 +604,17 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                         blk_pass<OT, TWO, NT, B, E1, E2, PROF, X, OE1, OT, false, true>(RH, s0, pen, nb, row_ld, row_st, s0 == 0);
                         __syncthreads();
                         if (tid == 0) k_sh.dg_steps += (unsigned long long)b_sh.nrunning * B;
+                        const int tid_o = tid;
                         if (tid < 64) {                          // one lane per base case: first level of the block that reached the end
+                            const int tid = (int)kopaque_v((unsigned)tid_o);       // (per pass, as in the searches' control section)
                             KPRIO_HI();
                             bool running = false;
                             if (tid < nb && b_sh.job[tid].active) {
-                                int hit = -1;
+                                int hit = -1, jr[B];                 // the job's B reach flags: one batch of independent LDS reads
 #pragma unroll
-                                for (int l = B - 1; l >= 0; l--) if (k_sh.jreach[l][tid]) hit = l;
+                                for (int l = 0; l < B; l++) jr[l] = k_sh.jreach[l][tid];
+#pragma unroll
+                                for (int l = B - 1; l >= 0; l--) if (jr[l]) hit = l;
                                 if (hit >= 0) {
                                     b_sh.base_score[tid] = s0 + hit; b_sh.job[tid].active = 0;
                                     atomicAdd(&b_sh.cells, (unsigned long long)(-blk_surplus(pen, tid, s0 + hit, s0 + B - 1)));
@@ -602,7 +627,7 @@ __global__ void __launch_bounds__(NT, SR_BLK_MIN_WAVES) sr_align_blk_kernel(SrAl
                             }
                             const unsigned long long rm = __ballot(running);
                             if (tid == 0) b_sh.nrunning = __popcll(rm);
-                            if (rm != 0ull) blk_setup<TWO, NT, B, E1, E2, false, true>(s0 + B, pen, nb);   // tables of the next pass (cone-clipped)
+                            if (rm != 0ull) blk_setup<TWO, NT, B, E1, E2, false, true>(s0 + B, pen, nb, tid);   // tables of the next pass (cone-clipped)
                             KPRIO_LO();
                         }
                         __syncthreads();

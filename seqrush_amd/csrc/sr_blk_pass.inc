@@ -2,21 +2,14 @@
 // (kreach, kwindow), the pass tables (blk_setup), the tile queue (blk_pass), the I/D recompute pass (blk_recompute).
 #include "sr_base_cone.h"       // backward cone of a base case (shared with the host twin)
 #include "sr_prio_rule.h"       // rotating tile priority of co-resident workgroups (shared with the host twin)
+#include "sr_pass_rule.h"       // the tables of a pass: reach, ranges, cone clip, cells, tile windows (shared with the host twin)
 // reach() with compile-time gap-extends (the host guarantees pen.e1 == E1, pen.e2 == E2): no runtime division
 template <bool TWO, int E1, int E2>
 __device__ __forceinline__ int kreach(const SrPen &p, int s, int begin) {
-    int r;
-    if (begin == SR_C_M) {
-        r = (s >= p.o1 + E1) ? (s - p.o1) / E1 : 0;
-        if (TWO && s >= p.o2 + E2) r = max(r, (s - p.o2) / E2);
-    } else {
-        r = s / E1;
-        if (TWO) r = max(r, s / E2);
-    }
-    return r;
+    return sr_pass_reach(p.o1, E1, p.o2, E2, TWO, s, begin == SR_C_M);
 }
 
-// Groups [glo, ghi] the tiles of block s0 (levels s0 .. s0+B-1) of aligner b cover -- and store.
+// Groups [glo, ghi] the tiles of block s0 (levels s0 .. s0+B-1) of aligner b cover -- and store (sr_pass_window).
 //  * wide (round 1-3, still used by base-case histories and the generic instances): the last level's range + scope + 1
 //    diagonals either side, so that every later reader (levels up to scope + B above, one neighbour diagonal) finds NULL
 //    beyond the range instead of whatever the ring slot held before: 2 (scope + 1) = 54 extra diagonals per aligner and
@@ -28,10 +21,9 @@ __device__ __forceinline__ int kreach(const SrPen &p, int s, int begin) {
 //    breakpoint detection tests every cell against its level's range anyway.
 template <bool TWO, int B, int E1, int E2, bool TIGHT>
 __device__ __forceinline__ void kwindow(const SrPen &pen, const BJob &b, int s0, int &glo, int &ghi) {
-    const int Rw = kreach<TWO, E1, E2>(pen, s0 + B - 1, b.begin);
-    const int mg = TIGHT ? 1 : pen.scope + 1;
-    const int wlo = max(-b.plen - 1, -Rw - mg), whi = min(b.tlen + 1, Rw + mg);
-    glo = (wlo + b.shift) >> 2; ghi = (whi + b.shift) >> 2;
+    int nt;
+    sr_pass_window(kreach<TWO, E1, E2>(pen, s0 + B - 1, b.begin), TIGHT ? 1 : pen.scope + 1, b.plen, b.tlen, b.shift, false, 0, 0,
+                   KGeo<B>::OWN, glo, ghi, nt);
 }
 
 // One pass: levels s0 .. s0+B-1 of every active aligner.  Ends with the data of the
@@ -54,6 +46,8 @@ __device__ __forceinline__ void kprio_role() {
 }
 // wave 0, once per pass (blk_setup): the role of the next pass from the workgroup's rank and the real-time counter.  The
 // counter is the same on every CU, so co-resident workgroups change roles together.  Rule off: no clock read, role stays 0.
+// (Issuing the read at the start of the caller's section and consuming it here was measured and did not pay: the next LDS
+// wait has to wait for the scalar read as well, DESIGN.md 6.1.)
 __device__ __forceinline__ void kprio_epoch() {
     const int wg = RFL(k_sh.prio_wg);
     if (wg > 1) {
@@ -63,9 +57,13 @@ __device__ __forceinline__ void kprio_epoch() {
 }
 #define KPRIO_HI() __builtin_amdgcn_s_setprio(3)
 #define KPRIO_LO() kprio_role()
-// Tables of one pass (levels s0 .. s0+B-1 of every active aligner): wave 0, one lane per aligner.  The first pass of a batch
+// Tables of one pass (levels s0 .. s0+B-1 of every active aligner): wave 0.  The first pass of a batch
 // of searches runs it inside blk_pass; later passes get their tables from the wave-0 section that ends the previous pass
 // (control, or the section after breakpoint detection), so a pass costs one barrier and one serial hop less.
+// The section is the pair's critical path and mostly serves two aligners (a depth-0 search), so nothing in it is a loop
+// over the block's levels (sr_pass_rule.h): the per-level tables are written one (aligner, level) pair per lane, 64 / B
+// aligners per step, the per-aligner ones one aligner per lane from the block's first and last level alone, and the tile
+// prefix is a DPP scan.  tid: the caller's opaque copy of the thread index (< 64).
 // BASE: the aligners are base cases.  Each knows its end diagonal (kend) and the levels it was given (pad1 = lj), so every
 // level's range, and the tile window with it, is intersected with the backward cone of the end (sr_base_cone.h): cells outside
 // it cannot lie on a path to the end, are not computed (NULL inside the window) and not stored.  The window keeps the wide
@@ -77,60 +75,74 @@ __device__ __forceinline__ void kprio_epoch() {
 #ifndef SR_BASE_CONE
 #define SR_BASE_CONE 1             // (0: A/B build that computes the full forward triangle, as before)
 #endif
+// inclusive prefix sum over the first BJ_MAX lanes of a full wave (lanes past them hold 0)
+__device__ __forceinline__ int kscan_jobs(int v) {
+    static_assert(BJ_MAX <= 32 && BJ_MAX % 4 == 0, "kscan_jobs: at most two DPP rows of aligners");
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);      // row_shr:1, 2, 4, 8 (zero-filled): the scan of a row of 16
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
+    if (BJ_MAX > 8) v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
+    if (BJ_MAX > 16) v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+    return v;
+}
 template <bool TWO, int NT, int B, int E1, int E2, bool TIGHT = false, bool BASE = false>
-__device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs) {
-    const int tid = threadIdx.x;                         // (tid < 64)
+__device__ __forceinline__ void blk_setup(int s0, const SrPen &pen, int njobs, const int tid) {
     constexpr bool CONE = BASE && SR_BASE_CONE;
-    int nt = 0, glo = 0, ghi = -1, cells = 0, ccells = 0;
+    if (tid < BJ_MAX) {        // (cleared per aligner lane: 16-byte stores over the flat tables were measured and did not pay)
+#pragma unroll
+        for (int j = 0; j < B; j++) { k_sh.jak[j][tid] = 0; k_sh.jreach[j][tid] = 0; }
+    }
+    if (BASE) {
+        // base cases: one lane per job, its levels one after the other -- a batch keeps up to 16 lanes busy, and by (job, level)
+        // lanes it took three steps and an LDS add per level (measured: the base cases' section 6 % slower, profiles/pass_ctl_ab.log)
+        if (tid < njobs && b_sh.job[tid].active) {
+            const BJob &b = b_sh.job[tid];
+            int cells = 0, ccells = 0;
+#pragma unroll
+            for (int j = 0; j < B; j++) {
+                const int rb = CONE ? sr_cone_reach(E1, E2, TWO, b.pad1 - 1 - (s0 + j)) : 0;      // (< 0 past the job's levels: empty)
+                int klo, khi, c, cc;
+                sr_pass_level(kreach<TWO, E1, E2>(pen, s0 + j, b.begin), b.plen, b.tlen, CONE, CONE ? b.kend : 0, rb, klo, khi, c, cc);
+                k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
+                cells += c; ccells += cc;
+            }
+            k_sh.cells_l[tid] += (unsigned long long)cells;
+            if (ccells) atomicAdd(&k_sh.base_cells, (unsigned long long)ccells);
+        }
+    } else {
+        // searches: range and cells per level -- lanes enumerate (aligner, level) pairs
+        const int steps = sr_pass_steps(njobs, B);
+        for (int st = 0; st < steps; st++) {
+            int a, j;
+            if (sr_pass_lane(tid, st, B, a, j) && a < njobs && b_sh.job[a].active) {
+                const BJob &b = b_sh.job[a];
+                int klo, khi, cells, ccells;
+                sr_pass_level(kreach<TWO, E1, E2>(pen, s0 + j, b.begin), b.plen, b.tlen, false, 0, 0, klo, khi, cells, ccells);
+                k_sh.jklo[j][a] = klo; k_sh.jkhi[j][a] = khi;
+                if (cells) atomicAdd(&k_sh.cells_l[a], (unsigned long long)cells);
+            }
+        }
+    }
+    // per aligner: window, tiles
+    int nt = 0, glo = 0, ghi = -1;
     const bool act = tid < njobs && b_sh.job[tid].active;
     const int pglo = (tid < BJ_MAX) ? k_sh.jglo[tid] : 0, pghi = (tid < BJ_MAX) ? k_sh.jghi[tid] : -1;
     if (act) {
         const BJob &b = b_sh.job[tid];
-        int Rw = 0, clo0 = 0, chi0 = 0;
-#pragma unroll
-        for (int j = 0; j < B; j++) {
-            Rw = kreach<TWO, E1, E2>(pen, s0 + j, b.begin);
-            int klo = max(-b.plen, -Rw), khi = min(b.tlen, Rw);
-            cells += (khi >= klo) ? khi - klo + 1 : 0;
-            if (CONE) {
-                const int rb = sr_cone_reach(E1, E2, TWO, b.pad1 - 1 - (s0 + j));      // (< 0 past the job's levels: empty)
-                klo = max(klo, b.kend - rb); khi = min(khi, b.kend + rb);
-                if (j == 0) { clo0 = b.kend - rb; chi0 = b.kend + rb; }                // the block's widest cone
-            }
-            k_sh.jklo[j][tid] = klo; k_sh.jkhi[j][tid] = khi;
-            ccells += (khi >= klo) ? khi - klo + 1 : 0;
-        }
-        (void)Rw;
-        kwindow<TWO, B, E1, E2, TIGHT>(pen, b, s0, glo, ghi);
-        if (CONE) {
-            const int mg = TIGHT ? 1 : pen.scope + 1;
-            const int wlo = max(max(-b.plen - 1, -Rw - mg), clo0 - 1), whi = min(min(b.tlen + 1, Rw + mg), chi0 + 1);
-            glo = (wlo + b.shift) >> 2; ghi = (whi >= wlo) ? (whi + b.shift) >> 2 : glo - 1;
-        }
-        nt = max(0, (ghi - glo + KGeo<B>::OWN) / KGeo<B>::OWN);
-        if (BASE && ccells) atomicAdd(&k_sh.base_cells, (unsigned long long)ccells);
+        const int rb0 = CONE ? sr_cone_reach(E1, E2, TWO, b.pad1 - 1 - s0) : 0;                // the block's widest cone
+        sr_pass_window(kreach<TWO, E1, E2>(pen, s0 + B - 1, b.begin), TIGHT ? 1 : pen.scope + 1, b.plen, b.tlen, b.shift, CONE,
+                       CONE ? b.kend : 0, rb0, KGeo<B>::OWN, glo, ghi, nt);
     }
-    // (jmerge, jband, jbandown, nband and the second prefix sum are what is left of two round-4 experiments that stayed off,
-    // merged tail tiles and the band-first tile order (profiles/r04_ab.log, DESIGN.md section 7): no tile is merged, the
-    // queue holds no band tile)
-    int incl = nt, hincl = 0;                          // prefix sums: tiles, aligners with a band tile
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64), h = __shfl_up(hincl, o, 64);
-        if (tid >= o) { incl += v; hincl += h; }
-    }
+    const int incl = kscan_jobs(nt);
     if (tid < BJ_MAX) {
         k_sh.jglo[tid] = glo; k_sh.jghi[tid] = ghi;
         k_sh.jgplo[tid] = pglo; k_sh.jgphi[tid] = pghi;
         k_sh.jtstart[tid + 1] = incl;
-        k_sh.jmerge[tid] = 0;
-        k_sh.jband[tid] = INT_MAX / 2;
-#pragma unroll
-        for (int j = 0; j < B; j++) { k_sh.jak[j][tid] = 0; k_sh.jreach[j][tid] = 0; }
     }
-    if (tid == 0) k_sh.jtstart[0] = 0;
-    if (tid == 63) { k_sh.nband = hincl; k_sh.total_tiles = incl + hincl; k_sh.next_tile = NT / 64; if (BASE) k_sh.base_tiles += (unsigned long long)incl; }
-    k_sh.cells_l[tid] += (unsigned long long)cells;      // (tid < 64)
+    // (the queue's start as an opaque copy: as a plain constant it was kept in a register across the pass loop, spilled, and
+    //  reloaded here, a memory round trip for a literal)
+    if (tid == 0) { k_sh.jtstart[0] = 0; k_sh.next_tile = (int)kopaque_v((unsigned)(NT / 64)); }
+    if (tid == BJ_MAX - 1) { k_sh.total_tiles = incl; if (BASE) k_sh.base_tiles += (unsigned long long)incl; }
     kprio_epoch();
 }
 
@@ -140,7 +152,7 @@ __device__ __forceinline__ void blk_pass(const KRows<OT, ST> &R, int s0, const S
     const int tid = threadIdx.x;
     if (setup) {
         const unsigned long long tsu0 = KTICK();
-        if (tid < 64) blk_setup<TWO, NT, B, E1, E2, RING && KTIGHT_OF(OT, ST, B, X), BASE>(s0, pen, njobs);
+        if (tid < 64) blk_setup<TWO, NT, B, E1, E2, RING && KTIGHT_OF(OT, ST, B, X), BASE>(s0, pen, njobs, (int)kopaque_v((unsigned)tid));
         __syncthreads();
         if (PROF && threadIdx.x == 0) k_sh.t_setup += KTICK() - tsu0;
     }
@@ -149,17 +161,10 @@ __device__ __forceinline__ void blk_pass(const KRows<OT, ST> &R, int s0, const S
     const int slot0 = kslots(R, s0);
     // Tiles differ in cost (extension loops, edge tiles): every wave takes its first tile by index and the following
     // ones from a queue, so that the pass ends when the work does and not when the unluckiest wave's share does.
-    const int nband = RFL(k_sh.nband);
     for (int t = (tid >> 6); t < total;) {
-        int lo, ti;
-        if (t < nband) { lo = RFL(k_sh.jbandown[t]); ti = RFL(k_sh.jband[lo]); }      // the band tiles first
-        else {
-            const int r = t - nband;
-            int hi = njobs; lo = 0;                 // last aligner with jtstart <= r (wave-uniform; jtstart counts the tiles but the band tile)
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (RFL(k_sh.jtstart[mid]) <= r) lo = mid; else hi = mid; }
-            ti = r - RFL(k_sh.jtstart[lo]);
-            ti += (ti >= RFL(k_sh.jband[lo])) ? 1 : 0;
-        }
+        int hi = njobs, lo = 0;                     // last aligner with jtstart <= t (wave-uniform)
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (RFL(k_sh.jtstart[mid]) <= t) lo = mid; else hi = mid; }
+        const int ti = t - RFL(k_sh.jtstart[lo]);
         blk_tile_any<OT, TWO, B, E1, E2, false, X, OE1, ST, RING>(R, s0, slot0, pen, lo, ti, lo, row_ld, row_st);
         int nx = 0;
         if ((tid & 63) == 0) nx = atomicAdd(&k_sh.next_tile, 1);

@@ -1,5 +1,6 @@
 // sr_blk_rows.inc -- blocked kernel (sr_align_blk.inc), part 1: the kernel's LDS state (KShared), row storage (KRows),
 // row addressing, row loads and stores, DPP lane helpers and the tile geometry (KGeo).
+#include "sr_pass_rule.h"       // tile geometry and pass tables shared with the host twin
 #define SR_ORI_B 16                // levels per pass of the in-kernel orientation (default orientation penalties; round 4: 8 -> 16)
 #define SR_KB_MAX 10               // deepest block any alignment instance of this build computes per pass (static LDS tables)
 #define KB_LV (SR_ORI_B > SR_KB_MAX ? SR_ORI_B : SR_KB_MAX)      // levels of the per-level range / reach tables (orientation blocks may be deeper)
@@ -10,10 +11,9 @@
 
 struct KShared {
     int jklo[KB_LV][BJ_MAX + 2], jkhi[KB_LV][BJ_MAX + 2];     // (+2: the aligners of an I/D recompute pass)
-    int jak[KB_MAX][BJ_MAX], jreach[KB_LV][BJ_MAX];
+    alignas(8) int jak[KB_MAX][BJ_MAX];                       // (8-byte aligned: the control lanes read a segment's two aligners as a pair)
+    int jreach[KB_LV][BJ_MAX];
     int jtstart[BJ_MAX + 1], jglo[BJ_MAX + 2], jghi[BJ_MAX + 2];
-    int jmerge[BJ_MAX];                                // blk_setup: forward aligner of a segment: 1 + index of the tile that also carries the reverse aligner's last tile (0: none)
-    int jband[BJ_MAX], jbandown[BJ_MAX], nband;        // band-first tile order (blk_setup): an aligner's tile over diagonal 0, the aligners that have one
     unsigned newmask;                                  // segments that entered phase 2 in this pass
     int rt_n0, rt_total;                               // recompute pass: tiles of its first aligner, of both
     int jgplo[BJ_MAX + 2], jgphi[BJ_MAX + 2];                  // groups the previous block of the aligner covered (U row validity)
@@ -263,6 +263,7 @@ __device__ __forceinline__ int row16_max_nn(int v) {
 template <int B> struct KGeo {
     static constexpr int HL = B <= 5 ? 2 : (B + 3) / 4;
     static constexpr int OWN = 64 - 2 * HL;              // owned 4-diagonal groups per tile
+    static_assert(OWN == sr_pass_own(B), "sr_pass_rule.h: the host twin of the pass tables counts tiles with the same geometry");
 };
 
 // (window reads, ffs_sym, min3u, lanes_or_zero: sr_dev_common.h)

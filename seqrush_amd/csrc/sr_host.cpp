@@ -27,6 +27,7 @@
 #include "sr_base_cone.h"
 #include "sr_mirror_rule.h"
 #include "sr_prio_rule.h"
+#include "sr_pass_rule.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -2939,6 +2940,47 @@ extern "C" int sr_iterative_stop_host(const uint64_t *counts, uint64_t nchecks, 
 // diagonals either side of the end diagonal that a level with `levels_left` levels to go keeps; < 0: none
 extern "C" int sr_base_cone_reach(int e1, int e2, int two, int levels_left) {
     return sr_cone_reach(e1, e2, two != 0, levels_left);
+}
+
+// host twin of the blocked kernel's pass tables (sr_pass_rule.h, blk_setup of sr_blk_pass.inc), organised as the kernel is: the
+// per-level tables by (aligner, level) lanes in steps of SR_PASS_LANES / B aligners, the per-aligner ones from the block's
+// first and last level, then the tile prefix.  pen6 = x, o1, e1, o2, e2, two; jobs = njobs records of SR_PASS_JOB_INTS ints
+// (active, begin component, plen, tlen, shift, kend, lj); base: the aligners are base cases (ranges and window cut to the cone
+// of lj).  klo / khi: [B][njobs], written for active aligners only, like the kernel's; cells / ccells: per-aligner sums of the
+// unclipped / clipped ranges (added to what the arrays hold); glo / ghi / nt per aligner; tstart[njobs + 1]: the prefix.
+// Returns the steps the lanes took, < 0 for arguments no instance has.
+#define SR_PASS_JOB_INTS 7
+extern "C" int sr_pass_tile_own(int B) { return sr_pass_own(B); }
+extern "C" int sr_pass_tables_host(const int *pen6, int scope, int B, int tight, int base, int s0, int njobs, const int *jobs,
+                                   int *klo, int *khi, long long *cells, long long *ccells, int *glo, int *ghi, int *nt, int *tstart) {
+    if (!pen6 || !jobs || B < 1 || B > SR_PASS_LANES || njobs < 0 || pen6[2] < 1 || (pen6[5] && pen6[4] < 1)) return -1;
+    const int o1 = pen6[1], e1 = pen6[2], o2 = pen6[3], e2 = pen6[4];
+    const bool two = pen6[5] != 0, cone = base != 0;
+    const int steps = sr_pass_steps(njobs, B);
+    for (int st = 0; st < steps; st++)
+        for (int lane = 0; lane < SR_PASS_LANES; lane++) {
+            int a, j;
+            if (!sr_pass_lane(lane, st, B, a, j) || a >= njobs) continue;
+            const int *b = jobs + (size_t)a * SR_PASS_JOB_INTS;
+            if (!b[0]) continue;
+            const int rb = cone ? sr_cone_reach(e1, e2, two, b[6] - 1 - (s0 + j)) : 0;
+            int lo, hi, c, cc;
+            sr_pass_level(sr_pass_reach(o1, e1, o2, e2, two, s0 + j, b[1] == SR_C_M), b[2], b[3], cone, cone ? b[5] : 0, rb, lo, hi, c, cc);
+            klo[(size_t)j * njobs + a] = lo; khi[(size_t)j * njobs + a] = hi;
+            cells[a] += c; ccells[a] += cc;
+        }
+    tstart[0] = 0;
+    for (int a = 0; a < njobs; a++) {
+        const int *b = jobs + (size_t)a * SR_PASS_JOB_INTS;
+        glo[a] = 0; ghi[a] = -1; nt[a] = 0;
+        if (b[0]) {
+            const int rb0 = cone ? sr_cone_reach(e1, e2, two, b[6] - 1 - s0) : 0;
+            sr_pass_window(sr_pass_reach(o1, e1, o2, e2, two, s0 + B - 1, b[1] == SR_C_M), tight ? 1 : scope + 1, b[2], b[3], b[4], cone,
+                           cone ? b[5] : 0, rb0, sr_pass_own(B), glo[a], ghi[a], nt[a]);
+        }
+        tstart[a + 1] = tstart[a] + nt[a];
+    }
+    return steps;
 }
 
 // canonical labels of a node array: the minimum element of each set (what sr_ctx_download_labels returns)
