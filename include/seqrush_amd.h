@@ -771,6 +771,56 @@ void sr_variants_free(sr_variants *v);
  * those whose GT is not `.`. */
 int sr_variants_vcf(const sr_variants *v, const char *const *names, char **text);
 
+/* -------- extending a graph (`--extend FILE.gfa`) -------------------------------------------------
+ * Adds sequences to an existing GFA without realigning the pairs it was built from.  A component of this library's
+ * union-find is a set of bases and a node offset of an induced graph is exactly one component, so a GFA whose paths spell
+ * their sequences IS the partition that produced it: uniting, per node offset, all bases that visit it restores the
+ * partition, and only the pairs that touch a new sequence are left to align.  Any GFA with S / L / P lines and numeric
+ * node ids, as the parser of sr_sort_gfa reads it, can be extended, whoever built it.
+ * Old sequences = the oriented sequences of the P lines in file order, named by their paths (a reverse handle reads its
+ * node reversed and complemented by the project's rule).  Merged set = the old sequences, then the records of new_seqs
+ * (NULL or n = 0: none).  SR_ERR_INVALID, naming the offender: a name that occurs twice (path / path or path / record), a
+ * path without steps, a step on a missing node, a visited node without a sequence (`*`), a GFA without a P line.  A node
+ * no path visits is ignored, and so are the L lines: induction re-derives the edges.
+ * Seed: with all steps of all paths back to back, every base a step spells is united with the base that the node's first
+ * step (smallest index) spells at the same node offset (csrc/sr_extend_rule.h).  -k does not apply to it.
+ * With -x none and fixed -k, -S, -d, extending the graph of the first m sequences by the other n - m gives the labels and
+ * the GFA bytes of building all n at once; in general, those of sr_ctx_load_pairs over the merged set with the old pair
+ * list followed by the new one.  The equality needs paths that spell their sequences (known limit).
+ * device >= 0: the old sequences are spelled by HIP kernels on that device (sr_extend.hip); SR_EXTEND_DEVICE_HOST: plain
+ * loops.  Both give the same bytes.  The plan owns the merged sr_seqset (sr_extend_plan_seqs: valid until the plan is
+ * freed) and the step / offset / node-length tables of the seed.  Every limit of a normal load applies to the merged set;
+ * 2^30 nodes, 2^31 steps or 2^39 old bases: SR_ERR_UNSUPPORTED. */
+#define SR_EXTEND_DEVICE_HOST (-1)
+typedef struct sr_extend_plan sr_extend_plan;
+typedef struct {
+    uint64_t old_paths, old_bases, old_steps, new_sequences;
+    uint64_t pairs_before, pairs_after;         /* the enumeration over the merged set; what the filter kept (before sharding) */
+    uint64_t unions_attempted, unions_joined;   /* of the last seed: bases not spelled by their node's first step; set joins */
+    uint64_t spell_us, seed_us;                 /* hipEvents (spell_us on the host twin: a host clock) */
+} sr_extend_stats;
+int sr_extend_plan_gfa(const char *gfa_in, const sr_seqset *new_seqs, int device, sr_extend_plan **out);
+void sr_extend_plan_free(sr_extend_plan *plan);
+const sr_seqset *sr_extend_plan_seqs(const sr_extend_plan *plan);
+uint32_t sr_extend_plan_n_old(const sr_extend_plan *plan);
+/* the pair filter (pure host code): drops every (q, t) with q < n_old and t < n_old, keeps the order of the rest; an index
+ * outside the merged set is SR_ERR_INVALID.  Both arrays sr_free. */
+int sr_extend_pair_list(const sr_extend_plan *plan, const uint32_t *q, const uint32_t *t, uint64_t count, uint32_t **q_out,
+                        uint32_t **t_out, uint64_t *count_out);
+/* sr_ctx_load of the plan's merged set with the filter applied to what the enumeration (or the tree: selection on the
+ * device) gives under p, then the seed tables are uploaded and the seed is enqueued on the context's stream (no run).  The
+ * plan may be freed afterwards; build the GFA with sr_extend_plan_seqs or an equal sr_seqset.  On such a context
+ * sr_ctx_reset_uf means init + seed; every other context behaves as before.  A plan without new sequences is
+ * SR_ERR_INVALID: there is nothing to align. */
+int sr_ctx_load_extend(sr_ctx *c, const sr_extend_plan *plan, const sr_params *p);
+/* the host twin of the seed (no device) on a node array of n >= 2 * total length of the merged set + 2 entries in the
+ * SeqRush::new state (sr_uf_init_host), through sr_uf_unite_host; stats (or NULL): [0] unions attempted, [1] joined */
+int sr_extend_seed_host(const sr_extend_plan *plan, uint64_t *nodes, uint64_t n, uint64_t stats[2]);
+/* the plan's counts alone (pairs, unions and seed_us 0) */
+int sr_extend_plan_stats(const sr_extend_plan *plan, sr_extend_stats *out);
+/* the same with the pair counts of the load and the counters and time of the last seed; syncs the context's stream */
+int sr_ctx_extend_stats(sr_ctx *c, sr_extend_stats *out);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

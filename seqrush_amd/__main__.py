@@ -71,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--vcf-ref", default=None, metavar="NAME", help="the reference path (default: the first path)")
     ap.add_argument("--vcf-max-allele-len", type=int, default=None, metavar="N",
                     help="traversals with a longer allele or reference span are skipped (default 10000; 0: no limit)")
+    ap.add_argument("--extend", default=None, metavar="FILE.gfa",
+                    help="add the sequences of -s to this graph: its paths are kept as they are and only the pairs that touch a "
+                         "new sequence are aligned")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1,
@@ -137,6 +140,13 @@ def main(argv=None):
     except SeqRushError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 1
+    if ns.extend is not None:
+        # before any device work: each of these would compose in principle, none is verified
+        for on, what in ((ns.iterative, "--iterative"), (ns.paf is not None, "-p"), (ns.patch_inversions, "--patch-inversions"),
+                         (ns.gpus > 1, "--gpus N > 1")):
+            if on:
+                print(f"Error: --extend cannot be combined with {what}", file=sys.stderr)
+                return 1
     if ns.gpus > 1 and "RANK" not in os.environ:
         # start one process per GPU BEFORE anything here touches the GPU (never exec from a process that has)
         port = os.environ.get("MASTER_PORT", str(29400 + os.getpid() % 2000))
@@ -160,7 +170,7 @@ def main(argv=None):
                 viz_mode=ns.viz_mode or "path", viz_depth_max=ns.viz_depth_max or 4, growth=ns.growth,
                 growth_permutations=ns.growth_permutations or 1000,
                 growth_seed=9399220 if ns.growth_seed is None else ns.growth_seed, growth_group_by=ns.growth_group_by or "path", vcf=ns.vcf, vcf_ref=ns.vcf_ref,
-                vcf_max_allele_len=10000 if ns.vcf_max_allele_len is None else ns.vcf_max_allele_len)
+                vcf_max_allele_len=10000 if ns.vcf_max_allele_len is None else ns.vcf_max_allele_len, extend=ns.extend)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

@@ -49,6 +49,8 @@ EXPORTS = [
     "sr_replay_record_ints", "sr_replay_transpose_host", "sr_replay_match_host",
     "sr_ctx_prio_timeline", "sr_tile_prio_role_host", "sr_tile_prio_epoch_shift",
     "sr_pass_tables_host", "sr_pass_tile_own",
+    "sr_extend_plan_gfa", "sr_extend_plan_free", "sr_extend_plan_seqs", "sr_extend_plan_n_old", "sr_extend_pair_list",
+    "sr_ctx_load_extend", "sr_extend_seed_host", "sr_extend_plan_stats", "sr_ctx_extend_stats",
 ]
 
 
@@ -187,6 +189,12 @@ class VariantsC(C.Structure):
                 ("allele_off", C.POINTER(C.c_uint64)), ("alleles", C.POINTER(C.c_char)), ("gt", C.POINTER(C.c_int32)),
                 ("ref_seq", C.POINTER(C.c_char)), ("variant", C.c_int32), ("reserved", C.c_int32),
                 ("variants_us", C.c_uint64), ("kernel_us", C.c_uint64 * 6)]
+
+
+class ExtendStatsC(C.Structure):
+    """sr_extend_stats (include/seqrush_amd.h, extending a graph)"""
+    _fields_ = [(f, C.c_uint64) for f in ("old_paths", "old_bases", "old_steps", "new_sequences", "pairs_before", "pairs_after",
+                                          "unions_attempted", "unions_joined", "spell_us", "seed_us")]
 
 
 class AlignmentsC(C.Structure):
@@ -369,6 +377,16 @@ def load():
     L.sr_replay_record_ints.argtypes = []
     L.sr_replay_transpose_host.argtypes = [PI, PI]; L.sr_replay_transpose_host.restype = None
     L.sr_replay_match_host.argtypes = [PI, i32, PI, i32, i32, PI]
+    PES = C.POINTER(ExtendStatsC)
+    L.sr_extend_plan_gfa.argtypes = [C.c_char_p, PS, i32, C.POINTER(vp)]
+    L.sr_extend_plan_free.argtypes = [vp]; L.sr_extend_plan_free.restype = None
+    L.sr_extend_plan_seqs.argtypes = [vp]; L.sr_extend_plan_seqs.restype = PS
+    L.sr_extend_plan_n_old.argtypes = [vp]; L.sr_extend_plan_n_old.restype = C.c_uint32
+    L.sr_extend_pair_list.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, PU32P, PU32P, C.POINTER(u64)]
+    L.sr_ctx_load_extend.argtypes = [vp, vp, PP]
+    L.sr_extend_seed_host.argtypes = [vp, C.POINTER(u64), u64, C.POINTER(u64)]
+    L.sr_extend_plan_stats.argtypes = [vp, PES]
+    L.sr_ctx_extend_stats.argtypes = [vp, PES]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

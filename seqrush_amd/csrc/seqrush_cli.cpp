@@ -83,13 +83,13 @@ static void usage() {
                     "       [--bin bins.tsv [--bin-width W | --bin-count N]] [--viz graph.png [--viz-width N] [--viz-path-height H]\n"
                     "       [--viz-path-gap G] [--viz-mode path|strand|depth] [--viz-depth-max D]]\n"
                     "       [--growth growth.tsv [--growth-permutations N] [--growth-seed N] [--growth-group-by path|sample|haplotype]]\n"
-                    "       [--vcf graph.vcf [--vcf-ref NAME] [--vcf-max-allele-len N]]\n"
+                    "       [--vcf graph.vcf [--vcf-ref NAME] [--vcf-max-allele-len N]] [--extend graph.gfa]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave", stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt, vcf_out, vcf_opt, vcf_ref;
+                aligner = "allwave", extend_in, stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt, vcf_out, vcf_opt, vcf_ref;
     sr_variant_params vcp;
     sr_variant_params_default(&vcp);
     sr_growth_params gp;
@@ -211,6 +211,7 @@ int main(int argc, char **argv) {
             if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: %s needs a non-negative integer, got '%s'\n", a.c_str(), v); return 1; }
             vcp.max_allele_len = n;
         }
+        else if (a == "--extend") extend_in = val("--extend");
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
             const char *v = val("--inversion-min-size");
@@ -252,6 +253,13 @@ int main(int argc, char **argv) {
                 inv_join, inv_min ? inv_min : 2ULL * (unsigned long long)(k > 0 ? k : 0));
         return 1;
     }
+    // --extend: each of these would compose in principle, none is verified (one process, one GPU: the --gpus N of this front
+    // end is --shard / --labels-out / --labels-in)
+    if (!extend_in.empty() && (iterative || !paf_in.empty() || patch_inv || shard_count > 1 || !labels_out.empty() || !labels_in.empty())) {
+        fprintf(stderr, "Error: --extend cannot be combined with %s\n",
+                iterative ? "--iterative" : !paf_in.empty() ? "-p" : patch_inv ? "--patch-inversions" : "--gpus N > 1");
+        return 1;
+    }
     if (shard_count > 1 && labels_out.empty()) {
         fprintf(stderr, "Error: --shard %u/%u aligns a part of the pair list only: give --labels-out and merge the parts with --labels-in "
                         "(a graph of one shard would be silently incomplete)\n", shard_rank, shard_count);
@@ -278,6 +286,20 @@ int main(int argc, char **argv) {
     std::vector<const char *> names;
     for (auto &s : seqs) { bases += s.data; offsets.push_back(bases.size()); names.push_back(s.id.c_str()); }
     sr_seqset set{(uint32_t)seqs.size(), (const uint8_t *)bases.data(), offsets.data(), names.data()};
+    // --extend: the paths of the graph are spelled back into sequences (on the device) and -s holds only the new ones; from
+    // here on `set` is the merged set, which the plan owns
+    sr_extend_plan *plan = nullptr;
+    size_t n_seqs = seqs.size(), n_bases = bases.size();
+    if (!extend_in.empty()) {
+        std::ifstream gf(extend_in, std::ios::binary);
+        if (!gf) { fprintf(stderr, "Error: cannot read %s\n", extend_in.c_str()); return 1; }
+        std::stringstream ss;
+        ss << gf.rdbuf();
+        if (sr_extend_plan_gfa(ss.str().c_str(), &set, device, &plan)) { fprintf(stderr, "Error: %s\n", sr_last_error()); return 1; }
+        set = *sr_extend_plan_seqs(plan);
+        printf("Extending %s: %u paths\n", extend_in.c_str(), sr_extend_plan_n_old(plan));
+        n_seqs = set.n; n_bases = (size_t)set.offsets[set.n];
+    }
     sr_params p;
     sr_default_params(&p);
     if (sr_parse_scores(scores.c_str(), &p) || sr_parse_orientation_scores(ori.c_str(), &p) ||
@@ -288,17 +310,17 @@ int main(int argc, char **argv) {
     p.min_match_len = (uint64_t)k; p.max_divergence = max_div; p.device = device; p.canonical_labels = 1;
     p.shard_rank = shard_rank; p.shard_count = shard_count;
     // what a part file must agree on: the sequences (bytes and boundaries) and everything that decides pairs and unions
-    uint64_t input_hash = fnv1a(bases.data(), bases.size());
+    uint64_t input_hash = fnv1a(bases.data(), bases.size());      // (shard runs only: never with --extend)
     input_hash = fnv1a(offsets.data(), offsets.size() * 8, input_hash);
     {
         const std::string cfg = scores + "|" + ori + "|" + sparsify + "|" + std::to_string(k) + "|" + std::to_string(max_div);
         input_hash = fnv1a(cfg.data(), cfg.size(), input_hash);
     }
-    printf("Building graph with %zu sequences (total length: %zu)\n", seqs.size(), bases.size());
-    if (!iterative) printf("Total sequence pairs: %zu (sparsification: %s)\n", seqs.size() * seqs.size(), sparsify.c_str());
+    printf("Building graph with %zu sequences (total length: %zu)\n", n_seqs, n_bases);
+    if (!iterative) printf("Total sequence pairs: %zu (sparsification: %s)\n", n_seqs * n_seqs, sparsify.c_str());
     // one resident context: load (or PAF replay) -> align -> unite -> graph induction, all on the device
     sr_ctx *ctx = nullptr;
-    auto die = [&]() { fprintf(stderr, "Error: %s\n", sr_last_error()); if (ctx) sr_ctx_destroy(ctx); return 1; };
+    auto die = [&]() { fprintf(stderr, "Error: %s\n", sr_last_error()); if (ctx) sr_ctx_destroy(ctx); sr_extend_plan_free(plan); return 1; };
     if (sr_ctx_create(device, &ctx)) return die();
     if (!labels_in.empty()) {                                // merge run: no pairs of its own, the forests come from files
         if (sr_ctx_load_pairs(ctx, &set, &p, nullptr, nullptr, 0)) return die();
@@ -360,6 +382,10 @@ int main(int argc, char **argv) {
             if (sr_write_paf(al, &set, paf_out.c_str())) { sr_alignments_free(al); return die(); }
             sr_alignments_free(al);
         }
+    } else if (plan) {                                       // --extend: only the pairs that touch a new sequence, seeded union-find
+        if (sr_ctx_load_extend(ctx, plan, &p)) return die();
+        printf("Extending %u paths by %u sequences: %llu pairs to align\n", sr_extend_plan_n_old(plan), set.n - sr_extend_plan_n_old(plan),
+               (unsigned long long)sr_ctx_num_pairs(ctx));
     } else {
         if (sr_ctx_load(ctx, &set, &p)) return die();
         if (patch_inv) {
@@ -384,6 +410,15 @@ int main(int argc, char **argv) {
         }
     }
     if (sr_ctx_sync(ctx)) return die();
+    if (plan && verbose) {
+        sr_extend_stats es;
+        if (sr_ctx_extend_stats(ctx, &es)) return die();
+        printf("Extend: %llu paths %llu bases %llu steps + %llu sequences, pairs %llu of %llu, unions %llu of %llu, spell_us=%llu seed_us=%llu\n",
+               (unsigned long long)es.old_paths, (unsigned long long)es.old_bases, (unsigned long long)es.old_steps,
+               (unsigned long long)es.new_sequences, (unsigned long long)es.pairs_after, (unsigned long long)es.pairs_before,
+               (unsigned long long)es.unions_joined, (unsigned long long)es.unions_attempted, (unsigned long long)es.spell_us,
+               (unsigned long long)es.seed_us);
+    }
     if (patch_inv) {
         sr_inv_stats ist;
         if (sr_ctx_inversion_stats(ctx, &ist)) return die();
@@ -422,6 +457,7 @@ int main(int argc, char **argv) {
                (unsigned long long)cs[4], (unsigned long long)cs[5], (unsigned long long)cs[6]);
     }
     sr_ctx_destroy(ctx);
+    sr_extend_plan_free(plan);                               // (`set` is not read below)
     std::ofstream o(output, std::ios::binary);
     o << gfa;
     std::vector<std::string> pnames;                         // names of the P lines, as the library's parser reads them

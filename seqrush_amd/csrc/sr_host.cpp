@@ -28,6 +28,8 @@
 #include "sr_mirror_rule.h"
 #include "sr_prio_rule.h"
 #include "sr_pass_rule.h"
+#include "sr_extend.h"
+#include "sr_extend_rule.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -328,6 +330,11 @@ struct sr_ctx {
     uint64_t inv_join_stats[4] = {0, 0, 0, 0};
     std::chrono::steady_clock::time_point t_first_kernel;      // host clock just before a load's first kernel (inv_patch_pass)
     int inv_ev_used = 0;
+    // --extend (sr_ctx_load_extend): the seed's tables on the device, its counters and event pair; sr_ctx_reset_uf re-seeds
+    bool ext_loaded = false;
+    SrExtendSeedArgs ext{};
+    sr_extend_stats ext_stats{};
+    hipEvent_t ext_ev[2] = {nullptr, nullptr};
 };
 
 static int dev_alloc(sr_ctx *c, void **p, size_t bytes) {
@@ -360,6 +367,7 @@ static void free_dev(sr_ctx *c) {
     for (uint64_t &v : c->inv_join_stats) v = 0;
     c->inv_ev_used = 0;
     if (c->inv_al) { sr_alignments_free(c->inv_al); c->inv_al = nullptr; }
+    c->ext_loaded = false; c->ext = SrExtendSeedArgs{}; c->ext_stats = sr_extend_stats{};
 }
 
 // event pair `idx` of kind `kind` (created on first use)
@@ -395,6 +403,7 @@ extern "C" void sr_ctx_destroy(sr_ctx *c) {
     for (int k = 0; k < 5; k++)
         for (auto &e : c->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto &e : c->inv_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (hipEvent_t e : c->ext_ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -786,7 +795,8 @@ static int tree_selection(sr_ctx *c, const sr_params *p, const SeqDev &sd, std::
 
 // ordered pair list of this rank + what follows from it: DP cells, worst-case CIGAR reserve per pair, divergence thresholds
 static int build_pair_list(sr_ctx *c, const sr_params *p, const SeqDev &sd, const uint32_t *eq, const uint32_t *et, uint64_t ecount,
-                           bool explicit_pairs, std::vector<int32_t> &max_score, uint64_t *max_reserve, bool iterative = false) {
+                           bool explicit_pairs, std::vector<int32_t> &max_score, uint64_t *max_reserve, bool iterative = false,
+                           uint32_t ext_n_old = 0) {
     const uint32_t n = c->n;
     if (iterative) {                  // --iterative: expanded tree entries, then expanded random entries (explicit list, no shard)
         std::vector<uint8_t> sel;
@@ -811,6 +821,14 @@ static int build_pair_list(sr_ctx *c, const sr_params *p, const SeqDev &sd, cons
         std::vector<uint8_t> sel;
         if (p->sparsify_kind == SR_SPARSE_TREE && n > 1) { const int r = tree_selection(c, p, sd, sel); if (r) return r; }
         enumerate_pairs(n, *p, sel.empty() ? nullptr : sel.data(), c->pair_q, c->pair_t);
+        if (ext_n_old) {              // --extend: the pairs between two old sequences were aligned when the input graph was built
+            c->ext_stats.pairs_before = c->pair_q.size();
+            size_t w = 0;
+            for (size_t i = 0; i < c->pair_q.size(); i++)
+                if (sr_ext_keep_pair(c->pair_q[i], c->pair_t[i], ext_n_old)) { c->pair_q[w] = c->pair_q[i]; c->pair_t[w] = c->pair_t[i]; w++; }
+            c->pair_q.resize(w); c->pair_t.resize(w);
+            c->ext_stats.pairs_after = w;
+        }
     }
     c->total_pairs_all_ranks = c->pair_q.size();
     shard_pairs(c->len, p->shard_rank, p->shard_count, c->pair_q, c->pair_t);
@@ -1384,7 +1402,7 @@ static void write_report(sr_ctx *c, const PackedSeqs &pk, const SrPen &pen, cons
 }
 
 static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const uint32_t *eq, const uint32_t *et,
-                     uint64_t ecount, bool explicit_pairs, bool iterative = false, bool forced_strand = false) {
+                     uint64_t ecount, bool explicit_pairs, bool iterative = false, bool forced_strand = false, uint32_t ext_n_old = 0) {
     if (!c || !seqs || !p) return fail(SR_ERR_INVALID, "null argument");
     if (seqs->n == 0) return fail(SR_ERR_INVALID, "no sequences");
     HIPCHK(hipSetDevice(c->device));
@@ -1401,7 +1419,7 @@ static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const
     if ((r = upload_sequences(c, seqs, pk, sd))) return r;
     Plan pl;
     std::vector<int32_t> max_score;
-    if ((r = build_pair_list(c, p, sd, eq, et, ecount, explicit_pairs, max_score, &pl.max_reserve, iterative))) return r;
+    if ((r = build_pair_list(c, p, sd, eq, et, ecount, explicit_pairs, max_score, &pl.max_reserve, iterative, ext_n_old))) return r;
     const uint32_t np = (uint32_t)c->pair_q.size();
     if ((r = plan_kernel(c, pk, pen, ori, maxlen, np, pl))) return r;
     if ((r = plan_workspace(c, pen, ori, maxlen, pl))) return r;
@@ -1448,10 +1466,65 @@ extern "C" int sr_ctx_orientation_scores(sr_ctx *c, int32_t *fwd, int32_t *rev) 
 extern "C" uint32_t sr_ctx_num_batches(const sr_ctx *c) { return (c && c->loaded) ? (uint32_t)c->batch_first.size() - 1 : 0; }
 extern "C" const char *sr_ctx_workspace_report(const sr_ctx *c) { return c ? c->workspace_report.c_str() : ""; }
 
+// --extend: the seed of the loaded plan on the context's stream, hipEvents around it
+static int enqueue_extend_seed(sr_ctx *c) {
+    for (hipEvent_t &e : c->ext_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipMemsetAsync(c->ext.counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipEventRecord(c->ext_ev[0], c->stream));
+    const int r = srk_extend_seed(&c->ext, c->stream);
+    if (r) return fail(SR_ERR_HIP, std::string("extend seed launch failed: ") + hipGetErrorString((hipError_t)r));
+    HIPCHK(hipEventRecord(c->ext_ev[1], c->stream));
+    return SR_OK;
+}
+
 extern "C" int sr_ctx_reset_uf(sr_ctx *c) {
     if (!c || !c->loaded) return fail(SR_ERR_INVALID, "context not loaded");
     HIPCHK(hipSetDevice(c->device));
     if (srk_uf_init(c->d_nodes, c->total_len, c->uf_size, c->stream)) return fail(SR_ERR_HIP, "uf init launch failed");
+    if (c->ext_loaded) return enqueue_extend_seed(c);      // a context of sr_ctx_load_extend starts from the input graph's partition
+    return SR_OK;
+}
+
+// sr_ctx_load of the plan's merged set with the pair filter, then the seed tables and the seed (include/seqrush_amd.h)
+extern "C" int sr_ctx_load_extend(sr_ctx *c, const sr_extend_plan *plan, const sr_params *p) {
+    if (!c || !plan || !p) return fail(SR_ERR_INVALID, "null argument");
+    if (plan->n_new == 0) return fail(SR_ERR_INVALID, "extend: no new sequences: there is nothing to align");
+    int r = load_impl(c, &plan->merged, p, nullptr, nullptr, 0, false, false, false, plan->n_old);
+    if (r) return r;
+    if (plan->old_bases > c->total_len || plan->S == 0 || plan->sinc[plan->S - 1] != plan->old_bases)
+        return fail(SR_ERR_INVALID, "extend: the plan's tables do not match its merged set");
+    const uint64_t before = c->ext_stats.pairs_before, after = c->ext_stats.pairs_after;
+    sr_extend_plan_stats(plan, &c->ext_stats);
+    c->ext_stats.pairs_before = before; c->ext_stats.pairs_after = after;
+    void *d_steps = nullptr, *d_len = nullptr, *d_sinc = nullptr, *d_anchor = nullptr, *d_counts = nullptr;
+    if ((r = dev_alloc(c, &d_steps, (size_t)plan->S * 4)) || (r = dev_alloc(c, &d_len, (size_t)plan->V * 4)) ||
+        (r = dev_alloc(c, &d_sinc, (size_t)plan->S * 8)) || (r = dev_alloc(c, &d_anchor, (size_t)plan->V * 4)) ||
+        (r = dev_alloc(c, &d_counts, 2 * sizeof(unsigned long long)))) { c->loaded = false; return r; }
+    c->loaded = false;                                       // until the tables are in place
+    HIPCHK(hipMemcpyAsync(d_steps, plan->steps.data(), (size_t)plan->S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_len, plan->len.data(), (size_t)plan->V * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_sinc, plan->sinc.data(), (size_t)plan->S * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(d_anchor, 0xff, (size_t)plan->V * 4, c->stream));
+    c->ext.steps = (const uint32_t *)d_steps; c->ext.len = (const uint32_t *)d_len; c->ext.sinc = (const uint64_t *)d_sinc;
+    c->ext.anchor = (uint32_t *)d_anchor; c->ext.S = plan->S; c->ext.V = plan->V; c->ext.bases = plan->old_bases;
+    c->ext.nodes = c->d_nodes; c->ext.counts = (unsigned long long *)d_counts; c->ext.error_flag = c->d_error;
+    if ((r = srk_extend_anchor(&c->ext, c->stream))) return fail(SR_ERR_HIP, std::string("extend anchor launch failed: ") + hipGetErrorString((hipError_t)r));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // (the plan's vectors may go away after this)
+    c->loaded = true; c->ext_loaded = true;
+    return enqueue_extend_seed(c);
+}
+
+extern "C" int sr_ctx_extend_stats(sr_ctx *c, sr_extend_stats *out) {
+    if (!c || !out || !c->loaded || !c->ext_loaded) return fail(SR_ERR_INVALID, "context was not loaded by sr_ctx_load_extend");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    unsigned long long cnt[2] = {0, 0};
+    HIPCHK(hipMemcpy(cnt, c->ext.counts, sizeof(cnt), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ext_ev[0], c->ext_ev[1]));
+    c->ext_stats.unions_attempted = cnt[0]; c->ext_stats.unions_joined = cnt[1];
+    c->ext_stats.seed_us = (uint64_t)(ms * 1000.0 + 0.5);
+    *out = c->ext_stats;
     return SR_OK;
 }
 

@@ -520,10 +520,12 @@ int sr_graph_parse_gfa(const char *text, SrGraph &g, std::vector<std::string> &n
             return sr_fail(SR_ERR_INVALID, "GFA: an L line names a missing segment");
         if (seen.insert(((uint64_t)a << 32) | b).second) g.edges.push_back({a, b});
     }
-    for (const auto &rp : raw_paths) {
+    for (size_t pi = 0; pi < raw_paths.size(); pi++) {
+        const auto &rp = raw_paths[pi];
         for (const auto &st : rp) {
             hnd h;
-            if (!map_h(st.first, (uint32_t)st.second, &h)) return sr_fail(SR_ERR_INVALID, "GFA: a P line names a missing segment");
+            if (!map_h(st.first, (uint32_t)st.second, &h))
+                return sr_fail(SR_ERR_INVALID, "GFA: a P line names a missing segment (path '" + names[pi] + "', segment " + std::to_string(st.first) + ")");
             g.steps.push_back(h);
         }
         g.path_off.push_back(g.steps.size());

@@ -14,7 +14,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, check, SeqRushError)
+                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, ExtendStatsC, check,
+                   SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
 
@@ -73,6 +74,7 @@ class Args:
     vcf: Optional[str] = None               # added: --vcf FILE: variant sites of the final GFA against one path as VCF
     vcf_ref: Optional[str] = None           # added: --vcf-ref NAME: the reference path (default: the first)
     vcf_max_allele_len: int = 10000         # added: --vcf-max-allele-len N (0: no limit)
+    extend: Optional[str] = None            # added: --extend FILE.gfa: add the sequences of -s to this graph
 
 
 @dataclasses.dataclass
@@ -287,6 +289,18 @@ class Context:
         check(self.L.sr_ctx_load_pairs(self._h, C.byref(seqset.c), C.byref(params.c),
                                        q.ctypes.data_as(C.POINTER(C.c_uint32)), t.ctypes.data_as(C.POINTER(C.c_uint32)),
                                        len(pairs)))
+
+    def load_extend(self, plan: "ExtendPlan", params: Params):
+        """--extend: the plan's merged set with only the pairs that touch a new sequence, and the union-find seeded with the
+        partition the input graph stands for (enqueued; reset_uf() on such a context means init + seed)"""
+        self.seqset = plan.seqset
+        check(self.L.sr_ctx_load_extend(self._h, plan._h, C.byref(params.c)))
+
+    def extend_stats(self) -> dict:
+        """sr_extend_stats of the loaded extend context (syncs the stream)"""
+        st = ExtendStatsC()
+        check(self.L.sr_ctx_extend_stats(self._h, C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in ExtendStatsC._fields_}
 
     def pairs(self):
         """this rank's (query, target) pair list after sparsification and sharding"""
@@ -1270,6 +1284,82 @@ class HostUnionFind:
         return out
 
 
+class ExtendPlan:
+    """Owned ``sr_extend_plan``: the paths of a GFA spelled back into sequences (device >= 0: on that GPU; -1: plain loops),
+    followed by the new records, and the tables that seed the union-find with the graph's partition."""
+
+    def __init__(self, gfa_text: str, new_records=(), device: int = -1):
+        self.L = _lib.load()
+        self._h = C.c_void_p()
+        new = new_records if isinstance(new_records, SeqSet) else SeqSet(list(new_records))
+        check(self.L.sr_extend_plan_gfa(gfa_text.encode(), C.byref(new.c) if new.n else None, device, C.byref(self._h)))
+        m = self.L.sr_extend_plan_seqs(self._h).contents
+        n = int(m.n)
+        off = [int(m.offsets[i]) for i in range(n + 1)]
+        raw = C.string_at(C.cast(C.byref(m, SeqSetC.bases.offset), C.POINTER(C.c_void_p))[0], off[n]) if off[n] else b""
+        self.n_old = int(self.L.sr_extend_plan_n_old(self._h))
+        self.records = [(m.names[i].decode(), raw[off[i]: off[i + 1]]) for i in range(n)]
+        self.seqset = SeqSet(self.records)          # a copy with the same bytes: what build_gfa() of a context reads
+
+    def stats(self) -> dict:
+        st = ExtendStatsC()
+        check(self.L.sr_extend_plan_stats(self._h, C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in ExtendStatsC._fields_}
+
+    def pair_list(self, pairs):
+        """the pair filter: the (query, target) pairs that touch a new sequence, in the order given"""
+        q = np.ascontiguousarray([a for a, _ in pairs] or [0], dtype=np.uint32)
+        t = np.ascontiguousarray([b for _, b in pairs] or [0], dtype=np.uint32)
+        PU = C.POINTER(C.c_uint32)
+        qo, to, cnt = PU(), PU(), C.c_uint64()
+        check(self.L.sr_extend_pair_list(self._h, q.ctypes.data_as(PU), t.ctypes.data_as(PU), len(pairs), C.byref(qo), C.byref(to),
+                                         C.byref(cnt)))
+        out = [(int(qo[i]), int(to[i])) for i in range(cnt.value)]
+        self.L.sr_free(C.cast(qo, C.c_void_p)); self.L.sr_free(C.cast(to, C.c_void_p))
+        return out
+
+    def close(self):
+        if self._h:
+            self.L.sr_extend_plan_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def extend_seed_host(plan: ExtendPlan, uf: "HostUnionFind") -> dict:
+    """the host twin of the seed on a HostUnionFind of the plan's merged set -> dict(unions_attempted, unions_joined)"""
+    st = (C.c_uint64 * 2)()
+    check(_lib.load().sr_extend_seed_host(plan._h, uf._p(uf.nodes), uf.n, st))
+    return dict(unions_attempted=int(st[0]), unions_joined=int(st[1]))
+
+
+def check_extend(args: "Args"):
+    """the refusals of --extend that need no device: each would compose in principle, none is verified"""
+    if not args.extend:
+        return
+    for on, what in ((args.iterative, "--iterative"), (args.paf is not None, "-p"), (args.patch_inversions, "--patch-inversions"),
+                     (args.gpus > 1 or args.shard_count > 1, "--gpus N > 1")):
+        if on:
+            raise SeqRushError(-6, f"--extend cannot be combined with {what}")
+
+
+def extend_report(st: dict) -> str:
+    """the -v line of --extend"""
+    return (f"Extend: {st['old_paths']} paths {st['old_bases']} bases {st['old_steps']} steps + {st['new_sequences']} sequences, "
+            f"pairs {st['pairs_after']} of {st['pairs_before']}, unions {st['unions_joined']} of {st['unions_attempted']}, "
+            f"spell_us={st['spell_us']} seed_us={st['seed_us']}")
+
+
 def uf_find(nodes: np.ndarray, x: int) -> int:
     nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
     return int(_lib.load().sr_uf_find(nodes.ctypes.data_as(C.POINTER(C.c_uint64)), len(nodes), x))
@@ -1279,7 +1369,8 @@ def uf_find(nodes: np.ndarray, x: int) -> int:
 class SeqRush:
     """Mirror of ``SeqRush`` (src/seqrush.rs:298-336, 433-458) over the device path."""
 
-    def __init__(self, sequences: List[Sequence], device: int = 0):
+    def __init__(self, sequences: List[Sequence], device: int = 0, extend_plan: "Optional[ExtendPlan]" = None):
+        self.extend_plan = extend_plan                       # --extend: `sequences` is its merged set
         for s in sequences:                                  # :310-317
             if len(s.data) == 0:
                 raise ValueError(
@@ -1297,6 +1388,7 @@ class SeqRush:
 
     def align_and_unite(self, args: Args):
         """align_and_unite_with_allwave (src/seqrush.rs:611-757) on the device"""
+        check_extend(args)
         if args.iterative and args.paf is not None:
             raise SeqRushError(-6, "--iterative cannot be combined with -p (there is no alignment stage to stop)")
         if args.patch_inversions and (args.iterative or args.paf is not None):
@@ -1318,9 +1410,15 @@ class SeqRush:
         params = Params.from_args(args)
         if args.iterative:
             return self._align_and_unite_iterative(args, params)
-        self.ctx.load(self.seqset, params)
         n = len(self.sequences)
-        print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
+        if self.extend_plan is not None:
+            self.ctx.load_extend(self.extend_plan, params)
+            self.seqset = self.ctx.seqset
+            print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
+            print(f"Extending {self.extend_plan.n_old} paths by {n - self.extend_plan.n_old} sequences: {self.ctx.num_pairs} pairs to align")
+        else:
+            self.ctx.load(self.seqset, params)
+            print(f"Total sequence pairs: {n * n} (sparsification: {args.sparsification})")
         if args.patch_inversions:
             self.ctx.enable_inversions(args.inversion_min_size, keep_alignments=bool(args.output_alignments),
                                        join_below=args.inversion_join)
@@ -1333,6 +1431,10 @@ class SeqRush:
         else:
             self.ctx.run()
         self.ctx.sync()
+        if self.extend_plan is not None:
+            self.extend_stats = self.ctx.extend_stats()
+            if args.verbose:
+                print(extend_report(self.extend_stats))
         if args.patch_inversions:
             st = self.ctx.inversion_stats()
             self.inversion_stats = st
@@ -1418,7 +1520,18 @@ def run_seqrush(args: Args):
     """src/seqrush.rs:1839-1853"""
     sequences = load_sequences(args.sequences)
     print(f"Loaded {len(sequences)} sequences")
-    sr = SeqRush(sequences, device=args.device)
+    plan = None
+    if args.extend:
+        check_extend(args)
+        try:
+            with open(args.extend) as fh:
+                text = fh.read()
+        except OSError as e:
+            raise SeqRushError(-8, f"cannot read {args.extend}: {e.strerror}")
+        plan = ExtendPlan(text, sequences, device=args.device)
+        print(f"Extending {args.extend}: {plan.n_old} paths")
+        sequences = [Sequence(name, data) for name, data in plan.records]
+    sr = SeqRush(sequences, device=args.device, extend_plan=plan)
     sr.build_graph(args)
     print(f"Graph written to {args.output}")
     return sr
