@@ -821,6 +821,61 @@ int sr_extend_plan_stats(const sr_extend_plan *plan, sr_extend_stats *out);
 /* the same with the pair counts of the load and the counters and time of the last seed; syncs the context's stream */
 int sr_ctx_extend_stats(sr_ctx *c, sr_extend_stats *out);
 
+/* -------- lifting intervals (`--lift IN.bed --lift-out FILE`) -------------------------------------
+ * Where an interval of one path lies in the other paths (`odgi position`, a liftover), of any GFA with S / L / P lines and
+ * numeric node ids as the parser of sr_sort_gfa reads it.  pstart[s] = the offset of step s in the oriented sequence of
+ * its own path, plen[p] = the length of path p.
+ * Queries: the lines of bed_text, `name start end [label [rest...]]`, 0-based and half-open; fields are separated by tabs
+ * or, on a line without a tab, by runs of blanks; a trailing CR is dropped.  A line that is blank or starts with `#`,
+ * `track` or `browser` is ignored.  Fewer than three fields, or a start or end that is not a decimal number below 2^64:
+ * SR_ERR_INVALID, naming the line.  A name that is no path (the first path of that name counts): skipped, counted in
+ * `unknown`.  start >= end or end > plen: skipped, counted in `out_of_range`.  Every other line is a query; label defaults to
+ * `name:start-end`; queries keep file order and may repeat.
+ * first[B][v] = the smallest step index of path B on node v.  A step s of the query path A on handle (v, r) whose interval
+ * [pstart[s], pstart[s] + len[v]) overlaps the query in the handle offsets [o0, o1) contributes to target B, if B visits
+ * v, with t = first[B][v] on handle (v, r'): the strand r xor r', the image [pstart[t] + o0, pstart[t] + o1) when the
+ * strands agree and [pstart[t] + len - o1, pstart[t] + len - o0) when not, and bp = o1 - o0.  The lift of (query, B):
+ * tstart = the smallest image start, tend = the largest image end, covered = the sum of bp, rev_bp = the sum of bp on the
+ * reverse strand; strand `-` iff 2 * rev_bp > covered.  covered = 0: unmapped, and all four are 0.  This is a hull over
+ * first visits: a target that visits the nodes in another order or a node more than once widens it, so covered stands
+ * beside tend - tstart for the user to filter on.  Nothing is chained.
+ * Targets: every path in file order, or the one named to_name (unknown: SR_ERR_INVALID, whatever the graph holds).  The
+ * tables are dense, [queries x targets], and include the query's own path (which lifts to itself when it visits no node
+ * twice).  queries x targets above 2^26 or targets x nodes above 2^28: SR_ERR_UNSUPPORTED.  Limits of the graph as for the
+ * statistics.  An empty graph, one without a path, or a BED without a query gives empty tables and no error.
+ * device >= 0: HIP kernels on that device (sr_lift.hip); SR_LIFT_DEVICE_HOST: plain loops on the host.  Both give the same
+ * integers and bytes.  short_steps: a query that touches at most this many steps is lifted by one lane per (query, target),
+ * a longer one by one wave per (query, target); 0 and UINT64_MAX send every query one way (tests), and no result depends
+ * on it. */
+#define SR_LIFT_DEVICE_HOST (-1)
+typedef struct {
+    const char *to_name;        /* the one target path; NULL (default): every path */
+    uint64_t min_covered;       /* default 1: sr_lift_bed leaves out pairs with covered below this */
+    uint64_t short_steps;       /* default 8 */
+    uint64_t reserved;          /* 0 */
+} sr_lift_params;
+void sr_lift_params_default(sr_lift_params *p);
+typedef struct {
+    uint64_t queries, targets, paths, unknown, out_of_range, mapped;      /* mapped: pairs of the tables with covered > 0 */
+    uint32_t *q_path;                                   /* [queries] */
+    uint64_t *q_start, *q_end;                          /* [queries] */
+    uint64_t *label_off;                                /* [queries + 1] into labels */
+    char *labels;
+    uint32_t *target_path;                              /* [targets] */
+    uint64_t *tstart, *tend, *covered, *rev_bp;         /* [queries * targets] */
+    int32_t variant, to_named;                          /* variant: 0 the host loops, 1 the device kernels; to_named: to_name was given */
+    uint64_t min_covered;                               /* as given: the writer filters by it */
+    uint64_t short_pairs, long_pairs;                   /* pairs through the lane-per-pair and the wave-per-pair kernel (host: 0, 0) */
+    uint64_t lift_us, kernel_us[5];                     /* the stage; positions, first visits, locate, short pairs, long pairs */
+} sr_lift;
+int sr_lift_gfa(const char *gfa_in, const char *bed_text, const sr_lift_params *p, int device, sr_lift **out);
+void sr_lift_free(sr_lift *l);
+/* The BED text, the only place its bytes are formed; names = the names of the paths in file order; *text is malloc'ed
+ * (sr_free).  One tab-separated line per kept pair in (query, target) order:
+ * `tname tstart tend label covered strand qname qstart qend rev_bp`.  Left out: unmapped pairs, pairs with covered <
+ * min_covered, and pairs whose target is the query's own path unless to_name chose it. */
+int sr_lift_bed(const sr_lift *l, const char *const *names, char **text);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

@@ -71,6 +71,12 @@ def main(argv=None):
     ap.add_argument("--vcf-ref", default=None, metavar="NAME", help="the reference path (default: the first path)")
     ap.add_argument("--vcf-max-allele-len", type=int, default=None, metavar="N",
                     help="traversals with a longer allele or reference span are skipped (default 10000; 0: no limit)")
+    ap.add_argument("--lift", default=None, metavar="IN.bed",
+                    help="project the BED intervals of paths of the final GFA onto its other paths (`odgi position`); needs --lift-out")
+    ap.add_argument("--lift-out", default=None, metavar="FILE", help="the lifted intervals, as BED")
+    ap.add_argument("--lift-to", default=None, metavar="NAME", help="the one target path (default: every other path)")
+    ap.add_argument("--lift-min-covered", type=int, default=None, metavar="N",
+                    help="leave out targets with fewer than N lifted bases (default 1)")
     ap.add_argument("--extend", default=None, metavar="FILE.gfa",
                     help="add the sequences of -s to this graph: its paths are kept as they are and only the pairs that touch a "
                          "new sequence are aligned")
@@ -119,6 +125,19 @@ def main(argv=None):
             print(f"Error: {flag} is an option of --vcf: give both", file=sys.stderr)
             return 1
         if flag == "--vcf-max-allele-len" and not 0 <= v <= 2 ** 64 - 1:
+            print(f"Error: {flag} needs a non-negative integer, got '{v}'", file=sys.stderr)
+            return 1
+    if ns.lift is not None and ns.lift_out is None:
+        print("Error: --lift needs --lift-out FILE: the lifted intervals have nowhere to go", file=sys.stderr)
+        return 1
+    for flag in ("--lift-out", "--lift-to", "--lift-min-covered"):
+        v = getattr(ns, flag.lstrip("-").replace("-", "_"))
+        if v is None:
+            continue
+        if ns.lift is None:
+            print(f"Error: {flag} is an option of --lift: give both", file=sys.stderr)
+            return 1
+        if flag == "--lift-min-covered" and not 0 <= v <= 2 ** 64 - 1:
             print(f"Error: {flag} needs a non-negative integer, got '{v}'", file=sys.stderr)
             return 1
     if ns.bin_width is not None and ns.bin_count is not None:
@@ -170,7 +189,8 @@ def main(argv=None):
                 viz_mode=ns.viz_mode or "path", viz_depth_max=ns.viz_depth_max or 4, growth=ns.growth,
                 growth_permutations=ns.growth_permutations or 1000,
                 growth_seed=9399220 if ns.growth_seed is None else ns.growth_seed, growth_group_by=ns.growth_group_by or "path", vcf=ns.vcf, vcf_ref=ns.vcf_ref,
-                vcf_max_allele_len=10000 if ns.vcf_max_allele_len is None else ns.vcf_max_allele_len, extend=ns.extend)
+                vcf_max_allele_len=10000 if ns.vcf_max_allele_len is None else ns.vcf_max_allele_len, extend=ns.extend,
+                lift=ns.lift, lift_out=ns.lift_out, lift_to=ns.lift_to, lift_min_covered=1 if ns.lift_min_covered is None else ns.lift_min_covered)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

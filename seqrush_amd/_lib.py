@@ -51,6 +51,7 @@ EXPORTS = [
     "sr_pass_tables_host", "sr_pass_tile_own",
     "sr_extend_plan_gfa", "sr_extend_plan_free", "sr_extend_plan_seqs", "sr_extend_plan_n_old", "sr_extend_pair_list",
     "sr_ctx_load_extend", "sr_extend_seed_host", "sr_extend_plan_stats", "sr_ctx_extend_stats",
+    "sr_lift_params_default", "sr_lift_gfa", "sr_lift_free", "sr_lift_bed",
 ]
 
 
@@ -195,6 +196,22 @@ class ExtendStatsC(C.Structure):
     """sr_extend_stats (include/seqrush_amd.h, extending a graph)"""
     _fields_ = [(f, C.c_uint64) for f in ("old_paths", "old_bases", "old_steps", "new_sequences", "pairs_before", "pairs_after",
                                           "unions_attempted", "unions_joined", "spell_us", "seed_us")]
+
+
+class LiftParamsC(C.Structure):
+    """sr_lift_params (include/seqrush_amd.h, lifting intervals)"""
+    _fields_ = [("to_name", C.c_char_p), ("min_covered", C.c_uint64), ("short_steps", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class LiftC(C.Structure):
+    """sr_lift"""
+    _fields_ = [("queries", C.c_uint64), ("targets", C.c_uint64), ("paths", C.c_uint64), ("unknown", C.c_uint64),
+                ("out_of_range", C.c_uint64), ("mapped", C.c_uint64),
+                ("q_path", C.POINTER(C.c_uint32)), ("q_start", C.POINTER(C.c_uint64)), ("q_end", C.POINTER(C.c_uint64)),
+                ("label_off", C.POINTER(C.c_uint64)), ("labels", C.POINTER(C.c_char)), ("target_path", C.POINTER(C.c_uint32)),
+                ("tstart", C.POINTER(C.c_uint64)), ("tend", C.POINTER(C.c_uint64)), ("covered", C.POINTER(C.c_uint64)),
+                ("rev_bp", C.POINTER(C.c_uint64)), ("variant", C.c_int32), ("to_named", C.c_int32), ("min_covered", C.c_uint64),
+                ("short_pairs", C.c_uint64), ("long_pairs", C.c_uint64), ("lift_us", C.c_uint64), ("kernel_us", C.c_uint64 * 5)]
 
 
 class AlignmentsC(C.Structure):
@@ -387,6 +404,11 @@ def load():
     L.sr_extend_seed_host.argtypes = [vp, C.POINTER(u64), u64, C.POINTER(u64)]
     L.sr_extend_plan_stats.argtypes = [vp, PES]
     L.sr_ctx_extend_stats.argtypes = [vp, PES]
+    PLF = C.POINTER(LiftC)
+    L.sr_lift_params_default.argtypes = [C.POINTER(LiftParamsC)]; L.sr_lift_params_default.restype = None
+    L.sr_lift_gfa.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(LiftParamsC), i32, C.POINTER(PLF)]
+    L.sr_lift_free.argtypes = [PLF]; L.sr_lift_free.restype = None
+    L.sr_lift_bed.argtypes = [PLF, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

@@ -84,12 +84,16 @@ static void usage() {
                     "       [--viz-path-gap G] [--viz-mode path|strand|depth] [--viz-depth-max D]]\n"
                     "       [--growth growth.tsv [--growth-permutations N] [--growth-seed N] [--growth-group-by path|sample|haplotype]]\n"
                     "       [--vcf graph.vcf [--vcf-ref NAME] [--vcf-max-allele-len N]] [--extend graph.gfa]\n"
+                    "       [--lift in.bed --lift-out lifted.bed [--lift-to NAME] [--lift-min-covered N]]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
 int main(int argc, char **argv) {
     std::string sequences, output = "output.gfa", scores = "0,5,8,2,24,1", ori = "0,1,1,1", sparsify = "none", paf_out, paf_in,
-                aligner = "allwave", extend_in, stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt, vcf_out, vcf_opt, vcf_ref;
+                aligner = "allwave", extend_in, stats_out, layout_out, layout_svg_out, bin_out, viz_out, bin_opt, viz_opt, growth_out, growth_opt, vcf_out, vcf_opt, vcf_ref,
+                lift_in, lift_out, lift_opt, lift_to;
+    sr_lift_params lfp;
+    sr_lift_params_default(&lfp);
     sr_variant_params vcp;
     sr_variant_params_default(&vcp);
     sr_growth_params gp;
@@ -211,6 +215,17 @@ int main(int argc, char **argv) {
             if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: %s needs a non-negative integer, got '%s'\n", a.c_str(), v); return 1; }
             vcp.max_allele_len = n;
         }
+        else if (a == "--lift") lift_in = val("--lift");
+        else if (a == "--lift-out") { lift_out = val("--lift-out"); lift_opt = a; }
+        else if (a == "--lift-to") { lift_to = val("--lift-to"); lift_opt = a; }
+        else if (a == "--lift-min-covered") {
+            const char *v = val("--lift-min-covered");
+            char *end = nullptr;
+            const unsigned long long n = strtoull(v, &end, 10);
+            lift_opt = a;
+            if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: %s needs a non-negative integer, got '%s'\n", a.c_str(), v); return 1; }
+            lfp.min_covered = n;
+        }
         else if (a == "--extend") extend_in = val("--extend");
         else if (a == "--patch-inversions") patch_inv = true;
         else if (a == "--inversion-min-size") {
@@ -274,6 +289,8 @@ int main(int argc, char **argv) {
     }
     if (!growth_opt.empty() && growth_out.empty()) { fprintf(stderr, "Error: %s is an option of --growth: give both\n", growth_opt.c_str()); return 1; }
     if (!vcf_opt.empty() && vcf_out.empty()) { fprintf(stderr, "Error: %s is an option of --vcf: give both\n", vcf_opt.c_str()); return 1; }
+    if (!lift_in.empty() && lift_out.empty()) { fprintf(stderr, "Error: --lift needs --lift-out FILE: the lifted intervals have nowhere to go\n"); return 1; }
+    if (!lift_opt.empty() && lift_in.empty()) { fprintf(stderr, "Error: %s is an option of --lift: give both\n", lift_opt.c_str()); return 1; }
     if (bin_width && bin_count) { fprintf(stderr, "Error: --bin-width and --bin-count exclude each other\n"); return 1; }
     if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
     if (compact_dev && no_compact) { fprintf(stderr, "Error: --compact-on device and --no-compact exclude each other\n"); return 1; }
@@ -462,7 +479,7 @@ int main(int argc, char **argv) {
     o << gfa;
     std::vector<std::string> pnames;                         // names of the P lines, as the library's parser reads them
     std::vector<const char *> pn;
-    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty() || !growth_out.empty() || !vcf_out.empty()) {
+    if (!stats_out.empty() || !bin_out.empty() || !viz_out.empty() || !growth_out.empty() || !vcf_out.empty() || !lift_in.empty()) {
         for (const char *q = gfa; *q;) {
             const char *eol = strchr(q, '\n');
             if (!eol) eol = q + strlen(q);
@@ -566,6 +583,29 @@ int main(int argc, char **argv) {
         printf("VCF written to %s\n", vcf_out.c_str());
         if (verbose) printf("Variants stage: %llu us on device %d\n", (unsigned long long)va->variants_us, device);
         sr_variants_free(va);
+    }
+    if (!lift_in.empty()) {                                  // the BED intervals lifted over the text just written
+        std::ifstream bi(lift_in, std::ios::binary);
+        if (!bi) { fprintf(stderr, "Error: cannot read %s\n", lift_in.c_str()); sr_free(gfa); return 1; }
+        const std::string bed((std::istreambuf_iterator<char>(bi)), std::istreambuf_iterator<char>());
+        sr_lift *lf = nullptr;
+        char *lifted = nullptr;
+        if (!lift_to.empty()) lfp.to_name = lift_to.c_str();
+        if (sr_lift_gfa(gfa, bed.c_str(), &lfp, device, &lf)) { fprintf(stderr, "Error: %s\n", sr_last_error()); sr_free(gfa); return 1; }
+        if (pn.size() != lf->paths || sr_lift_bed(lf, pn.data(), &lifted)) {
+            fprintf(stderr, "Error: %s\n", pn.size() != lf->paths ? "lift: path names do not match the paths" : sr_last_error());
+            sr_lift_free(lf); sr_free(gfa);
+            return 1;
+        }
+        std::ofstream lo(lift_out, std::ios::binary);
+        lo << lifted;
+        sr_free(lifted);
+        printf("Lifted intervals written to %s\n", lift_out.c_str());
+        if (verbose)
+            printf("Lift stage: %llu us on device %d, %llu queries x %llu targets, %llu mapped, %llu unknown, %llu out of range\n",
+                   (unsigned long long)lf->lift_us, device, (unsigned long long)lf->queries, (unsigned long long)lf->targets,
+                   (unsigned long long)lf->mapped, (unsigned long long)lf->unknown, (unsigned long long)lf->out_of_range);
+        sr_lift_free(lf);
     }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, ExtendStatsC, check,
+                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, ExtendStatsC, LiftParamsC, LiftC, check,
                    SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
@@ -74,6 +74,10 @@ class Args:
     vcf: Optional[str] = None               # added: --vcf FILE: variant sites of the final GFA against one path as VCF
     vcf_ref: Optional[str] = None           # added: --vcf-ref NAME: the reference path (default: the first)
     vcf_max_allele_len: int = 10000         # added: --vcf-max-allele-len N (0: no limit)
+    lift: Optional[str] = None              # added: --lift IN.bed: intervals of paths of the final GFA to project onto its other paths
+    lift_out: Optional[str] = None          # added: --lift-out FILE: where the lifted intervals go (required with --lift)
+    lift_to: Optional[str] = None           # added: --lift-to NAME: the one target path (default: every path)
+    lift_min_covered: int = 1               # added: --lift-min-covered N
     extend: Optional[str] = None            # added: --extend FILE.gfa: add the sequences of -s to this graph
 
 
@@ -1077,6 +1081,102 @@ def write_vcf(text: str, args: "Args"):
         print(f"Variants stage: {us} us on device {args.device}")
 
 
+SR_LIFT_DEVICE_HOST = -1
+LIFT_KERNELS = ("positions", "first_visits", "locate", "short_pairs", "long_pairs")
+
+
+class Lift:
+    """an owned sr_lift: the BED intervals of paths of a GFA text projected onto its other paths"""
+
+    def __init__(self, text: str, bed: str, device: int = 0, to: Optional[str] = None, min_covered: int = 1, short_steps: int = 8):
+        for k, v in (("min_covered", min_covered), ("short_steps", short_steps)):
+            if not 0 <= int(v) < 2 ** 64:
+                raise SeqRushError(-1, f"{k} must be in 0 .. 2^64 - 1")
+        self.L = _lib.load()
+        self.p = C.POINTER(LiftC)()
+        self.names = _path_names(text)
+        prm = LiftParamsC(None if to is None else to.encode(), int(min_covered), int(short_steps), 0)
+        check(self.L.sr_lift_gfa(text.encode(), bed.encode(), C.byref(prm), int(device), C.byref(self.p)))
+
+    def close(self):
+        if self.p:
+            self.L.sr_lift_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def as_dict(self) -> dict:
+        s = self.p.contents
+        Q, T = int(s.queries), int(s.targets)
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].astype(dt, copy=True)
+        d = {k: int(getattr(s, k)) for k in ("queries", "targets", "paths", "unknown", "out_of_range", "mapped", "variant", "to_named",
+                                             "min_covered", "short_pairs", "long_pairs", "lift_us")}
+        d["q_path"], d["q_start"], d["q_end"] = arr(s.q_path, Q, np.uint32), arr(s.q_start, Q, np.uint64), arr(s.q_end, Q, np.uint64)
+        off = arr(s.label_off, Q + 1, np.uint64)
+        arena = C.string_at(s.labels, int(off[-1]))
+        d["labels"] = [arena[int(off[k]):int(off[k + 1])].decode() for k in range(Q)]
+        d["target_path"] = arr(s.target_path, T, np.uint32)
+        for k in ("tstart", "tend", "covered", "rev_bp"):
+            d[k] = arr(getattr(s, k), Q * T, np.uint64).reshape(Q, T)
+        d["kernel_us"] = dict(zip(LIFT_KERNELS, (int(v) for v in s.kernel_us)))
+        return d
+
+    def bed(self) -> str:
+        arr = (C.c_char_p * max(1, len(self.names)))(*[n.encode() for n in self.names])
+        out = C.c_void_p()
+        check(self.L.sr_lift_bed(self.p, C.cast(arr, C.POINTER(C.c_char_p)), C.byref(out)))
+        return _take_text(out)
+
+
+def lift(text: str, bed: str, device: int = 0, to: Optional[str] = None, min_covered: int = 1, short_steps: int = 8) -> dict:
+    """the BED intervals `bed` (name start end [label ...], 0-based, half-open) of paths of any GFA with S / L / P lines and
+    numeric node ids, projected onto every path or onto the path `to`.  device >= 0: HIP kernels on
+    that device, -1: the host twin (the same integers).  -> dict: queries, targets, paths, unknown, out_of_range, mapped;
+    q_path / q_start / q_end / labels per query; target_path; tstart / tend / covered / rev_bp (uint64 [queries, targets],
+    all 0 where unmapped); short_pairs, long_pairs, lift_us, kernel_us"""
+    with Lift(text, bed, device, to, min_covered, short_steps) as v:
+        return v.as_dict()
+
+
+def lift_bed(text: str, bed: str, device: int = 0, to: Optional[str] = None, min_covered: int = 1, short_steps: int = 8) -> str:
+    """the lifted intervals of lift() as BED text, formatted by the library"""
+    with Lift(text, bed, device, to, min_covered, short_steps) as v:
+        return v.bed()
+
+
+def check_lift(args: "Args"):
+    """--lift needs --lift-out and the other way round; before any device work"""
+    if args.lift and not args.lift_out:
+        raise SeqRushError(-1, "--lift needs --lift-out FILE: the lifted intervals have nowhere to go")
+    for flag, on in (("--lift-out", args.lift_out), ("--lift-to", args.lift_to), ("--lift-min-covered", args.lift_min_covered != 1)):
+        if on and not args.lift:
+            raise SeqRushError(-1, f"{flag} is an option of --lift: give both")
+
+
+def write_lift(text: str, args: "Args"):
+    """the --lift stage of both Python front ends on the final GFA text"""
+    try:
+        with open(args.lift) as fh:
+            bed = fh.read()
+    except OSError as e:
+        raise SeqRushError(-8, f"cannot read {args.lift}: {e.strerror}")
+    with Lift(text, bed, args.device, args.lift_to, args.lift_min_covered) as v:
+        with open(args.lift_out, "w") as fh:
+            fh.write(v.bed())
+        s = v.p.contents
+        line = (f"Lift stage: {int(s.lift_us)} us on device {args.device}, {int(s.queries)} queries x {int(s.targets)} targets, "
+                f"{int(s.mapped)} mapped, {int(s.unknown)} unknown, {int(s.out_of_range)} out of range")
+    print(f"Lifted intervals written to {args.lift_out}")
+    if args.verbose:
+        print(line)
+
+
 LAYOUT_STATS =("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
 
 
@@ -1514,10 +1614,13 @@ class SeqRush:
             write_growth(text, args)
         if args.vcf:
             write_vcf(text, args)
+        if args.lift:
+            write_lift(text, args)
 
 
 def run_seqrush(args: Args):
     """src/seqrush.rs:1839-1853"""
+    check_lift(args)
     sequences = load_sequences(args.sequences)
     print(f"Loaded {len(sequences)} sequences")
     plan = None
