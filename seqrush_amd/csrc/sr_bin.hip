@@ -12,7 +12,6 @@
 // B <= SR_BIN_LDS_MAX_BINS: a workgroup works inside one path and keeps its two rows in LDS; larger B: global atomics.
 // No captured graph.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +20,8 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_sort.h"
+#include "sr_stage_host.h"
+#include "sr_stage_dev.h"
 #include "sr_bin_rule.h"
 
 #define BN_BLOCK 256
@@ -35,16 +36,6 @@ static_assert(SR_BIN_CHUNK % BN_BLOCK == 0, "a chunk is a whole number of workgr
 static_assert(2ull * 8 * SR_BIN_LDS_MAX_BINS <= 65536, "two u64 rows of the LDS variant fit 64 KiB");
 
 // ------------------------------------------------------------------ device helpers
-// the path of step s: the largest p with path_off[p] <= s (empty paths share an offset with their successor)
-__device__ __forceinline__ uint32_t bn_path_of(const uint32_t *path_off, uint32_t np, uint32_t s) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (path_off[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // One wave, one step per lane (valid == false: no step).  `row` is the lane's path's row offset into cov / inv: p * B
 // for the global tables, 0 for the LDS rows of the one path a workgroup works in.  The key of a contribution is
 // row + bin, below 2^26, so a run of equal keys never joins two paths.
@@ -134,49 +125,32 @@ __global__ void __launch_bounds__(BN_BLOCK) bn_steps_global_kernel(const uint32_
     const uint64_t s = (uint64_t)blockIdx.x * BN_BLOCK + threadIdx.x;
     const bool valid = s < S;
     uint32_t h = 0, row = 0;
-    if (valid) { h = steps[s]; row = bn_path_of(path_off, np, (uint32_t)s) * B; }
+    if (valid) { h = steps[s]; row = sr_path_of(path_off, np, (uint32_t)s) * B; }
     const uint32_t node = h >> 1;
     bn_wave_steps(valid, row, valid ? pos[node] : 0, valid ? len[node] : 0, h & 1u, w, cov, inv);
 }
 
 namespace {
 
-double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the tables both executions read: node v = 1..V at index v, slot 0 unused (length 0)
-struct BnTables {
-    uint32_t V = 0, S = 0, P = 0, w32 = 1;
+struct BnTables : SrPathTables {
+    uint32_t w32 = 1;
     uint64_t L = 0, w = 1, B = 0;
-    std::vector<uint32_t> len, steps, path_off;
 };
 
 int bn_tables(const SrGraph &g, const sr_bin_params &prm, BnTables &t) {
     if ((prm.bin_width != 0) == (prm.bins != 0)) return sr_fail(SR_ERR_INVALID, "bins: give exactly one of bin_width and bins");
-    const uint64_t nn = g.node_seq.size() ? g.node_seq.size() - 1 : 0, ns = g.steps.size();
-    const uint64_t np = g.path_off.size() ? g.path_off.size() - 1 : 0;
-    uint64_t bases = 0;
-    for (uint64_t v = 1; v <= nn; v++) bases += g.node_seq[v].size();
-    if (nn >= 0x3fffffffULL || ns >= 0x7fffffffULL || np >= 0x7fffffffULL || bases >= 0x7fffffffULL)
+    const SrPathSizes z = sr_path_sizes(g);
+    const uint64_t np = z.paths, bases = z.bases;
+    if (z.nodes >= 0x3fffffffULL || z.steps >= 0x7fffffffULL || np >= 0x7fffffffULL || bases >= 0x7fffffffULL)
         return sr_fail(SR_ERR_UNSUPPORTED, "bins supports < 2^30 nodes and < 2^31 steps, paths and bases");
-    t.V = (uint32_t)nn; t.S = (uint32_t)ns; t.P = (uint32_t)np; t.L = bases;
+    t.L = bases;
     t.w = prm.bin_width ? prm.bin_width : sr_bin_width_of(bases, prm.bins);
     t.w32 = sr_bin_width32(t.w);
     t.B = t.w >= bases ? (bases ? 1 : 0) : sr_bin_count_of(bases, t.w);
     if (np * t.B > SR_BIN_MAX_CELLS)
         return sr_fail(SR_ERR_UNSUPPORTED, "bins: " + std::to_string(np) + " paths x " + std::to_string(t.B) + " bins; the tables support at most 2^26 cells");
-    t.len.assign(nn + 1, 0);
-    for (uint64_t v = 1; v <= nn; v++) {
-        if (!g.node_alive[v]) return sr_fail(SR_ERR_INVALID, "bins: node ids must be dense");
-        t.len[v] = (uint32_t)g.node_seq[v].size();
-    }
-    t.steps = g.steps;
-    for (uint32_t h : t.steps)
-        if ((h >> 1) == 0 || (h >> 1) > nn) return sr_fail(SR_ERR_INVALID, "bins: a path step names a missing node");
-    t.path_off.resize(np + 1, 0);
-    for (uint64_t p = 0; p <= np && p < g.path_off.size(); p++) t.path_off[p] = (uint32_t)g.path_off[p];
-    return SR_OK;
+    return sr_path_tables_fill(g, z, "bins", false, true, t);
 }
 
 sr_path_bins *bn_result(const BnTables &t) {
@@ -215,50 +189,12 @@ void bn_run_host(const BnTables &t, sr_path_bins *r) {
 }
 
 // ------------------------------------------------------------------ device execution
-struct BnDev {
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    int prev_device = -1;
-    std::vector<void *> bufs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int err = 0;
-    void chk(hipError_t e) { if (e != hipSuccess && !err) { err = SR_ERR_HIP; sr_fail(SR_ERR_HIP, std::string("bins: ") + hipGetErrorString(e)); } }
-    ~BnDev() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *b : bufs) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <class Tp> Tp *alloc(uint64_t n, bool zero) {
-        void *p = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(Tp);
-        if (err) return nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { err = SR_ERR_NOMEM; sr_fail(SR_ERR_NOMEM, "not enough device memory for the bin tables"); return nullptr; }
-        bufs.push_back(p);
-        if (zero) chk(hipMemsetAsync(p, 0, bytes, st));
-        return (Tp *)p;
-    }
-    void put(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); }
-    void get(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); }
-    void mark(int i) { if (!err) chk(hipEventRecord(ev[i], st)); }
-};
-
 int bn_run_device(const BnTables &t, int device, void *stream, sr_path_bins *r) {
     const uint32_t V = t.V, S = t.S, P = t.P, B = (uint32_t)t.B;   // P x B <= 2^26 and P >= 1 where it matters: B fits
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sr_fail(SR_ERR_NO_DEVICE, "bins: no HIP device (device -1 selects the host twin)");
-    if (device >= ndev) return sr_fail(SR_ERR_INVALID, "bins: no HIP device " + std::to_string(device));
+    SrStage x("bins", "the bin tables");
+    if (x.open(device, stream, 4)) return x.err;
     const uint64_t cells = (uint64_t)P * B;
     if (!cells || !S) return SR_OK;                                  // no path, no bin or no step: the tables stay zero
-    BnDev x;
-    x.chk(hipGetDevice(&x.prev_device));
-    x.chk(hipSetDevice(device));
-    x.st = (hipStream_t)stream;
-    if (!x.st && !x.err) { x.chk(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking)); x.own_stream = !x.err; }
-    for (hipEvent_t &e : x.ev) if (!x.err) x.chk(hipEventCreate(&e));
-    if (x.err) return x.err;
-
     // the work items of the LDS variant: every path cut into chunks of SR_BIN_CHUNK steps
     const bool lds = B <= SR_BIN_LDS_MAX_BINS;
     std::vector<uint32_t> item_path, item_first;
@@ -267,11 +203,11 @@ int bn_run_device(const BnTables &t, int device, void *stream, sr_path_bins *r) 
             for (uint64_t s = t.path_off[p]; s < t.path_off[p + 1]; s += SR_BIN_CHUNK) { item_path.push_back(p); item_first.push_back((uint32_t)s); }
 
     const uint64_t nv = (uint64_t)V + 1;
-    uint32_t *d_len = x.alloc<uint32_t>(nv, false), *d_pos = x.alloc<uint32_t>(nv, true), *d_steps = x.alloc<uint32_t>(S, false);
-    uint32_t *d_poff = x.alloc<uint32_t>((uint64_t)P + 1, false);
-    uint32_t *d_tile = x.alloc<uint32_t>(nv / 1024 + 2, false), *d_grand = x.alloc<uint32_t>(1, true);
-    uint32_t *d_ipath = x.alloc<uint32_t>(item_path.size(), false), *d_ifirst = x.alloc<uint32_t>(item_first.size(), false);
-    u64d *d_cov = x.alloc<u64d>(cells, true), *d_inv = x.alloc<u64d>(cells, true);
+    uint32_t *d_len = x.alloc<uint32_t>(nv), *d_pos = x.alloc<uint32_t>(nv, 0), *d_steps = x.alloc<uint32_t>(S);
+    uint32_t *d_poff = x.alloc<uint32_t>((uint64_t)P + 1);
+    uint32_t *d_tile = x.alloc<uint32_t>(nv / 1024 + 2), *d_grand = x.alloc<uint32_t>(1, 0);
+    uint32_t *d_ipath = x.alloc<uint32_t>(item_path.size()), *d_ifirst = x.alloc<uint32_t>(item_first.size());
+    u64d *d_cov = x.alloc<u64d>(cells, 0), *d_inv = x.alloc<u64d>(cells, 0);
     if (x.err) return x.err;
     x.put(d_len, t.len.data(), nv * 4); x.put(d_steps, t.steps.data(), (size_t)S * 4); x.put(d_poff, t.path_off.data(), ((size_t)P + 1) * 4);
     x.put(d_ipath, item_path.data(), item_path.size() * 4); x.put(d_ifirst, item_first.data(), item_first.size() * 4);
@@ -291,21 +227,14 @@ int bn_run_device(const BnTables &t, int device, void *stream, sr_path_bins *r) 
     x.chk(hipGetLastError());
     x.get(r->cov, d_cov, (size_t)cells * 8); x.get(r->inv, d_inv, (size_t)cells * 8);
     x.mark(3);
-    if (!x.err) x.chk(hipStreamSynchronize(x.st));       // the one synchronisation
+    x.sync();                                        // the one synchronisation
     if (x.err) return x.err;
-    float total = 0.f;
-    x.chk(hipEventElapsedTime(&total, x.ev[0], x.ev[3]));
-    r->bin_us = (uint64_t)(total * 1000.0 + 0.5);
-    for (int k = 0; k < 3; k++) {
-        float ms = 0.f;
-        x.chk(hipEventElapsedTime(&ms, x.ev[k], x.ev[k + 1]));
-        r->kernel_us[k] = (uint64_t)(ms * 1000.0 + 0.5);
-    }
+    r->bin_us = x.us(0, 3);
+    for (int k = 0; k < 3; k++) r->kernel_us[k] = x.us(k, k + 1);
     return x.err;
 }
 
 // ------------------------------------------------------------------ outputs
-std::string u64s(uint64_t v) { return std::to_string((unsigned long long)v); }
 std::string name_of(const char *const *names, uint64_t p) { return names && names[p] ? std::string(names[p]) : u64s(p); }
 
 int viz_check(const sr_path_bins *b, const sr_viz_params &v, uint64_t *width, uint64_t *height) {
@@ -393,11 +322,7 @@ extern "C" int sr_path_bins_tsv(const sr_path_bins *b, const char *const *names,
             o += buf;
         }
     }
-    char *res = (char *)malloc(o.size() + 1);
-    if (!res) return sr_fail(SR_ERR_NOMEM, "not enough memory for the bin table text");
-    memcpy(res, o.c_str(), o.size() + 1);
-    *text = res;
-    return SR_OK;
+    return sr_give_text(o, text, "not enough memory for the bin table text");
 }
 
 extern "C" void sr_viz_params_default(sr_viz_params *p) {

@@ -10,7 +10,6 @@
 //   seed  (the context's stream): anchor[] by atomicMin from one lane per step, then one lane per spelled base: bisection,
 //         the rule, uf_unite (sr_uf_dev.h); unions attempted / joined are counted with one add per wave
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,48 +20,20 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_sort.h"
+#include "sr_stage_host.h"
+#include "sr_stage_dev.h"
 #include "sr_uf_dev.h"
 #include "sr_extend.h"
 #include "sr_extend_rule.h"
 
 #define EX_BLOCK 256
-#define EX_WAVES (EX_BLOCK / 64)
 
 typedef unsigned long long u64d;
 
+static_assert(EX_BLOCK == SR_STAGE_BLOCK, "the grids of sr_stage_grid");
+
 // ------------------------------------------------------------------ spell
-__global__ void __launch_bounds__(EX_BLOCK) ex_len_kernel(const uint32_t *steps, const uint32_t *len, uint32_t S, u64d *out) {
-    const uint32_t s = blockIdx.x * EX_BLOCK + threadIdx.x;
-    if (s < S) out[s] = len[(steps[s] >> 1) - 1];
-}
-
-// inclusive sum scan of n u64 values in place: wave shuffles, an LDS combine across the workgroup, and a block-sums pass
-// as the carry across workgroups (ex_scan below recurses on the sums)
-__global__ void __launch_bounds__(EX_BLOCK) ex_scan_block_kernel(u64d *data, uint32_t n, u64d *sums) {
-    __shared__ u64d wsum[EX_WAVES];
-    const uint32_t i = blockIdx.x * EX_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64d v = i < n ? data[i] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64d t = __shfl_up(v, o, 64);
-        if ((int)lane >= o) v += t;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    u64d carry = 0;
-#pragma unroll
-    for (int w = 0; w < EX_WAVES; w++) if (w < (int)wave) carry += wsum[w];
-    v += carry;
-    if (i < n) data[i] = v;
-    if (threadIdx.x == EX_BLOCK - 1) sums[blockIdx.x] = v;       // lanes beyond n carry the last value on
-}
-
-__global__ void __launch_bounds__(EX_BLOCK) ex_scan_carry_kernel(u64d *data, uint32_t n, const u64d *sums) {
-    const uint32_t i = blockIdx.x * EX_BLOCK + threadIdx.x;
-    if (blockIdx.x == 0 || i >= n) return;
-    data[i] += sums[blockIdx.x - 1];
-}
-
+// the step lengths and their inclusive scan: sr_stage_dev.h
 __global__ void __launch_bounds__(EX_BLOCK) ex_spell_kernel(const uint32_t *steps, const uint32_t *len, const u64d *sinc, const uint64_t *seq_off,
                                                             const uint8_t *seq, uint32_t S, uint64_t bases, uint8_t *out) {
     const uint64_t x = (uint64_t)blockIdx.x * EX_BLOCK + threadIdx.x;
@@ -89,25 +60,19 @@ __global__ void __launch_bounds__(EX_BLOCK) ex_seed_kernel(SrExtendSeedArgs a) {
     if (err) atomicOr(a.error_flag, err);
 }
 
-static unsigned ex_grid(uint64_t n) { return (unsigned)((n + EX_BLOCK - 1) / EX_BLOCK); }
-
 int srk_extend_anchor(const SrExtendSeedArgs *a, void *stream) {
     if (!a->S) return 0;
-    hipLaunchKernelGGL(ex_anchor_kernel, dim3(ex_grid(a->S)), dim3(EX_BLOCK), 0, (hipStream_t)stream, a->steps, a->S, a->anchor);
+    hipLaunchKernelGGL(ex_anchor_kernel, dim3(sr_stage_grid(a->S)), dim3(EX_BLOCK), 0, (hipStream_t)stream, a->steps, a->S, a->anchor);
     return (int)hipGetLastError();
 }
 
 int srk_extend_seed(const SrExtendSeedArgs *a, void *stream) {
     if (!a->bases) return 0;
-    hipLaunchKernelGGL(ex_seed_kernel, dim3(ex_grid(a->bases)), dim3(EX_BLOCK), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(ex_seed_kernel, dim3(sr_stage_grid(a->bases)), dim3(EX_BLOCK), 0, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }
 
 namespace {
-
-double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // the node sequences back to back, as the spelling reads them
 struct ExSeq { std::vector<uint64_t> off; std::vector<uint8_t> seq; };
@@ -123,82 +88,33 @@ void ex_spell_host(sr_extend_plan &pl, const ExSeq &q) {
 }
 
 // ------------------------------------------------------------------ device execution of the spell group
-struct ExStream {
-    hipStream_t st = nullptr;
-    int prev_device = -1;
-    std::vector<void *> bufs;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int err = 0;
-    void chk(hipError_t e) { if (e != hipSuccess && !err) { err = SR_ERR_HIP; sr_fail(SR_ERR_HIP, std::string("extend: ") + hipGetErrorString(e)); } }
-    ~ExStream() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *b : bufs) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <class Tp> Tp *alloc(uint64_t n) {
-        void *p = nullptr;
-        if (err) return nullptr;
-        if (hipMalloc(&p, (n ? n : 1) * sizeof(Tp)) != hipSuccess) { err = SR_ERR_NOMEM; sr_fail(SR_ERR_NOMEM, "not enough device memory for the extend tables"); return nullptr; }
-        bufs.push_back(p);
-        return (Tp *)p;
-    }
-    void put(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); }
-    void get(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); }
-};
-
-uint64_t ex_scan_room(uint64_t n) {
-    uint64_t room = 0;
-    while (n > 1) { n = (n + EX_BLOCK - 1) / EX_BLOCK; room += n; }
-    return room + 1;
-}
-// inclusive scan of data[0..n) in place; `sums` holds the block sums of every level (ex_scan_room elements)
-void ex_scan(ExStream &x, u64d *data, uint32_t n, u64d *sums) {
-    if (x.err || !n) return;
-    const unsigned blocks = ex_grid(n);
-    hipLaunchKernelGGL(ex_scan_block_kernel, dim3(blocks), dim3(EX_BLOCK), 0, x.st, data, n, sums);
-    if (blocks == 1) return;
-    ex_scan(x, sums, blocks, sums + blocks);
-    hipLaunchKernelGGL(ex_scan_carry_kernel, dim3(blocks), dim3(EX_BLOCK), 0, x.st, data, n, (const u64d *)sums);
-}
-
 int ex_spell_device(sr_extend_plan &pl, const ExSeq &q, int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sr_fail(SR_ERR_NO_DEVICE, "extend: no HIP device (device -1 selects the host twin)");
-    if (device >= ndev) return sr_fail(SR_ERR_INVALID, "extend: no HIP device " + std::to_string(device));
-    ExStream x;
-    x.chk(hipGetDevice(&x.prev_device));
-    x.chk(hipSetDevice(device));
-    if (!x.err) x.chk(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking));
-    for (hipEvent_t &e : x.ev) if (!x.err) x.chk(hipEventCreate(&e));
-    if (x.err) return x.err;
+    SrStage x("extend", "the extend tables");
+    if (x.open(device, nullptr, 2)) return x.err;             // the plan's own stream
     const uint32_t S = pl.S, V = pl.V;
     const uint64_t B = pl.old_bases;
     uint32_t *d_steps = x.alloc<uint32_t>(S), *d_len = x.alloc<uint32_t>(V);
     uint64_t *d_soff = x.alloc<uint64_t>((uint64_t)V + 1);
     uint8_t *d_seq = x.alloc<uint8_t>(q.seq.size()), *d_out = x.alloc<uint8_t>(B);
-    u64d *d_sinc = x.alloc<u64d>(S), *d_sums = x.alloc<u64d>(ex_scan_room(S));
+    u64d *d_sinc = x.alloc<u64d>(S), *d_sums = x.alloc<u64d>(sr_scan_room(S));
     if (x.err) return x.err;
     x.put(d_steps, pl.steps.data(), (size_t)S * 4); x.put(d_len, pl.len.data(), (size_t)V * 4);
     x.put(d_soff, q.off.data(), ((size_t)V + 1) * 8); x.put(d_seq, q.seq.data(), q.seq.size());
-    if (!x.err) x.chk(hipEventRecord(x.ev[0], x.st));
+    x.mark(0);
     if (!x.err) {
-        hipLaunchKernelGGL(ex_len_kernel, dim3(ex_grid(S)), dim3(EX_BLOCK), 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_len, S, d_sinc);
-        ex_scan(x, d_sinc, S, d_sums);
+        sr_step_len(x, d_steps, d_len, S, d_sinc);
+        sr_scan<false>(x, d_sinc, S, d_sums);
         // B is the host's sum of the same lengths: the scan's last entry equals it
-        hipLaunchKernelGGL(ex_spell_kernel, dim3(ex_grid(B)), dim3(EX_BLOCK), 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_len, (const u64d *)d_sinc,
+        hipLaunchKernelGGL(ex_spell_kernel, dim3(sr_stage_grid(B)), dim3(EX_BLOCK), 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_len, (const u64d *)d_sinc,
                            (const uint64_t *)d_soff, (const uint8_t *)d_seq, S, B, d_out);
         x.chk(hipGetLastError());
     }
-    if (!x.err) x.chk(hipEventRecord(x.ev[1], x.st));
+    x.mark(1);
     x.get(pl.bases.data(), d_out, B);                            // the one download: the front of the merged set
     x.get(pl.sinc.data(), d_sinc, (size_t)S * 8);
-    if (!x.err) x.chk(hipStreamSynchronize(x.st));
+    x.sync();
     if (x.err) return x.err;
-    float ms = 0.f;
-    x.chk(hipEventElapsedTime(&ms, x.ev[0], x.ev[1]));
-    pl.spell_us = (uint64_t)(ms * 1000.0 + 0.5);
+    pl.spell_us = x.us(0, 1);
     if (pl.sinc[S - 1] != B) return sr_fail(SR_ERR_DEVICE_FAULT, "extend: the device scan of the step lengths does not end at the number of old bases");
     return x.err;
 }

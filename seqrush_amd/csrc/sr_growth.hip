@@ -11,7 +11,6 @@
 // tables.  No captured graph.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +22,8 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_sort.h"
+#include "sr_stage_host.h"
+#include "sr_stage_dev.h"
 #include "sr_growth_rule.h"
 
 #define GR_BLOCK 256
@@ -31,27 +32,18 @@
 
 typedef unsigned long long u64d;
 
+static_assert(GR_BLOCK == SR_STAGE_BLOCK, "the grids of sr_stage_grid");
 static_assert(SR_GROWTH_CHUNK_WORDS == 64, "one node word per lane of a wave");
 static_assert((SR_GROWTH_MAX_GROUPS + 1) * 8 <= 65536, "the histogram and the keys of one permutation fit 64 KiB of LDS");
 
 // ------------------------------------------------------------------ presence
-// the path of step s: the largest p with path_off[p] <= s (empty paths share an offset with their successor)
-__device__ __forceinline__ uint32_t gr_path_of(const uint32_t *path_off, uint32_t np, uint32_t s) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (path_off[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // steps name nodes 1..V (checked on the host); cnt[b] = groups present on node b + 1
 __global__ void __launch_bounds__(GR_BLOCK) gr_presence_kernel(const uint32_t *steps, uint32_t S, const uint32_t *path_off, uint32_t np,
                                                                const uint32_t *group_of, uint64_t W, u64d *cols, uint32_t *cnt) {
     const uint64_t s = (uint64_t)blockIdx.x * GR_BLOCK + threadIdx.x;
     if (s >= S) return;
     const uint32_t b = (steps[s] >> 1) - 1;
-    const uint32_t g = group_of[gr_path_of(path_off, np, (uint32_t)s)];
+    const uint32_t g = group_of[sr_path_of(path_off, np, (uint32_t)s)];
     const u64d bit = 1ULL << (b & 63u);
     const u64d old = atomicOr(&cols[(uint64_t)g * W + (b >> 6)], bit);
     if (!(old & bit)) atomicAdd(&cnt[b], 1u);
@@ -172,29 +164,23 @@ __global__ void __launch_bounds__(GR_BLOCK) gr_prefix_kernel(uint32_t R, uint32_
 
 namespace {
 
-double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the tables both executions read.  Node v = 1..V sits at index v - 1.
-struct GrTables {
-    uint32_t V = 0, S = 0, P = 0, G = 0, R = 0;
+struct GrTables : SrPathTables {
+    uint32_t G = 0, R = 0;
     uint64_t L = 0, W = 0, seed = 0;
     bool exhaustive = false;
-    std::vector<uint32_t> len, steps, path_off, group_of;
+    std::vector<uint32_t> group_of;
 };
 
 int gr_tables(const SrGraph &g, const uint32_t *group_of, uint32_t n_groups, const sr_growth_params &prm, GrTables &t) {
     if (prm.permutations == 0) return sr_fail(SR_ERR_INVALID, "growth: permutations must be at least 1");
-    const uint64_t nn = g.node_seq.size() ? g.node_seq.size() - 1 : 0, ns = g.steps.size();
-    const uint64_t np = g.path_off.size() ? g.path_off.size() - 1 : 0;
-    uint64_t bases = 0;
-    for (uint64_t v = 1; v <= nn; v++) bases += g.node_seq[v].size();
-    if (nn >= 0x3fffffffULL || ns >= 0x7fffffffULL || np >= 0x7fffffffULL || bases >= 0x7fffffffULL)
+    const SrPathSizes z = sr_path_sizes(g);
+    const uint64_t nn = z.nodes, np = z.paths;
+    if (nn >= 0x3fffffffULL || z.steps >= 0x7fffffffULL || np >= 0x7fffffffULL || z.bases >= 0x7fffffffULL)
         return sr_fail(SR_ERR_UNSUPPORTED, "growth supports < 2^30 nodes and < 2^31 steps, paths and bases");
     const uint64_t G = group_of ? n_groups : np;
     if (G > SR_GROWTH_MAX_GROUPS) return sr_fail(SR_ERR_UNSUPPORTED, "growth: " + std::to_string(G) + " groups; at most 4096 are supported");
-    t.V = (uint32_t)nn; t.S = (uint32_t)ns; t.P = (uint32_t)np; t.L = bases; t.W = sr_growth_words(nn); t.seed = prm.seed;
+    t.L = z.bases; t.W = sr_growth_words(nn); t.seed = prm.seed;
     t.group_of.resize(np);
     std::vector<uint8_t> used(G, 0);
     for (uint64_t p = 0; p < np; p++) {
@@ -209,17 +195,7 @@ int gr_tables(const SrGraph &g, const uint32_t *group_of, uint32_t n_groups, con
     t.G = (uint32_t)G;
     t.exhaustive = G >= 1 && G <= SR_GROWTH_EXHAUSTIVE_MAX && sr_growth_factorial((uint32_t)G) <= prm.permutations;
     t.R = G == 0 ? 0 : t.exhaustive ? (uint32_t)sr_growth_factorial((uint32_t)G) : (uint32_t)prm.permutations;
-    t.len.assign(nn, 0);
-    for (uint64_t v = 1; v <= nn; v++) {
-        if (!g.node_alive[v]) return sr_fail(SR_ERR_INVALID, "growth: node ids must be dense");
-        t.len[v - 1] = (uint32_t)g.node_seq[v].size();
-    }
-    t.steps = g.steps;
-    for (uint32_t h : t.steps)
-        if ((h >> 1) == 0 || (h >> 1) > nn) return sr_fail(SR_ERR_INVALID, "growth: a path step names a missing node");
-    t.path_off.resize(np + 1, 0);
-    for (uint64_t p = 0; p <= np && p < g.path_off.size(); p++) t.path_off[p] = (uint32_t)g.path_off[p];
-    return SR_OK;
+    return sr_path_tables_fill(g, z, "growth", false, false, t);
 }
 
 sr_growth *gr_result(const GrTables &t) {
@@ -295,53 +271,13 @@ void gr_run_host(const GrTables &t, sr_growth *r) {
 }
 
 // ------------------------------------------------------------------ device execution
-struct GrDev {
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    int prev_device = -1;
-    std::vector<void *> bufs;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int err = 0;
-    void chk(hipError_t e) { if (e != hipSuccess && !err) { err = SR_ERR_HIP; sr_fail(SR_ERR_HIP, std::string("growth: ") + hipGetErrorString(e)); } }
-    ~GrDev() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *b : bufs) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <class Tp> Tp *alloc(uint64_t n, bool zero) {
-        void *p = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(Tp);
-        if (err) return nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { err = SR_ERR_NOMEM; sr_fail(SR_ERR_NOMEM, "not enough device memory for the growth tables"); return nullptr; }
-        bufs.push_back(p);
-        if (zero) chk(hipMemsetAsync(p, 0, bytes, st));
-        return (Tp *)p;
-    }
-    void put(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); }
-    void get(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); }
-    void mark(int i) { if (!err) chk(hipEventRecord(ev[i], st)); }
-};
-
-unsigned gr_grid(uint64_t n) { return (unsigned)((n + GR_BLOCK - 1) / GR_BLOCK); }
-
 int gr_run_device(const GrTables &t, int device, void *stream, sr_growth *r) {
     const uint32_t V = t.V, S = t.S, P = t.P, G = t.G, R = t.R;
     const uint64_t W = t.W;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sr_fail(SR_ERR_NO_DEVICE, "growth: no HIP device (device -1 selects the host twin)");
-    if (device >= ndev) return sr_fail(SR_ERR_INVALID, "growth: no HIP device " + std::to_string(device));
+    SrStage x("growth", "the growth tables");
+    if (x.open(device, stream, 6)) return x.err;
     r->variant = SR_GROWTH_VARIANT_WAVE;
     if (!G) return SR_OK;                            // no group: empty tables; bp_by_groups[0] below needs no device either
-    GrDev x;
-    x.chk(hipGetDevice(&x.prev_device));
-    x.chk(hipSetDevice(device));
-    x.st = (hipStream_t)stream;
-    if (!x.st && !x.err) { x.chk(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking)); x.own_stream = !x.err; }
-    for (hipEvent_t &e : x.ev) if (!x.err) x.chk(hipEventCreate(&e));
-    if (x.err) return x.err;
-
     const uint64_t cells = (uint64_t)R * G;          // <= 2^24
     const uint64_t chunks = (W + SR_GROWTH_CHUNK_WORDS - 1) / SR_GROWTH_CHUNK_WORDS;      // <= 2^18
     // permutations per workgroup: enough workgroups to fill the device on a small graph, a shared LDS copy on a large one
@@ -350,61 +286,46 @@ int gr_run_device(const GrTables &t, int device, void *stream, sr_growth *r) {
     const uint64_t slices = (R + ppb - 1) / ppb;     // <= 2^22; chunks x slices < 2^31 is checked below
     if (chunks * slices > 0x7fffffffULL) return sr_fail(SR_ERR_UNSUPPORTED, "growth: too many (chunk, permutation) work items for one launch");
 
-    uint32_t *d_len = x.alloc<uint32_t>(V, false), *d_cnt = x.alloc<uint32_t>(V, true), *d_steps = x.alloc<uint32_t>(S, false);
-    uint32_t *d_poff = x.alloc<uint32_t>((uint64_t)P + 1, false), *d_gof = x.alloc<uint32_t>(P, false);
-    u64d *d_cols = x.alloc<u64d>((uint64_t)G * W, true), *d_hist = x.alloc<u64d>((uint64_t)G + 1, true);
-    uint32_t *d_perm = x.alloc<uint32_t>(cells, false);
-    u64d *d_pan = x.alloc<u64d>(cells, true), *d_core = x.alloc<u64d>(cells, true);
+    uint32_t *d_len = x.alloc<uint32_t>(V), *d_cnt = x.alloc<uint32_t>(V, 0), *d_steps = x.alloc<uint32_t>(S);
+    uint32_t *d_poff = x.alloc<uint32_t>((uint64_t)P + 1), *d_gof = x.alloc<uint32_t>(P);
+    u64d *d_cols = x.alloc<u64d>((uint64_t)G * W, 0), *d_hist = x.alloc<u64d>((uint64_t)G + 1, 0);
+    uint32_t *d_perm = x.alloc<uint32_t>(cells);
+    u64d *d_pan = x.alloc<u64d>(cells, 0), *d_core = x.alloc<u64d>(cells, 0);
     if (x.err) return x.err;
     x.put(d_len, t.len.data(), (size_t)V * 4); x.put(d_steps, t.steps.data(), (size_t)S * 4);
     x.put(d_poff, t.path_off.data(), ((size_t)P + 1) * 4); x.put(d_gof, t.group_of.data(), (size_t)P * 4);
 
     x.mark(0);
-    if (!x.err && S) hipLaunchKernelGGL(gr_presence_kernel, dim3(gr_grid(S)), dim3(GR_BLOCK), 0, x.st, d_steps, S, d_poff, P, d_gof, W, d_cols, d_cnt);
+    if (!x.err && S) hipLaunchKernelGGL(gr_presence_kernel, dim3(sr_stage_grid(S)), dim3(GR_BLOCK), 0, x.st, d_steps, S, d_poff, P, d_gof, W, d_cols, d_cnt);
     x.mark(1);
     if (!x.err && V) {
-        const uint64_t blocks = gr_grid(V) < 1024 ? gr_grid(V) : 1024;
+        const uint64_t blocks = sr_stage_grid(V) < 1024 ? sr_stage_grid(V) : 1024;
         hipLaunchKernelGGL(gr_hist_kernel, dim3((unsigned)blocks), dim3(GR_BLOCK), ((size_t)G + 1) * 8, x.st, d_len, d_cnt, V, G, d_hist);
     }
     x.mark(2);
     if (!x.err) {
-        if (t.exhaustive) hipLaunchKernelGGL(gr_unrank_kernel, dim3(gr_grid(R)), dim3(GR_BLOCK), 0, x.st, R, G, d_perm);
+        if (t.exhaustive) hipLaunchKernelGGL(gr_unrank_kernel, dim3(sr_stage_grid(R)), dim3(GR_BLOCK), 0, x.st, R, G, d_perm);
         else hipLaunchKernelGGL(gr_ranks_kernel, dim3(R), dim3(GR_BLOCK), (size_t)G * 8, x.st, (uint64_t)t.seed, G, d_perm);
     }
     x.mark(3);
     if (!x.err) {
         if (W) hipLaunchKernelGGL(gr_growth_kernel, dim3((unsigned)(chunks * slices)), dim3(GR_BLOCK), 0, x.st, d_cols, W, V, d_len, d_perm, R, G,
                                   (uint32_t)ppb, (uint32_t)slices, d_pan, d_core);
-        hipLaunchKernelGGL(gr_prefix_kernel, dim3(gr_grid(R)), dim3(GR_BLOCK), 0, x.st, R, G, d_pan, d_core);
+        hipLaunchKernelGGL(gr_prefix_kernel, dim3(sr_stage_grid(R)), dim3(GR_BLOCK), 0, x.st, R, G, d_pan, d_core);
     }
     x.mark(4);
     x.chk(hipGetLastError());
     x.get(r->pan, d_pan, (size_t)cells * 8); x.get(r->core, d_core, (size_t)cells * 8); x.get(r->perm, d_perm, (size_t)cells * 4);
     x.get(r->bp_by_groups, d_hist, ((size_t)G + 1) * 8);
     x.mark(5);
-    if (!x.err) x.chk(hipStreamSynchronize(x.st));   // the one synchronisation
+    x.sync();                                        // the one synchronisation
     if (x.err) return x.err;
-    float total = 0.f;
-    x.chk(hipEventElapsedTime(&total, x.ev[0], x.ev[5]));
-    r->growth_us = (uint64_t)(total * 1000.0 + 0.5);
-    for (int k = 0; k < 4; k++) {
-        float ms = 0.f;
-        x.chk(hipEventElapsedTime(&ms, x.ev[k], x.ev[k + 1]));
-        r->kernel_us[k] = (uint64_t)(ms * 1000.0 + 0.5);
-    }
+    r->growth_us = x.us(0, 5);
+    for (int k = 0; k < 4; k++) r->kernel_us[k] = x.us(k, k + 1);
     return x.err;
 }
 
-std::string u64s(uint64_t v) { return std::to_string((unsigned long long)v); }
 std::string f6(double v) { char b[64]; snprintf(b, sizeof b, "%.6f", v); return b; }
-
-int gr_text(const std::string &o, char **text) {
-    char *res = (char *)malloc(o.size() + 1);
-    if (!res) return sr_fail(SR_ERR_NOMEM, "not enough memory for the growth report");
-    memcpy(res, o.c_str(), o.size() + 1);
-    *text = res;
-    return SR_OK;
-}
 
 }   // namespace
 
@@ -570,7 +491,7 @@ extern "C" int sr_growth_report(const sr_growth *g, char **text) {
         };
         for (uint64_t k = 0; k < G; k++)
             o += u64s(k + 1) + "\t" + f6(pe[k]) + "\t" + f6(ce[k]) + "\t" + column(g->pan, k) + "\t" + column(g->core, k) + "\n";
-        return gr_text(o, text);
+        return sr_give_text(o, text, "not enough memory for the growth report");
     } catch (const std::bad_alloc &) {
         return sr_fail(SR_ERR_NOMEM, "not enough memory for the growth report");
     }

@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/seqrush_amd.h"
 #include "sr_layout.h"
+#include "sr_stage_host.h"
 
 #pragma clang fp contract(off)
 
@@ -248,20 +249,12 @@ static void appendf(std::string &s, const char *fmt, ...) {
     if (n > 0) s.append(buf, std::min((size_t)n, sizeof(buf) - 1));
 }
 
-static int give_text(const std::string &s, char **text) {
-    char *out = (char *)malloc(s.size() + 1);
-    if (!out) return sr_fail(SR_ERR_NOMEM, "out of memory");
-    memcpy(out, s.c_str(), s.size() + 1);
-    *text = out;
-    return SR_OK;
-}
-
 extern "C" int sr_layout_tsv(const double *xy, uint64_t n, char **text) {
     if ((!xy && n) || !text) return sr_fail(SR_ERR_INVALID, "null argument");
     std::string s = "idx\tX\tY\n";
     s.reserve(16 + n * 64);
     for (uint64_t e = 0; e < 2 * n; e++) appendf(s, "%llu\t%.4f\t%.4f\n", (unsigned long long)e, xy[2 * e], xy[2 * e + 1]);
-    return give_text(s, text);
+    return sr_give_text(s, text, "out of memory");
 }
 
 extern "C" int sr_layout_svg(const char *gfa_in, const double *xy, uint64_t n, char **text) {
@@ -296,7 +289,7 @@ extern "C" int sr_layout_svg(const char *gfa_in, const double *xy, uint64_t n, c
         appendf(s, "<line x1=\"%.4f\" y1=\"%.4f\" x2=\"%.4f\" y2=\"%.4f\"/>\n", xy[2 * a], xy[2 * a + 1], xy[2 * b], xy[2 * b + 1]);
     }
     s += "</g>\n</svg>\n";
-    return give_text(s, text);
+    return sr_give_text(s, text, "out of memory");
 }
 
 extern "C" int sr_layout_quality(const char *gfa_in, const double *xy, uint64_t n, uint64_t seed, uint64_t samples, double out[4]) {

@@ -12,7 +12,6 @@
 // download: one synchronisation.  No atomic decides a value except the min of the first-visit table.  No captured graph.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +22,8 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_sort.h"
+#include "sr_stage_host.h"
+#include "sr_stage_dev.h"
 #include "sr_lift_rule.h"
 
 #define LF_BLOCK 256
@@ -31,57 +32,15 @@
 
 typedef uint64_t u64d;
 
-// ------------------------------------------------------------------ scan
-// inclusive sum scan of n u64 values in place: wave shuffles, an LDS combine across the workgroup, and a block-sums pass
-// as the carry across workgroups (lf_scan below recurses on the sums); the idiom of sr_variants.hip, kept private so that
-// no other object file changes
-__global__ void __launch_bounds__(LF_BLOCK) lf_scan_block_kernel(u64d *data, uint32_t n, u64d *sums) {
-    __shared__ u64d wsum[LF_WAVES];
-    const uint32_t i = blockIdx.x * LF_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64d v = i < n ? data[i] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64d t = __shfl_up(v, o, 64);
-        if ((int)lane >= o) v += t;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    u64d carry = 0;
-#pragma unroll
-    for (int w = 0; w < LF_WAVES; w++) if (w < (int)wave) carry += wsum[w];
-    v += carry;
-    if (i < n) data[i] = v;
-    if (threadIdx.x == LF_BLOCK - 1) sums[blockIdx.x] = v;     // lanes beyond n carry the last value on
-}
-
-__global__ void __launch_bounds__(LF_BLOCK) lf_scan_carry_kernel(u64d *data, uint32_t n, const u64d *sums) {
-    const uint32_t i = blockIdx.x * LF_BLOCK + threadIdx.x;
-    if (blockIdx.x == 0 || i >= n) return;
-    data[i] += sums[blockIdx.x - 1];
-}
-
-// the path of step s: the largest p with path_off[p] <= s (empty paths share an offset with their successor)
-__device__ __forceinline__ uint32_t lf_path_of(const uint32_t *path_off, uint32_t np, uint32_t s) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (path_off[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+static_assert(LF_BLOCK == SR_STAGE_BLOCK, "the grids of sr_stage_grid");
 
 // ------------------------------------------------------------------ group 0: positions
-__global__ void __launch_bounds__(LF_BLOCK) lf_len_kernel(const uint32_t *steps, const uint32_t *len, uint32_t S, u64d *out) {
-    const uint32_t s = blockIdx.x * LF_BLOCK + threadIdx.x;
-    if (s < S) out[s] = len[(steps[s] >> 1) - 1];
-}
-
-// sinc = the inclusive scan over all steps -> the offset of a step in its own path
+// the step lengths and their inclusive scan: sr_stage_dev.h.  sinc = the inclusive scan over all steps -> the offset of a step in its own path
 __global__ void __launch_bounds__(LF_BLOCK) lf_pstart_kernel(const uint32_t *steps, const uint32_t *len, const uint32_t *path_off, uint32_t P,
                                                              const u64d *sinc, uint32_t S, u64d *pstart) {
     const uint32_t s = blockIdx.x * LF_BLOCK + threadIdx.x;
     if (s >= S) return;
-    const uint32_t a0 = path_off[lf_path_of(path_off, P, s)];
+    const uint32_t a0 = path_off[sr_path_of(path_off, P, s)];
     pstart[s] = sinc[s] - len[(steps[s] >> 1) - 1] - (a0 ? sinc[a0 - 1] : 0);
 }
 
@@ -92,7 +51,7 @@ __global__ void __launch_bounds__(LF_BLOCK) lf_first_kernel(const uint32_t *step
                                                             uint32_t T, int single, uint32_t *first) {
     const uint32_t s = s0 + blockIdx.x * LF_BLOCK + threadIdx.x;
     if (s >= s1) return;
-    const uint32_t t = single ? 0u : lf_path_of(path_off, P, s);
+    const uint32_t t = single ? 0u : sr_path_of(path_off, P, s);
     atomicMin(&first[(size_t)((steps[s] >> 1) - 1) * T + t], s);
 }
 
@@ -165,14 +124,8 @@ __global__ void __launch_bounds__(LF_BLOCK) lf_long_kernel(SrLiftTables g, LfQue
 
 namespace {
 
-double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the tables both executions read.  Node v = 1..V sits at index v - 1.
-struct LfTables {
-    uint32_t V = 0, S = 0, P = 0;
-    std::vector<uint32_t> len, steps, path_off;
+struct LfTables : SrPathTables {
     std::vector<uint64_t> plen;
     std::vector<uint32_t> target_path;
     bool to_named = false;
@@ -191,14 +144,13 @@ struct LfOutHost {
 };
 
 int lf_tables(const SrGraph &g, const std::vector<std::string> &names, const sr_lift_params &prm, LfTables &t) {
-    const uint64_t nn = g.node_seq.size() ? g.node_seq.size() - 1 : 0, ns = g.steps.size();
-    const uint64_t np = g.path_off.size() ? g.path_off.size() - 1 : 0;
-    if (nn >= 0x3fffffffULL || ns >= 0x7fffffffULL || np >= 0x7fffffffULL)
+    const SrPathSizes z = sr_path_sizes(g);
+    const uint64_t nn = z.nodes, np = z.paths;
+    if (nn >= 0x3fffffffULL || z.steps >= 0x7fffffffULL || np >= 0x7fffffffULL)
         return sr_fail(SR_ERR_UNSUPPORTED, "lift supports < 2^30 nodes and < 2^31 steps and paths");
-    t.V = (uint32_t)nn; t.S = (uint32_t)ns; t.P = (uint32_t)np; t.min_covered = prm.min_covered; t.short_steps = prm.short_steps;
+    t.min_covered = prm.min_covered; t.short_steps = prm.short_steps;
     if (prm.to_name) {
-        uint64_t p = 0;
-        while (p < np && (p >= names.size() || names[p] != prm.to_name)) p++;
+        const uint64_t p = sr_path_by_name(names, np, prm.to_name);
         if (p == np) return sr_fail(SR_ERR_INVALID, std::string("lift: no path is named '") + prm.to_name + "'");
         t.target_path.assign(1, (uint32_t)p); t.to_named = true;
     } else {
@@ -208,17 +160,7 @@ int lf_tables(const SrGraph &g, const std::vector<std::string> &names, const sr_
     if ((uint64_t)t.target_path.size() * nn > SR_LIFT_MAX_TABLE)
         return sr_fail(SR_ERR_UNSUPPORTED, "lift: " + std::to_string(t.target_path.size()) + " targets x " + std::to_string(nn) +
                                                " nodes; the first-visit table supports at most 2^28 entries");
-    t.len.assign(nn, 0);
-    for (uint64_t v = 1; v <= nn; v++) {
-        if (!g.node_alive[v]) return sr_fail(SR_ERR_INVALID, "lift: node ids must be dense");
-        if (g.node_seq[v].empty()) return sr_fail(SR_ERR_INVALID, "lift: a node has no sequence");
-        t.len[v - 1] = (uint32_t)g.node_seq[v].size();
-    }
-    t.steps = g.steps;
-    for (uint32_t h : t.steps)
-        if ((h >> 1) == 0 || (h >> 1) > nn) return sr_fail(SR_ERR_INVALID, "lift: a path step names a missing node");
-    t.path_off.resize(np + 1, 0);
-    for (uint64_t p = 0; p <= np && p < g.path_off.size(); p++) t.path_off[p] = (uint32_t)g.path_off[p];
+    if (const int r = sr_path_tables_fill(g, z, "lift", true, false, t)) return r;
     t.plen.assign(np, 0);
     for (uint64_t p = 0; p < np; p++)
         for (uint32_t s = t.path_off[p]; s < t.path_off[p + 1]; s++) t.plen[p] += t.len[(t.steps[s] >> 1) - 1];
@@ -324,71 +266,16 @@ int lf_run_host(const LfTables &t, LfOutHost &o) {
 }
 
 // ------------------------------------------------------------------ device execution
-struct LfStream {
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    int prev_device = -1;
-    std::vector<void *> bufs;
-    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int err = 0;
-    void chk(hipError_t e) { if (e != hipSuccess && !err) { err = SR_ERR_HIP; sr_fail(SR_ERR_HIP, std::string("lift: ") + hipGetErrorString(e)); } }
-    ~LfStream() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *b : bufs) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <class Tp> Tp *alloc(uint64_t n, int fill = -1) {             // fill: -1 none, else the byte
-        void *p = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(Tp);
-        if (err) return nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { err = SR_ERR_NOMEM; sr_fail(SR_ERR_NOMEM, "not enough device memory for the lift tables"); return nullptr; }
-        bufs.push_back(p);
-        if (fill >= 0) chk(hipMemsetAsync(p, fill, bytes, st));
-        return (Tp *)p;
-    }
-    void put(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); }
-    void get(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); }
-    void mark(int i) { if (!err) chk(hipEventRecord(ev[i], st)); }
-    void sync() { if (!err) chk(hipStreamSynchronize(st)); }
-};
-
-unsigned lf_grid(uint64_t n) { return (unsigned)((n + LF_BLOCK - 1) / LF_BLOCK); }
-
-// inclusive scan of data[0..n) in place; `sums` holds the block sums of every level (lf_scan_room elements)
-uint64_t lf_scan_room(uint64_t n) {
-    uint64_t room = 0;
-    while (n > 1) { n = (n + LF_BLOCK - 1) / LF_BLOCK; room += n; }
-    return room + 1;
-}
-void lf_scan(LfStream &x, u64d *data, uint32_t n, u64d *sums) {
-    if (x.err || !n) return;
-    const unsigned blocks = lf_grid(n);
-    hipLaunchKernelGGL(lf_scan_block_kernel, dim3(blocks), dim3(LF_BLOCK), 0, x.st, data, n, sums);
-    if (blocks == 1) return;
-    lf_scan(x, sums, blocks, sums + blocks);
-    hipLaunchKernelGGL(lf_scan_carry_kernel, dim3(blocks), dim3(LF_BLOCK), 0, x.st, data, n, (const u64d *)sums);
-}
-
 int lf_run_device(const LfTables &t, int device, void *stream, LfOutHost &o) {
     const uint32_t V = t.V, S = t.S, P = t.P, Q = (uint32_t)t.q_path.size(), T = (uint32_t)t.target_path.size();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sr_fail(SR_ERR_NO_DEVICE, "lift: no HIP device (device -1 selects the host twin)");
-    if (device >= ndev) return sr_fail(SR_ERR_INVALID, "lift: no HIP device " + std::to_string(device));
+    SrStage x("lift", "the lift tables");
+    if (x.open(device, stream, 7)) return x.err;
     o.variant = SR_LIFT_VARIANT_DEVICE;
     const uint64_t pairs = (uint64_t)Q * T;                     // <= 2^26
     o.tstart.assign(pairs, 0); o.tend.assign(pairs, 0); o.covered.assign(pairs, 0); o.rev_bp.assign(pairs, 0);
     if (!pairs) return SR_OK;                                    // no query or no target: nothing to lift (a query implies a step)
-    LfStream x;
-    x.chk(hipGetDevice(&x.prev_device));
-    x.chk(hipSetDevice(device));
-    x.st = (hipStream_t)stream;
-    if (!x.st && !x.err) { x.chk(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking)); x.own_stream = !x.err; }
-    for (hipEvent_t &e : x.ev) if (!x.err) x.chk(hipEventCreate(&e));
-    if (x.err) return x.err;
 
-    const uint64_t room = std::max(lf_scan_room(S), lf_scan_room(Q));
+    const uint64_t room = std::max(sr_scan_room(S), sr_scan_room(Q));
     uint32_t *d_len = x.alloc<uint32_t>(V), *d_steps = x.alloc<uint32_t>(S), *d_poff = x.alloc<uint32_t>((uint64_t)P + 1);
     u64d *d_sinc = x.alloc<u64d>(S), *d_pstart = x.alloc<u64d>(S), *d_sums = x.alloc<u64d>(room);
     uint32_t *d_first = x.alloc<uint32_t>((uint64_t)V * T, 0xff);
@@ -401,30 +288,30 @@ int lf_run_device(const LfTables &t, int device, void *stream, LfOutHost &o) {
     x.put(d_qpath, t.q_path.data(), (size_t)Q * 4); x.put(d_qstart, t.q_start.data(), (size_t)Q * 8); x.put(d_qend, t.q_end.data(), (size_t)Q * 8);
     const SrLiftTables g{d_steps, d_len, d_pstart};
     const LfQueries q{d_qpath, d_qstart, d_qend, Q};
-    const dim3 blk(LF_BLOCK), gs(lf_grid(S)), gq(lf_grid(Q));
+    const dim3 blk(LF_BLOCK), gs(sr_stage_grid(S)), gq(sr_stage_grid(Q));
     const bool single = t.to_named;
     const uint32_t f0 = single ? t.path_off[t.target_path[0]] : 0, f1 = single ? t.path_off[t.target_path[0] + 1] : S;
 
     x.mark(0);                                                   // ---- positions
     if (!x.err) {
-        hipLaunchKernelGGL(lf_len_kernel, gs, blk, 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_len, S, d_sinc);
-        lf_scan(x, d_sinc, S, d_sums);
+        sr_step_len(x, d_steps, d_len, S, d_sinc);
+        sr_scan<false>(x, d_sinc, S, d_sums);
         hipLaunchKernelGGL(lf_pstart_kernel, gs, blk, 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_len, (const uint32_t *)d_poff, P,
                            (const u64d *)d_sinc, S, d_pstart);
     }
     x.mark(1);                                                   // ---- first visits
     if (!x.err && f1 > f0)
-        hipLaunchKernelGGL(lf_first_kernel, dim3(lf_grid(f1 - f0)), blk, 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_poff, P, f0, f1, T,
+        hipLaunchKernelGGL(lf_first_kernel, dim3(sr_stage_grid(f1 - f0)), blk, 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_poff, P, f0, f1, T,
                            single ? 1 : 0, d_first);
     x.mark(2);                                                   // ---- locate
     if (!x.err) {
         hipLaunchKernelGGL(lf_locate_kernel, gq, blk, 0, x.st, q, (const uint32_t *)d_poff, (const u64d *)d_pstart, (u64d)t.short_steps, d_slo, d_shi, d_long);
-        lf_scan(x, d_long, Q, d_sums);
+        sr_scan<false>(x, d_long, Q, d_sums);
         hipLaunchKernelGGL(lf_compact_kernel, gq, blk, 0, x.st, (const u64d *)d_long, Q, d_list);
     }
     x.mark(3);                                                   // ---- short pairs
     if (!x.err)
-        hipLaunchKernelGGL(lf_short_kernel, dim3(lf_grid(pairs)), blk, 0, x.st, g, q, (const uint32_t *)d_slo, (const uint32_t *)d_shi, (const u64d *)d_long,
+        hipLaunchKernelGGL(lf_short_kernel, dim3(sr_stage_grid(pairs)), blk, 0, x.st, g, q, (const uint32_t *)d_slo, (const uint32_t *)d_shi, (const u64d *)d_long,
                            (const uint32_t *)d_first, T, out);
     x.mark(4);                                                   // ---- long pairs
     if (!x.err)
@@ -439,14 +326,8 @@ int lf_run_device(const LfTables &t, int device, void *stream, LfOutHost &o) {
     x.mark(6);
     x.sync();                                                    // the synchronisation after the download, the only one
     if (x.err) return x.err;
-    float total = 0.f;
-    x.chk(hipEventElapsedTime(&total, x.ev[0], x.ev[6]));
-    o.us = (uint64_t)(total * 1000.0 + 0.5);
-    for (int k = 0; k < 5; k++) {
-        float ms = 0.f;
-        x.chk(hipEventElapsedTime(&ms, x.ev[k], x.ev[k + 1]));
-        o.kernel_us[k] = (uint64_t)(ms * 1000.0 + 0.5);
-    }
+    o.us = x.us(0, 6);
+    for (int k = 0; k < 5; k++) o.kernel_us[k] = x.us(k, k + 1);
     o.long_pairs = n_long * T; o.short_pairs = pairs - o.long_pairs;
     return x.err;
 }
@@ -527,7 +408,6 @@ extern "C" int sr_lift_bed(const sr_lift *l, const char *const *names, char **te
     const uint64_t Q = l->queries, T = l->targets;
     if (Q * (T ? T : 1) > SR_LIFT_MAX_PAIRS) return sr_fail(SR_ERR_INVALID, "lift: not a result of sr_lift_gfa");
     try {
-        auto u64s = [](uint64_t x) { return std::to_string((unsigned long long)x); };
         std::string o;
         for (uint64_t i = 0; i < Q; i++) {
             const uint32_t a = l->q_path[i];
@@ -542,10 +422,7 @@ extern "C" int sr_lift_bed(const sr_lift *l, const char *const *names, char **te
                 o += names[a]; o += "\t" + u64s(l->q_start[i]) + "\t" + u64s(l->q_end[i]) + "\t" + u64s(l->rev_bp[n]) + "\n";
             }
         }
-        char *res = (char *)malloc(o.size() + 1);
-        if (!res) return sr_fail(SR_ERR_NOMEM, "not enough memory for the lifted intervals");
-        memcpy(res, o.c_str(), o.size() + 1);
-        *text = res;
+        return sr_give_text(o, text, "not enough memory for the lifted intervals");
     } catch (const std::bad_alloc &) {
         return sr_fail(SR_ERR_NOMEM, "not enough memory for the lifted intervals");
     }

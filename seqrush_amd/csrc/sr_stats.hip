@@ -8,7 +8,6 @@
 // one 32 KiB LDS accumulator per (tile pair, node chunk);  layout -> per-path error sums by a segmented wave reduction;
 // topology -> side flags, self loops, union-find (sr_uf_dev.h), tips and roots.  No captured graph.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +16,8 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_sort.h"
+#include "sr_stage_host.h"
+#include "sr_stage_dev.h"
 #include "sr_uf_dev.h"
 #include "sr_stats_rule.h"
 
@@ -33,16 +34,6 @@ __device__ __forceinline__ u64d st_wave_sum(u64d v) {
     return v;                                        // lane 0 holds the wave's sum
 }
 
-// the path of step s: the largest p with path_off[p] <= s (empty paths share an offset with their successor)
-__device__ __forceinline__ uint32_t st_path_of(const uint32_t *path_off, uint32_t np, uint32_t s) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (path_off[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // ------------------------------------------------------------------ steps
 __global__ void __launch_bounds__(ST_BLOCK) st_steps_kernel(const uint32_t *steps, uint32_t S, const uint32_t *path_off, uint32_t np,
                                                             uint32_t W, uint32_t *depth, u64d *bits, u64d *sc) {
@@ -50,7 +41,7 @@ __global__ void __launch_bounds__(ST_BLOCK) st_steps_kernel(const uint32_t *step
     u64d rev = 0;
     for (uint64_t s = (uint64_t)blockIdx.x * ST_BLOCK + threadIdx.x; s < S; s += stride) {
         const uint32_t h = steps[s], node = h >> 1;
-        const uint32_t p = st_path_of(path_off, np, (uint32_t)s);
+        const uint32_t p = sr_path_of(path_off, np, (uint32_t)s);
         atomicAdd(&depth[node], 1u);
         atomicOr(&bits[(uint64_t)node * W + (p >> 6)], 1ULL << (p & 63u));
         rev += h & 1u;
@@ -159,7 +150,7 @@ __global__ void __launch_bounds__(ST_BLOCK) st_layout_kernel(const uint32_t *ste
 #pragma unroll
     for (int k = 0; k < LY_N; k++) val[k] = 0;
     if (s < S) {
-        p = st_path_of(path_off, np, (uint32_t)s);
+        p = sr_path_of(path_off, np, (uint32_t)s);
         if (s + 1 < path_off[p + 1]) {
             const uint32_t a = steps[s] >> 1, b = steps[s + 1] >> 1;
             const uint64_t e = sr_stats_pair_error(pos[a], pos[b], len[a]);
@@ -223,39 +214,23 @@ __global__ void __launch_bounds__(ST_BLOCK) st_count_kernel(uint32_t V, const ui
 
 namespace {
 
-double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the tables both executions read: node v = 1..V at index v, slot 0 unused (length 0)
-struct StTables {
-    uint32_t V = 0, S = 0, E = 0, P = 0, W = 0;
-    std::vector<uint32_t> len, steps, path_off;
+struct StTables : SrPathTables {
+    uint32_t E = 0, W = 0;
     std::vector<u64d> edges;
 };
 
 int st_tables(const SrGraph &g, StTables &t) {
-    const uint64_t nn = g.node_seq.size() ? g.node_seq.size() - 1 : 0, ns = g.steps.size(), ne = g.edges.size();
-    const uint64_t np = g.path_off.size() ? g.path_off.size() - 1 : 0;
+    const SrPathSizes z = sr_path_sizes(g);
+    const uint64_t nn = z.nodes, ne = z.edges, np = z.paths;
     if (np > SR_STATS_MAX_PATHS)
         return sr_fail(SR_ERR_UNSUPPORTED, "stats: " + std::to_string(np) + " paths; the path bitset and the similarity matrix support at most " +
                                                std::to_string(SR_STATS_MAX_PATHS));
-    uint64_t bases = 0;
-    for (uint64_t v = 1; v <= nn; v++) bases += g.node_seq[v].size();
-    if (nn >= 0x3fffffffULL || ns >= 0x7fffffffULL || ne >= 0x7fffffffULL || bases >= 0x7fffffffULL)
+    if (nn >= 0x3fffffffULL || z.steps >= 0x7fffffffULL || ne >= 0x7fffffffULL || z.bases >= 0x7fffffffULL)
         return sr_fail(SR_ERR_UNSUPPORTED, "stats supports < 2^30 nodes and < 2^31 steps, edges and bases");
-    t.V = (uint32_t)nn; t.S = (uint32_t)ns; t.E = (uint32_t)ne; t.P = (uint32_t)np; t.W = (uint32_t)((np + 63) / 64);
+    t.E = (uint32_t)ne; t.W = (uint32_t)((np + 63) / 64);
     if (t.W == 0) t.W = 1;
-    t.len.assign(nn + 1, 0);
-    for (uint64_t v = 1; v <= nn; v++) {
-        if (!g.node_alive[v]) return sr_fail(SR_ERR_INVALID, "stats: node ids must be dense");
-        t.len[v] = (uint32_t)g.node_seq[v].size();
-    }
-    t.steps = g.steps;
-    for (uint32_t h : t.steps)
-        if ((h >> 1) == 0 || (h >> 1) > nn) return sr_fail(SR_ERR_INVALID, "stats: a path step names a missing node");
-    t.path_off.resize(np + 1, 0);
-    for (uint64_t p = 0; p <= np && p < g.path_off.size(); p++) t.path_off[p] = (uint32_t)g.path_off[p];
+    if (const int r = sr_path_tables_fill(g, z, "stats", false, true, t)) return r;
     t.edges.resize(ne);
     for (uint64_t i = 0; i < ne; i++) {
         const uint32_t a = g.edges[i].first, b = g.edges[i].second;
@@ -366,35 +341,6 @@ void st_run_host(const StTables &t, sr_graph_stats *r) {
 }
 
 // ------------------------------------------------------------------ device execution
-struct StDev {
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    int prev_device = -1;
-    std::vector<void *> bufs;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int err = 0;
-    void chk(hipError_t e) { if (e != hipSuccess && !err) { err = SR_ERR_HIP; sr_fail(SR_ERR_HIP, std::string("stats: ") + hipGetErrorString(e)); } }
-    ~StDev() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *b : bufs) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <class Tp> Tp *alloc(uint64_t n, bool zero) {
-        void *p = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(Tp);
-        if (err) return nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { err = SR_ERR_NOMEM; sr_fail(SR_ERR_NOMEM, "not enough device memory for the statistics stage"); return nullptr; }
-        bufs.push_back(p);
-        if (zero) chk(hipMemsetAsync(p, 0, bytes, st));
-        return (Tp *)p;
-    }
-    void put(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); }
-    void get(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); }
-    void mark(int i) { if (!err) chk(hipEventRecord(ev[i], st)); }
-};
-
 unsigned st_grid(uint64_t n) {
     uint64_t b = (n + ST_BLOCK - 1) / ST_BLOCK;
     return (unsigned)(b > 8192 ? 8192 : (b ? b : 1));
@@ -402,25 +348,17 @@ unsigned st_grid(uint64_t n) {
 
 int st_run_device(const StTables &t, int device, void *stream, sr_graph_stats *r) {
     const uint32_t V = t.V, S = t.S, E = t.E, P = t.P, W = t.W;
-    StDev x;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sr_fail(SR_ERR_NO_DEVICE, "stats: no HIP device (device -1 selects the host twin)");
-    if (device >= ndev) return sr_fail(SR_ERR_INVALID, "stats: no HIP device " + std::to_string(device));
-    x.chk(hipGetDevice(&x.prev_device));
-    x.chk(hipSetDevice(device));
-    x.st = (hipStream_t)stream;
-    if (!x.st && !x.err) { x.chk(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking)); x.own_stream = !x.err; }
-    for (hipEvent_t &e : x.ev) if (!x.err) x.chk(hipEventCreate(&e));
-    if (x.err) return x.err;
+    SrStage x("stats", "the statistics stage");
+    if (x.open(device, stream, 6)) return x.err;
 
     const uint64_t nv = (uint64_t)V + 1;
-    uint32_t *d_len = x.alloc<uint32_t>(nv, false), *d_pos = x.alloc<uint32_t>(nv, true), *d_steps = x.alloc<uint32_t>(S, false);
-    uint32_t *d_poff = x.alloc<uint32_t>((uint64_t)P + 1, false), *d_depth = x.alloc<uint32_t>(nv, true), *d_pon = x.alloc<uint32_t>(nv, true);
-    uint32_t *d_tile = x.alloc<uint32_t>(nv / 1024 + 2, false), *d_grand = x.alloc<uint32_t>(1, true);
-    u64d *d_edges = x.alloc<u64d>(E, false), *d_bits = x.alloc<u64d>(nv * W, true), *d_sc = x.alloc<u64d>(ST_NSC, true);
-    u64d *d_hbp = x.alloc<u64d>((uint64_t)P + 1, true), *d_hn = x.alloc<u64d>((uint64_t)P + 1, true);
-    u64d *d_shared = x.alloc<u64d>((uint64_t)P * P, true), *d_pp = x.alloc<u64d>((uint64_t)P * LY_N, true), *d_uf = x.alloc<u64d>(nv, false);
-    uint8_t *d_side = x.alloc<uint8_t>(2 * nv, true);
+    uint32_t *d_len = x.alloc<uint32_t>(nv), *d_pos = x.alloc<uint32_t>(nv, 0), *d_steps = x.alloc<uint32_t>(S);
+    uint32_t *d_poff = x.alloc<uint32_t>((uint64_t)P + 1), *d_depth = x.alloc<uint32_t>(nv, 0), *d_pon = x.alloc<uint32_t>(nv, 0);
+    uint32_t *d_tile = x.alloc<uint32_t>(nv / 1024 + 2), *d_grand = x.alloc<uint32_t>(1, 0);
+    u64d *d_edges = x.alloc<u64d>(E), *d_bits = x.alloc<u64d>(nv * W, 0), *d_sc = x.alloc<u64d>(ST_NSC, 0);
+    u64d *d_hbp = x.alloc<u64d>((uint64_t)P + 1, 0), *d_hn = x.alloc<u64d>((uint64_t)P + 1, 0);
+    u64d *d_shared = x.alloc<u64d>((uint64_t)P * P, 0), *d_pp = x.alloc<u64d>((uint64_t)P * LY_N, 0), *d_uf = x.alloc<u64d>(nv);
+    uint8_t *d_side = x.alloc<uint8_t>(2 * nv, 0);
     if (x.err) return x.err;
     x.put(d_len, t.len.data(), nv * 4); x.put(d_steps, t.steps.data(), (size_t)S * 4); x.put(d_poff, t.path_off.data(), ((size_t)P + 1) * 4);
     x.put(d_edges, t.edges.data(), (size_t)E * 8);
@@ -455,7 +393,7 @@ int st_run_device(const StTables &t, int device, void *stream, sr_graph_stats *r
     if (V) { x.get(r->depth, d_depth + 1, (size_t)V * 4); x.get(r->paths_on, d_pon + 1, (size_t)V * 4); }
     x.get(r->bp_by_paths, d_hbp, ((size_t)P + 1) * 8); x.get(r->nodes_by_paths, d_hn, ((size_t)P + 1) * 8);
     x.get(r->shared, d_shared, (size_t)P * P * 8); x.get(pp.data(), d_pp, pp.size() * 8);
-    if (!x.err) x.chk(hipStreamSynchronize(x.st));       // the one synchronisation
+    x.sync();                                        // the one synchronisation
     if (x.err) return x.err;
     if (sc[ST_ERR]) return sr_fail(SR_ERR_DEVICE_FAULT, "stats: union-find retry bound hit");
     r->length = sc[ST_LENGTH]; r->depth_bp = sc[ST_DEPTH_BP]; r->rev_steps = sc[ST_REV]; r->self_loops = sc[ST_LOOPS];
@@ -466,14 +404,8 @@ int st_run_device(const StTables &t, int device, void *stream, sr_graph_stats *r
         r->path_sq[p * 3] = pp[(uint64_t)p * LY_N + LY_HH]; r->path_sq[p * 3 + 1] = pp[(uint64_t)p * LY_N + LY_HL];
         r->path_sq[p * 3 + 2] = pp[(uint64_t)p * LY_N + LY_LL];
     }
-    float total = 0.f;
-    x.chk(hipEventElapsedTime(&total, x.ev[0], x.ev[5]));
-    r->stats_us = (uint64_t)(total * 1000.0 + 0.5);
-    for (int k = 0; k < 5; k++) {
-        float ms = 0.f;
-        x.chk(hipEventElapsedTime(&ms, x.ev[k], x.ev[k + 1]));
-        r->kernel_us[k] = (uint64_t)(ms * 1000.0 + 0.5);
-    }
+    r->stats_us = x.us(0, 5);
+    for (int k = 0; k < 5; k++) r->kernel_us[k] = x.us(k, k + 1);
     return x.err;
 }
 
@@ -493,7 +425,6 @@ std::string ratio(double num, double den, double scale = 1.0) {
     snprintf(buf, sizeof buf, "%.6f", num / den * scale);
     return buf;
 }
-std::string u64s(uint64_t v) { return std::to_string((unsigned long long)v); }
 
 }   // namespace
 
@@ -589,9 +520,5 @@ extern "C" int sr_graph_stats_report(const sr_graph_stats *s, const char *const 
     o += "layout\tnormalized_mae\t" + ratio((double)s->total_abs, (double)s->length) + "\n";
     // overall_mae / (total_path_length / total_steps) * 100 (measure_layout_quality.rs:209)
     o += "layout\trelative_error_pct\t" + (n > 0 ? ratio(mae, (double)s->total_len / n, 100.0) : std::string("NA")) + "\n";
-    char *res = (char *)malloc(o.size() + 1);
-    if (!res) return sr_fail(SR_ERR_NOMEM, "not enough memory for the report");
-    memcpy(res, o.c_str(), o.size() + 1);
-    *text = res;
-    return SR_OK;
+    return sr_give_text(o, text, "not enough memory for the report");
 }

@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,42 +24,15 @@
 #include "../../include/seqrush_amd.h"
 #include "sr_internal.h"
 #include "sr_sort.h"
+#include "sr_stage_host.h"
+#include "sr_stage_dev.h"
 #include "sr_variants_rule.h"
 
 #define VA_BLOCK 256
-#define VA_WAVES (VA_BLOCK / 64)
 
 typedef unsigned long long u64d;
 
-// ------------------------------------------------------------------ scans
-// inclusive scan of n u64 values in place, sum or max (identity 0 for both): wave shuffles, an LDS combine across the
-// workgroup, and a block-sums pass as the carry across workgroups (va_scan below recurses on the sums)
-template <bool MAX> __device__ __forceinline__ u64d va_op(u64d a, u64d b) { return MAX ? (a > b ? a : b) : a + b; }
-
-template <bool MAX> __global__ void __launch_bounds__(VA_BLOCK) va_scan_block_kernel(u64d *data, uint32_t n, u64d *sums) {
-    __shared__ u64d wsum[VA_WAVES];
-    const uint32_t i = blockIdx.x * VA_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64d v = i < n ? data[i] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64d t = __shfl_up(v, o, 64);
-        if ((int)lane >= o) v = va_op<MAX>(v, t);
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    u64d carry = 0;
-#pragma unroll
-    for (int w = 0; w < VA_WAVES; w++) if (w < (int)wave) carry = va_op<MAX>(carry, wsum[w]);
-    v = va_op<MAX>(v, carry);
-    if (i < n) data[i] = v;
-    if (threadIdx.x == VA_BLOCK - 1) sums[blockIdx.x] = v;     // lanes beyond n carry the last value on
-}
-
-template <bool MAX> __global__ void __launch_bounds__(VA_BLOCK) va_scan_carry_kernel(u64d *data, uint32_t n, const u64d *sums) {
-    const uint32_t i = blockIdx.x * VA_BLOCK + threadIdx.x;
-    if (blockIdx.x == 0 || i >= n) return;
-    data[i] = va_op<MAX>(data[i], sums[blockIdx.x - 1]);
-}
+static_assert(VA_BLOCK == SR_STAGE_BLOCK, "the grids of sr_stage_grid");
 
 // ------------------------------------------------------------------ tables on the device
 struct VaDev {
@@ -73,16 +45,6 @@ struct VaDev {
     uint32_t V, S, P;
     uint64_t max_len, hash_mask;
 };
-
-// the path of step s: the largest p with path_off[p] <= s (empty paths share an offset with their successor)
-__device__ __forceinline__ uint32_t va_path_of(const uint32_t *path_off, uint32_t np, uint32_t s) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (path_off[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ u64d va_spos_ex(const VaDev &d, uint32_t s) { return s ? d.spos[s - 1] : 0; }
 
@@ -99,11 +61,7 @@ __device__ __forceinline__ void va_count_by_path(bool flag, uint32_t p, u64d *ta
 }
 
 // ------------------------------------------------------------------ group 0: anchors
-__global__ void __launch_bounds__(VA_BLOCK) va_len_kernel(const uint32_t *steps, const uint32_t *len, uint32_t S, u64d *out) {
-    const uint32_t s = blockIdx.x * VA_BLOCK + threadIdx.x;
-    if (s < S) out[s] = len[(steps[s] >> 1) - 1];
-}
-
+// the step lengths and the scans (sum and max): sr_stage_dev.h
 __global__ void __launch_bounds__(VA_BLOCK) va_visits_kernel(const uint32_t *steps, uint32_t s0, uint32_t s1, uint32_t *visits) {
     const uint32_t s = s0 + blockIdx.x * VA_BLOCK + threadIdx.x;
     if (s < s1) atomicAdd(&visits[(steps[s] >> 1) - 1], 1u);
@@ -155,7 +113,7 @@ __global__ void __launch_bounds__(VA_BLOCK) va_classify_kernel(VaDev d, uint8_t 
     uint32_t p = 0, f = 0;
     bool brk = false, skp = false;
     if (live && d.visits[(d.g.steps[s] >> 1) - 1] == 1) {
-        p = va_path_of(d.path_off, d.P, s);
+        p = sr_path_of(d.path_off, d.P, s);
         const VaPair q = va_pair(d, s, p);
         brk = q.cls == SR_VAR_BREAK; skp = q.cls == SR_VAR_SKIPPED;
         f = VA_F_ANCHOR | (q.cls == SR_VAR_TRAVERSAL ? VA_F_TRAV : 0u) | (q.cls == SR_VAR_ADJACENT && q.i + 1 == s ? 0u : VA_F_HEAD);
@@ -174,7 +132,7 @@ __global__ void __launch_bounds__(VA_BLOCK) va_scatter_kernel(VaDev d, const uin
     if (s >= d.S) return;
     const uint32_t f = cls[s];
     if (!(f & VA_F_ANCHOR)) return;
-    const uint32_t p = va_path_of(d.path_off, d.P, s);
+    const uint32_t p = sr_path_of(d.path_off, d.P, s);
     const u64d c = cnt[s];
     if (f & VA_F_TRAV) {
         const VaPair q = va_pair(d, s, p);
@@ -347,15 +305,10 @@ __global__ void __launch_bounds__(VA_BLOCK) va_gt_kernel(const uint32_t *site_so
 
 namespace {
 
-double us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the tables both executions read.  Node v = 1..V sits at index v - 1.
-struct VaTables {
-    uint32_t V = 0, S = 0, P = 0, R = 0;
+struct VaTables : SrPathTables {
+    uint32_t R = 0;
     uint64_t max_len = 0, hash_mask = ~0ULL;
-    std::vector<uint32_t> len, steps, path_off;
     std::vector<uint64_t> seq_off;
     std::vector<uint8_t> seq;
     std::string refseq;
@@ -373,32 +326,22 @@ struct VaOut {
 };
 
 int va_tables(const SrGraph &g, const std::vector<std::string> &names, const sr_variant_params &prm, VaTables &t) {
-    const uint64_t nn = g.node_seq.size() ? g.node_seq.size() - 1 : 0, ns = g.steps.size();
-    const uint64_t np = g.path_off.size() ? g.path_off.size() - 1 : 0;
-    uint64_t bases = 0;
-    for (uint64_t v = 1; v <= nn; v++) bases += g.node_seq[v].size();
-    if (nn >= 0x3fffffffULL || ns >= 0x7fffffffULL || np >= 0x7fffffffULL || bases >= 0x7fffffffULL)
+    const SrPathSizes z = sr_path_sizes(g);
+    const uint64_t nn = z.nodes, np = z.paths;
+    if (nn >= 0x3fffffffULL || z.steps >= 0x7fffffffULL || np >= 0x7fffffffULL || z.bases >= 0x7fffffffULL)
         return sr_fail(SR_ERR_UNSUPPORTED, "variants support < 2^30 nodes and < 2^31 steps, paths and bases");
-    t.V = (uint32_t)nn; t.S = (uint32_t)ns; t.P = (uint32_t)np; t.max_len = prm.max_allele_len; t.hash_mask = prm.hash_mask;
+    t.max_len = prm.max_allele_len; t.hash_mask = prm.hash_mask;
     if (prm.ref_name) {
-        uint64_t p = 0;
-        while (p < np && (p >= names.size() || names[p] != prm.ref_name)) p++;
+        const uint64_t p = sr_path_by_name(names, np, prm.ref_name);
         if (p == np) return sr_fail(SR_ERR_INVALID, std::string("variants: no path is named '") + prm.ref_name + "'");
         t.R = (uint32_t)p;
     }
-    t.len.assign(nn, 0); t.seq_off.assign(nn + 1, 0); t.seq.reserve(bases);
+    if (const int r = sr_path_tables_fill(g, z, "variants", true, false, t)) return r;
+    t.seq_off.assign(nn + 1, 0); t.seq.reserve(z.bases);
     for (uint64_t v = 1; v <= nn; v++) {
-        if (!g.node_alive[v]) return sr_fail(SR_ERR_INVALID, "variants: node ids must be dense");
-        if (g.node_seq[v].empty()) return sr_fail(SR_ERR_INVALID, "variants: a node has no sequence");
-        t.len[v - 1] = (uint32_t)g.node_seq[v].size();
         t.seq.insert(t.seq.end(), g.node_seq[v].begin(), g.node_seq[v].end());
         t.seq_off[v] = t.seq.size();
     }
-    t.steps = g.steps;
-    for (uint32_t h : t.steps)
-        if ((h >> 1) == 0 || (h >> 1) > nn) return sr_fail(SR_ERR_INVALID, "variants: a path step names a missing node");
-    t.path_off.resize(np + 1, 0);
-    for (uint64_t p = 0; p <= np && p < g.path_off.size(); p++) t.path_off[p] = (uint32_t)g.path_off[p];
     if (np) {
         uint64_t L = 0;
         for (uint32_t s = t.path_off[t.R]; s < t.path_off[t.R + 1]; s++) L += t.len[(t.steps[s] >> 1) - 1];
@@ -510,54 +453,7 @@ int va_run_host(const VaTables &t, VaOut &o) {
 }
 
 // ------------------------------------------------------------------ device execution
-struct VaStream {
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    int prev_device = -1;
-    std::vector<void *> bufs;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int err = 0;
-    void chk(hipError_t e) { if (e != hipSuccess && !err) { err = SR_ERR_HIP; sr_fail(SR_ERR_HIP, std::string("variants: ") + hipGetErrorString(e)); } }
-    ~VaStream() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *b : bufs) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <class Tp> Tp *alloc(uint64_t n, int fill = -1) {             // fill: -1 none, else the byte
-        void *p = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(Tp);
-        if (err) return nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { err = SR_ERR_NOMEM; sr_fail(SR_ERR_NOMEM, "not enough device memory for the variant tables"); return nullptr; }
-        bufs.push_back(p);
-        if (fill >= 0) chk(hipMemsetAsync(p, fill, bytes, st));
-        return (Tp *)p;
-    }
-    void put(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); }
-    void get(void *dst, const void *src, size_t bytes) { if (!err && bytes) chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); }
-    void mark(int i) { if (!err) chk(hipEventRecord(ev[i], st)); }
-    void sync() { if (!err) chk(hipStreamSynchronize(st)); }
-};
-
-unsigned va_grid(uint64_t n) { return (unsigned)((n + VA_BLOCK - 1) / VA_BLOCK); }
-
-// inclusive scan of data[0..n) in place; `sums` holds the block sums of every level (va_scan_room elements)
-uint64_t va_scan_room(uint64_t n) {
-    uint64_t room = 0;
-    while (n > 1) { n = (n + VA_BLOCK - 1) / VA_BLOCK; room += n; }
-    return room + 1;
-}
-template <bool MAX> void va_scan(VaStream &x, u64d *data, uint32_t n, u64d *sums) {
-    if (x.err || !n) return;
-    const unsigned blocks = va_grid(n);
-    hipLaunchKernelGGL(va_scan_block_kernel<MAX>, dim3(blocks), dim3(VA_BLOCK), 0, x.st, data, n, sums);
-    if (blocks == 1) return;
-    va_scan<MAX>(x, sums, blocks, sums + blocks);
-    hipLaunchKernelGGL(va_scan_carry_kernel<MAX>, dim3(blocks), dim3(VA_BLOCK), 0, x.st, data, n, (const u64d *)sums);
-}
-
-template <class K> void va_sort(VaStream &x, void *temp, size_t temp_bytes, K *kin, K *kout, uint32_t *vin, uint32_t *vout, uint32_t n, unsigned bits) {
+template <class K> void va_sort(SrStage &x, void *temp, size_t temp_bytes, K *kin, K *kout, uint32_t *vin, uint32_t *vout, uint32_t n, unsigned bits) {
     if (x.err || !n) return;
     size_t need = temp_bytes;
     x.chk(rocprim::radix_sort_pairs(temp, need, kin, kout, vin, vout, (size_t)n, 0, bits, x.st));
@@ -565,26 +461,18 @@ template <class K> void va_sort(VaStream &x, void *temp, size_t temp_bytes, K *k
 
 int va_run_device(const VaTables &t, int device, void *stream, VaOut &o) {
     const uint32_t V = t.V, S = t.S, P = t.P;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sr_fail(SR_ERR_NO_DEVICE, "variants: no HIP device (device -1 selects the host twin)");
-    if (device >= ndev) return sr_fail(SR_ERR_INVALID, "variants: no HIP device " + std::to_string(device));
+    SrStage x("variants", "the variant tables");
+    if (x.open(device, stream, 8)) return x.err;
     o.variant = SR_VARIANTS_VARIANT_DEVICE;
     o.breaks.assign(P, 0); o.skipped.assign(P, 0);
     const uint32_t s0 = P ? t.path_off[t.R] : 0, s1 = P ? t.path_off[t.R + 1] : 0;
     if (!P || !S || s0 == s1) return SR_OK;                      // no path, no step or a reference without steps: nothing to find
-    VaStream x;
-    x.chk(hipGetDevice(&x.prev_device));
-    x.chk(hipSetDevice(device));
-    x.st = (hipStream_t)stream;
-    if (!x.st && !x.err) { x.chk(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking)); x.own_stream = !x.err; }
-    for (hipEvent_t &e : x.ev) if (!x.err) x.chk(hipEventCreate(&e));
-    if (x.err) return x.err;
 
     uint32_t *d_len = x.alloc<uint32_t>(V), *d_steps = x.alloc<uint32_t>(S), *d_poff = x.alloc<uint32_t>((uint64_t)P + 1);
     uint64_t *d_soff = x.alloc<uint64_t>((uint64_t)V + 1);
     uint8_t *d_seq = x.alloc<uint8_t>(t.seq.size()), *d_ref = x.alloc<uint8_t>(t.refseq.size());
     uint32_t *d_visits = x.alloc<uint32_t>(V, 0), *d_refpr = x.alloc<uint32_t>(V, 0);
-    u64d *d_spos = x.alloc<u64d>(S), *d_prev = x.alloc<u64d>(S), *d_cnt = x.alloc<u64d>(S), *d_sums = x.alloc<u64d>(va_scan_room(S));
+    u64d *d_spos = x.alloc<u64d>(S), *d_prev = x.alloc<u64d>(S), *d_cnt = x.alloc<u64d>(S), *d_sums = x.alloc<u64d>(sr_scan_room(S));
     u64d *d_breaks = x.alloc<u64d>(P, 0), *d_skipped = x.alloc<u64d>(P, 0), *d_counts = x.alloc<u64d>(4, 0);
     uint8_t *d_cls = x.alloc<uint8_t>((uint64_t)S + 1, 0);
     if (x.err) return x.err;
@@ -594,24 +482,24 @@ int va_run_device(const VaTables &t, int device, void *stream, VaOut &o) {
     d.g = SrVarGraph{d_steps, d_len, d_soff, d_seq};
     d.path_off = d_poff; d.visits = d_visits; d.ref_pr = d_refpr; d.spos = d_spos; d.prev = d_prev;
     d.V = V; d.S = S; d.P = P; d.max_len = t.max_len; d.hash_mask = t.hash_mask;
-    const dim3 blk(VA_BLOCK), gs(va_grid(S));
+    const dim3 blk(VA_BLOCK), gs(sr_stage_grid(S));
 
     x.mark(0);                                                   // ---- anchors
     if (!x.err) {
-        hipLaunchKernelGGL(va_len_kernel, gs, blk, 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_len, S, d_spos);
-        va_scan<false>(x, d_spos, S, d_sums);
-        hipLaunchKernelGGL(va_visits_kernel, dim3(va_grid(s1 - s0)), blk, 0, x.st, (const uint32_t *)d_steps, s0, s1, d_visits);
-        hipLaunchKernelGGL(va_refpos_kernel, dim3(va_grid(s1 - s0)), blk, 0, x.st, d, s0, s1, d_refpr, d_counts + 0);
+        sr_step_len(x, d_steps, d_len, S, d_spos);
+        sr_scan<false>(x, d_spos, S, d_sums);
+        hipLaunchKernelGGL(va_visits_kernel, dim3(sr_stage_grid(s1 - s0)), blk, 0, x.st, (const uint32_t *)d_steps, s0, s1, d_visits);
+        hipLaunchKernelGGL(va_refpos_kernel, dim3(sr_stage_grid(s1 - s0)), blk, 0, x.st, d, s0, s1, d_refpr, d_counts + 0);
     }
     x.mark(1);                                                   // ---- the previous anchor step
     if (!x.err) {
         hipLaunchKernelGGL(va_mark_kernel, gs, blk, 0, x.st, (const uint32_t *)d_steps, (const uint32_t *)d_visits, S, d_prev);
-        va_scan<true>(x, d_prev, S, d_sums);
+        sr_scan<true>(x, d_prev, S, d_sums);
     }
     x.mark(2);                                                   // ---- emit
     if (!x.err) {
         hipLaunchKernelGGL(va_classify_kernel, gs, blk, 0, x.st, d, d_cls, d_cnt, d_breaks, d_skipped);
-        va_scan<false>(x, d_cnt, S, d_sums);
+        sr_scan<false>(x, d_cnt, S, d_sums);
     }
     uint64_t totals = 0;
     x.get(&totals, d_cnt + (S - 1), 8);
@@ -638,7 +526,7 @@ int va_run_device(const VaTables &t, int device, void *stream, VaOut &o) {
     const size_t temp_bytes = tb64 > tb32 ? tb64 : tb32;
     void *d_temp = x.alloc<uint8_t>(temp_bytes);
     if (x.err) return x.err;
-    const dim3 gt_(va_grid(T));
+    const dim3 gt_(sr_stage_grid(T));
     if (!x.err) hipLaunchKernelGGL(va_scatter_kernel, gs, blk, 0, x.st, d, (const uint8_t *)d_cls, (const u64d *)d_cnt, rec, runs);
     x.mark(3);                                                   // ---- hash
     if (!x.err && T) hipLaunchKernelGGL(va_hash_kernel, gt_, blk, 0, x.st, d, rec, T, d_hash, d_iota);
@@ -651,14 +539,14 @@ int va_run_device(const VaTables &t, int device, void *stream, VaOut &o) {
         hipLaunchKernelGGL(va_key_ab_kernel, gt_, blk, 0, x.st, (const uint32_t *)d_p0, (const uint32_t *)rec.a, (const uint32_t *)rec.b, T, d_k64);
         va_sort<u64d>(x, d_temp, temp_bytes, d_k64, d_k64o, d_p0, d_p1, T, 64);                  // by (a, b, length, hash): d_p1
         hipLaunchKernelGGL(va_compare_kernel, gt_, blk, 0, x.st, d, rec, (const uint32_t *)d_p1, (const u64d *)d_hash, (const uint8_t *)d_ref, T, d_flags, d_site);
-        va_scan<false>(x, d_site, T, d_sums);
+        sr_scan<false>(x, d_site, T, d_sums);
         hipLaunchKernelGGL(va_clash_kernel, gt_, blk, 0, x.st, (const uint8_t *)d_flags, (const u64d *)d_site, T, d_coll);
         hipLaunchKernelGGL(va_class_kernel, gt_, blk, 0, x.st, d, rec, (const uint32_t *)d_p1, (const uint8_t *)d_ref, d_flags, (const u64d *)d_site,
                            (const uint32_t *)d_coll, T, d_keep, d_class);
-        va_scan<false>(x, d_class, T, d_sums);
+        sr_scan<false>(x, d_class, T, d_sums);
         hipLaunchKernelGGL(va_site_kernel, gt_, blk, 0, x.st, (const uint8_t *)d_flags, (const u64d *)d_site, (const u64d *)d_class, (const uint32_t *)d_keep,
                            (const uint32_t *)d_coll, T, d_base, d_cref, d_sout);
-        va_scan<false>(x, d_sout, T, d_sums);
+        sr_scan<false>(x, d_sout, T, d_sums);
         hipLaunchKernelGGL(va_number_kernel, gt_, blk, 0, x.st, rec, (const uint32_t *)d_p1, (const uint8_t *)d_flags, (const u64d *)d_site, (const u64d *)d_class,
                            (const uint32_t *)d_keep, (const uint32_t *)d_base, (const uint32_t *)d_cref, (const u64d *)d_sout, T, d_psite, d_palle, d_rsite, d_ralle, d_oa, d_ob);
         x.get(&site_totals, d_sout + (T - 1), 8);
@@ -674,7 +562,7 @@ int va_run_device(const VaTables &t, int device, void *stream, VaOut &o) {
     if (x.err) return x.err;
     x.mark(5);                                                   // ---- genotypes
     if (!x.err && NS) {
-        if (NR) hipLaunchKernelGGL(va_runs_kernel, dim3(va_grid(NR)), blk, 0, x.st, d, runs, NR, (const uint32_t *)d_oa, (const uint32_t *)d_ob, NS, d_gt);
+        if (NR) hipLaunchKernelGGL(va_runs_kernel, dim3(sr_stage_grid(NR)), blk, 0, x.st, d, runs, NR, (const uint32_t *)d_oa, (const uint32_t *)d_ob, NS, d_gt);
         // the order of the records by site is a stable sort of the emission order: (site, path, step)
         va_sort<uint32_t>(x, d_temp, temp_bytes, d_rsite, d_k32o, d_iota, d_k32, T, 32);
         hipLaunchKernelGGL(va_gt_kernel, gt_, blk, 0, x.st, (const uint32_t *)d_k32o, (const uint32_t *)d_k32, (const uint32_t *)rec.path,
@@ -694,14 +582,8 @@ int va_run_device(const VaTables &t, int device, void *stream, VaOut &o) {
     x.mark(7);
     x.sync();                                                    // the synchronisation after the download
     if (x.err) return x.err;
-    float total = 0.f;
-    x.chk(hipEventElapsedTime(&total, x.ev[0], x.ev[7]));
-    o.us = (uint64_t)(total * 1000.0 + 0.5);
-    for (int k = 0; k < 6; k++) {
-        float ms = 0.f;
-        x.chk(hipEventElapsedTime(&ms, x.ev[k], x.ev[k + 1]));
-        o.kernel_us[k] = (uint64_t)(ms * 1000.0 + 0.5);
-    }
+    o.us = x.us(0, 7);
+    for (int k = 0; k < 6; k++) o.kernel_us[k] = x.us(k, k + 1);
     o.anchors = h_count[0]; o.traversals = T;
 
     // host work over the output: the ALT classes of every kept site, numbered by (length, bytes); where that is not the
@@ -813,7 +695,6 @@ extern "C" int sr_variants_vcf(const sr_variants *v, const char *const *names, c
     const uint64_t P = v->paths, NS = v->sites, R = v->ref_path;
     if (NS * (P ? P : 1) > SR_VARIANTS_MAX_CELLS || (P && R >= P)) return sr_fail(SR_ERR_INVALID, "variants: not a result of sr_variants_gfa");
     try {
-        auto u64s = [](uint64_t x) { return std::to_string((unsigned long long)x); };
         uint64_t breaks = 0, skipped = 0;
         for (uint64_t p = 0; p < P; p++) { breaks += v->breaks[p]; skipped += v->skipped[p]; }
         const std::string chrom = P ? names[R] : "";
@@ -855,10 +736,7 @@ extern "C" int sr_variants_vcf(const sr_variants *v, const char *const *names, c
             o += "\n";
             k += n;
         }
-        char *res = (char *)malloc(o.size() + 1);
-        if (!res) return sr_fail(SR_ERR_NOMEM, "not enough memory for the VCF text");
-        memcpy(res, o.c_str(), o.size() + 1);
-        *text = res;
+        return sr_give_text(o, text, "not enough memory for the VCF text");
     } catch (const std::bad_alloc &) {
         return sr_fail(SR_ERR_NOMEM, "not enough memory for the VCF text");
     }
