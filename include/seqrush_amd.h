@@ -876,6 +876,60 @@ void sr_lift_free(sr_lift *l);
  * min_covered, and pairs whose target is the query's own path unless to_name chose it. */
 int sr_lift_bed(const sr_lift *l, const char *const *names, char **text);
 
+/* -------- extracting a subgraph (`--extract-region R --extract-out FILE`) ---------------------------
+ * The graph of a locus alone, with every path's allele through it (`odgi extract`), of any GFA with S / L / P lines and
+ * numeric node ids as the parser of sr_sort_gfa reads it.  pstart and plen as for the lift; the E edges are the distinct L
+ * lines in file order.  A node without a sequence: SR_ERR_INVALID.  Limits of the graph as for the statistics.
+ * Regions: the lines of bed_text (may be NULL), read by the rules of the lift (the label is ignored; unknown names and
+ * ranges outside their path are skipped and counted), and the n_regions strings `NAME` or `NAME:START-END`.  A string that
+ * equals a path name (the first path of that name) is the whole path [0, plen); else it is split at its last `:` and the
+ * rest at its first `-`, both decimal numbers below 2^64.  A string is explicit, so a missing `:`, a bad number, an
+ * unknown path, start >= end and end > plen are SR_ERR_INVALID, naming the string; only the whole of a path of length 0 is
+ * counted in out_of_range instead.  Regions may overlap, nest and repeat in any order; more than 2^24: SR_ERR_UNSUPPORTED.
+ * level[v], all ones = not kept:  (1) seeds, level 0: some step s on v of a region's path has [pstart[s], pstart[s] +
+ * len[v]) meet [start, end).  (2) context, context_steps = c <= 65535 (else SR_ERR_UNSUPPORTED): for r = 1..c a node
+ * without a level gets level r if an L line joins it, by either end in any orientation, to a node of level r - 1; a
+ * self-loop gives nothing, and a GFA without L lines has no context.  (3) merge, merge_distance = D bases and merge_rounds
+ * = R <= 64 (else SR_ERR_UNSUPPORTED): in round k = 1..R, within one path, every maximal run of steps on nodes without a
+ * level that has a kept step directly before and directly after it and whose lengths sum to <= D gets level c + k on all
+ * its nodes; every run of a round is judged against the set at the start of the round, and a round that adds nothing
+ * ends the merge.  merge_rounds_run = the rounds that added a node.
+ * Result: kept nodes in their order, the new id = the rank from 1; every L line between two kept nodes, in file order
+ * with its orientation; per path in file order every maximal run of steps on kept nodes as a subpath named
+ * `NAME:start-end` (start = pstart of its first step, end = pstart + len of its last; always written).  Nothing kept: empty
+ * tables, the text `H\tVN:Z:1.0\n` and no error.
+ * device >= 0: HIP kernels on that device (sr_extract.hip); SR_EXTRACT_DEVICE_HOST: plain loops on the host.  Both give
+ * the same integers and bytes. */
+#define SR_EXTRACT_DEVICE_HOST (-1)
+typedef struct {
+    uint64_t context_steps;     /* default 0 */
+    uint64_t merge_distance;    /* default 100000: a decision of the rule, not a measurement */
+    uint64_t merge_rounds;      /* default 3: likewise */
+    uint64_t reserved;          /* 0 */
+} sr_extract_params;
+void sr_extract_params_default(sr_extract_params *p);
+typedef struct {
+    uint64_t regions, unknown, out_of_range;               /* regions: those that count */
+    uint64_t in_nodes, in_edges, in_steps, in_paths;
+    uint64_t nodes, edges, subpaths, steps, bases;         /* of the result */
+    uint64_t seeds, by_context, by_merge, merge_rounds_run;
+    uint32_t *level;                                       /* [in_nodes], all ones: not kept */
+    uint32_t *node_old;                                    /* [nodes]: the input id (1-based rank of the S line) of result node k + 1 */
+    uint32_t *edge_from, *edge_to;                         /* [edges]: result handles, id << 1 | reverse */
+    uint32_t *sub_path;                                    /* [subpaths]: the input path */
+    uint64_t *sub_start, *sub_end, *sub_off;               /* [subpaths]; sub_off [subpaths + 1] into sub_steps */
+    uint32_t *sub_steps;                                   /* [steps]: result handles */
+    int32_t variant;                                       /* 0 the host loops, 1 the device kernels */
+    uint64_t extract_us, kernel_us[6];                     /* the stage; positions, seeds, context, merge, numbering, emission */
+    void *priv;                                            /* node sequences and path names for the writer */
+} sr_extract;
+int sr_extract_gfa(const char *gfa_in, const char *bed_text, const char *const *regions, uint64_t n_regions,
+                   const sr_extract_params *p, int device, sr_extract **out);
+/* The GFA text of the result, the only place its bytes are formed (those of the GFA writer: H, S, L with 0M, P with *);
+ * *gfa is malloc'ed (sr_free). */
+int sr_extract_text(const sr_extract *x, char **gfa);
+void sr_extract_free(sr_extract *x);
+
 void sr_free(void *p);
 
 const char *sr_last_error(void);

@@ -11,7 +11,7 @@ from .aligner import (AlignmentSequence, AlignmentRecord, Aligner, AllwaveAligne
 from .seqrush import (Args, Sequence, SeqRush, load_sequences, run_seqrush,  # noqa: F401
                       AlignmentScores, SeqSet, Params, Context, build_gfa, graph_stats, graph_stats_report,
                       path_bins, path_bins_tsv, path_bins_rgb, path_bins_png, growth, growth_report, growth_groups,
-                      variants, variants_vcf, lift, lift_bed)
+                      variants, variants_vcf, lift, lift_bed, extract, extract_gfa)
 from ._lib import SeqRushError  # noqa: F401
 
 __all__ = ["AlignmentSequence", "AlignmentRecord", "Aligner", "AllwaveAligner", "AlignerBackend",
@@ -19,4 +19,4 @@ __all__ = ["AlignmentSequence", "AlignmentRecord", "Aligner", "AllwaveAligner", 
            "AlignmentScores", "SeqSet", "Params", "Context", "build_gfa", "SeqRushError", "graph_stats",
            "graph_stats_report", "path_bins", "path_bins_tsv", "path_bins_rgb", "path_bins_png", "growth",
            "growth_report", "growth_groups", "variants", "variants_vcf", "lift",
-           "lift_bed"]
+           "lift_bed", "extract", "extract_gfa"]

@@ -77,6 +77,14 @@ def main(argv=None):
     ap.add_argument("--lift-to", default=None, metavar="NAME", help="the one target path (default: every other path)")
     ap.add_argument("--lift-min-covered", type=int, default=None, metavar="N",
                     help="leave out targets with fewer than N lifted bases (default 1)")
+    ap.add_argument("--extract-region", action="append", default=None, metavar="REGION",
+                    help="cut the subgraph of NAME or NAME:START-END of a path out of the final GFA (`odgi extract`; repeatable); needs --extract-out")
+    ap.add_argument("--extract-bed", default=None, metavar="FILE", help="regions to extract, as BED lines")
+    ap.add_argument("--extract-out", default=None, metavar="FILE", help="the extracted graph, as GFA")
+    ap.add_argument("--extract-context-steps", type=int, default=None, metavar="N", help="grow the regions' nodes by N L lines (default 0)")
+    ap.add_argument("--extract-merge-distance", type=int, default=None, metavar="N",
+                    help="close a gap of at most N bases between two kept steps of a path (default 100000)")
+    ap.add_argument("--extract-merge-rounds", type=int, default=None, metavar="N", help="rounds of gap closing (default 3)")
     ap.add_argument("--extend", default=None, metavar="FILE.gfa",
                     help="add the sequences of -s to this graph: its paths are kept as they are and only the pairs that touch a "
                          "new sequence are aligned")
@@ -140,6 +148,23 @@ def main(argv=None):
         if flag == "--lift-min-covered" and not 0 <= v <= 2 ** 64 - 1:
             print(f"Error: {flag} needs a non-negative integer, got '{v}'", file=sys.stderr)
             return 1
+    asked = ns.extract_region is not None or ns.extract_bed is not None
+    if asked and ns.extract_out is None:
+        print("Error: --extract-region / --extract-bed need --extract-out FILE: the extracted graph has nowhere to go", file=sys.stderr)
+        return 1
+    if ns.extract_out is not None and not asked:
+        print("Error: --extract-out needs --extract-region REGION or --extract-bed FILE: there is nothing to extract", file=sys.stderr)
+        return 1
+    for flag in ("--extract-context-steps", "--extract-merge-distance", "--extract-merge-rounds"):
+        v = getattr(ns, flag.lstrip("-").replace("-", "_"))
+        if v is None:
+            continue
+        if not asked:
+            print(f"Error: {flag} is an option of --extract-region / --extract-bed: give both", file=sys.stderr)
+            return 1
+        if not 0 <= v <= 2 ** 64 - 1:
+            print(f"Error: {flag} needs a non-negative integer, got '{v}'", file=sys.stderr)
+            return 1
     if ns.bin_width is not None and ns.bin_count is not None:
         print("Error: --bin-width and --bin-count exclude each other", file=sys.stderr)
         return 1
@@ -190,7 +215,11 @@ def main(argv=None):
                 growth_permutations=ns.growth_permutations or 1000,
                 growth_seed=9399220 if ns.growth_seed is None else ns.growth_seed, growth_group_by=ns.growth_group_by or "path", vcf=ns.vcf, vcf_ref=ns.vcf_ref,
                 vcf_max_allele_len=10000 if ns.vcf_max_allele_len is None else ns.vcf_max_allele_len, extend=ns.extend,
-                lift=ns.lift, lift_out=ns.lift_out, lift_to=ns.lift_to, lift_min_covered=1 if ns.lift_min_covered is None else ns.lift_min_covered)
+                lift=ns.lift, lift_out=ns.lift_out, lift_to=ns.lift_to, lift_min_covered=1 if ns.lift_min_covered is None else ns.lift_min_covered,
+                extract_regions=tuple(ns.extract_region or ()), extract_bed=ns.extract_bed, extract_out=ns.extract_out,
+                extract_context_steps=ns.extract_context_steps or 0,
+                extract_merge_distance=100000 if ns.extract_merge_distance is None else ns.extract_merge_distance,
+                extract_merge_rounds=3 if ns.extract_merge_rounds is None else ns.extract_merge_rounds)
     try:
         if ns.gpus > 1:
             if int(os.environ.get("WORLD_SIZE", "1")) != ns.gpus:

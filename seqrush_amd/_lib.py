@@ -52,6 +52,7 @@ EXPORTS = [
     "sr_extend_plan_gfa", "sr_extend_plan_free", "sr_extend_plan_seqs", "sr_extend_plan_n_old", "sr_extend_pair_list",
     "sr_ctx_load_extend", "sr_extend_seed_host", "sr_extend_plan_stats", "sr_ctx_extend_stats",
     "sr_lift_params_default", "sr_lift_gfa", "sr_lift_free", "sr_lift_bed",
+    "sr_extract_params_default", "sr_extract_gfa", "sr_extract_free", "sr_extract_text",
 ]
 
 
@@ -212,6 +213,21 @@ class LiftC(C.Structure):
                 ("tstart", C.POINTER(C.c_uint64)), ("tend", C.POINTER(C.c_uint64)), ("covered", C.POINTER(C.c_uint64)),
                 ("rev_bp", C.POINTER(C.c_uint64)), ("variant", C.c_int32), ("to_named", C.c_int32), ("min_covered", C.c_uint64),
                 ("short_pairs", C.c_uint64), ("long_pairs", C.c_uint64), ("lift_us", C.c_uint64), ("kernel_us", C.c_uint64 * 5)]
+
+
+class ExtractParamsC(C.Structure):
+    """sr_extract_params (include/seqrush_amd.h, extracting a subgraph)"""
+    _fields_ = [("context_steps", C.c_uint64), ("merge_distance", C.c_uint64), ("merge_rounds", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class ExtractC(C.Structure):
+    """sr_extract"""
+    _fields_ = [(f, C.c_uint64) for f in ("regions", "unknown", "out_of_range", "in_nodes", "in_edges", "in_steps", "in_paths", "nodes",
+                                          "edges", "subpaths", "steps", "bases", "seeds", "by_context", "by_merge", "merge_rounds_run")] + \
+               [("level", C.POINTER(C.c_uint32)), ("node_old", C.POINTER(C.c_uint32)), ("edge_from", C.POINTER(C.c_uint32)),
+                ("edge_to", C.POINTER(C.c_uint32)), ("sub_path", C.POINTER(C.c_uint32)), ("sub_start", C.POINTER(C.c_uint64)),
+                ("sub_end", C.POINTER(C.c_uint64)), ("sub_off", C.POINTER(C.c_uint64)), ("sub_steps", C.POINTER(C.c_uint32)),
+                ("variant", C.c_int32), ("extract_us", C.c_uint64), ("kernel_us", C.c_uint64 * 6), ("priv", C.c_void_p)]
 
 
 class AlignmentsC(C.Structure):
@@ -409,6 +425,11 @@ def load():
     L.sr_lift_gfa.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(LiftParamsC), i32, C.POINTER(PLF)]
     L.sr_lift_free.argtypes = [PLF]; L.sr_lift_free.restype = None
     L.sr_lift_bed.argtypes = [PLF, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    PEX = C.POINTER(ExtractC)
+    L.sr_extract_params_default.argtypes = [C.POINTER(ExtractParamsC)]; L.sr_extract_params_default.restype = None
+    L.sr_extract_gfa.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u64, C.POINTER(ExtractParamsC), i32, C.POINTER(PEX)]
+    L.sr_extract_free.argtypes = [PEX]; L.sr_extract_free.restype = None
+    L.sr_extract_text.argtypes = [PEX, C.POINTER(vp)]
     L.sr_free.argtypes = [vp]; L.sr_free.restype = None
     L.sr_last_error.restype = C.c_char_p
     L.sr_abi_version.restype = i32

@@ -85,6 +85,8 @@ static void usage() {
                     "       [--growth growth.tsv [--growth-permutations N] [--growth-seed N] [--growth-group-by path|sample|haplotype]]\n"
                     "       [--vcf graph.vcf [--vcf-ref NAME] [--vcf-max-allele-len N]] [--extend graph.gfa]\n"
                     "       [--lift in.bed --lift-out lifted.bed [--lift-to NAME] [--lift-min-covered N]]\n"
+                    "       [--extract-region REGION ... | --extract-bed in.bed] --extract-out sub.gfa [--extract-context-steps N]\n"
+                    "       [--extract-merge-distance N] [--extract-merge-rounds N]\n"
                     "       [--shard R/N --labels-out part.bin]  |  [--labels-in part0.bin --labels-in part1.bin ...]\n");
 }
 
@@ -94,6 +96,10 @@ int main(int argc, char **argv) {
                 lift_in, lift_out, lift_opt, lift_to;
     sr_lift_params lfp;
     sr_lift_params_default(&lfp);
+    std::vector<std::string> extract_regions;
+    std::string extract_bed, extract_out, extract_opt;
+    sr_extract_params exp_;
+    sr_extract_params_default(&exp_);
     sr_variant_params vcp;
     sr_variant_params_default(&vcp);
     sr_growth_params gp;
@@ -215,6 +221,17 @@ int main(int argc, char **argv) {
             if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: %s needs a non-negative integer, got '%s'\n", a.c_str(), v); return 1; }
             vcp.max_allele_len = n;
         }
+        else if (a == "--extract-region") extract_regions.push_back(val("--extract-region"));
+        else if (a == "--extract-bed") extract_bed = val("--extract-bed");
+        else if (a == "--extract-out") extract_out = val("--extract-out");
+        else if (a == "--extract-context-steps" || a == "--extract-merge-distance" || a == "--extract-merge-rounds") {
+            const char *v = val(a.c_str());
+            char *end = nullptr;
+            const unsigned long long n = strtoull(v, &end, 10);
+            extract_opt = a;
+            if (*v < '0' || *v > '9' || *end != 0) { fprintf(stderr, "Error: %s needs a non-negative integer, got '%s'\n", a.c_str(), v); return 1; }
+            (a == "--extract-context-steps" ? exp_.context_steps : a == "--extract-merge-distance" ? exp_.merge_distance : exp_.merge_rounds) = n;
+        }
         else if (a == "--lift") lift_in = val("--lift");
         else if (a == "--lift-out") { lift_out = val("--lift-out"); lift_opt = a; }
         else if (a == "--lift-to") { lift_to = val("--lift-to"); lift_opt = a; }
@@ -291,6 +308,10 @@ int main(int argc, char **argv) {
     if (!vcf_opt.empty() && vcf_out.empty()) { fprintf(stderr, "Error: %s is an option of --vcf: give both\n", vcf_opt.c_str()); return 1; }
     if (!lift_in.empty() && lift_out.empty()) { fprintf(stderr, "Error: --lift needs --lift-out FILE: the lifted intervals have nowhere to go\n"); return 1; }
     if (!lift_opt.empty() && lift_in.empty()) { fprintf(stderr, "Error: %s is an option of --lift: give both\n", lift_opt.c_str()); return 1; }
+    const bool extract_asked = !extract_regions.empty() || !extract_bed.empty();
+    if (extract_asked && extract_out.empty()) { fprintf(stderr, "Error: --extract-region / --extract-bed need --extract-out FILE: the extracted graph has nowhere to go\n"); return 1; }
+    if (!extract_out.empty() && !extract_asked) { fprintf(stderr, "Error: --extract-out needs --extract-region REGION or --extract-bed FILE: there is nothing to extract\n"); return 1; }
+    if (!extract_opt.empty() && !extract_asked) { fprintf(stderr, "Error: %s is an option of --extract-region / --extract-bed: give both\n", extract_opt.c_str()); return 1; }
     if (bin_width && bin_count) { fprintf(stderr, "Error: --bin-width and --bin-count exclude each other\n"); return 1; }
     if (sort && no_sort) { fprintf(stderr, "Error: --sort and --no-sort exclude each other\n"); return 1; }
     if (compact_dev && no_compact) { fprintf(stderr, "Error: --compact-on device and --no-compact exclude each other\n"); return 1; }
@@ -606,6 +627,36 @@ int main(int argc, char **argv) {
                    (unsigned long long)lf->lift_us, device, (unsigned long long)lf->queries, (unsigned long long)lf->targets,
                    (unsigned long long)lf->mapped, (unsigned long long)lf->unknown, (unsigned long long)lf->out_of_range);
         sr_lift_free(lf);
+    }
+    if (extract_asked) {                                     // the subgraph of the regions, cut out of the text just written
+        std::string bed;
+        if (!extract_bed.empty()) {
+            std::ifstream bi(extract_bed, std::ios::binary);
+            if (!bi) { fprintf(stderr, "Error: cannot read %s\n", extract_bed.c_str()); sr_free(gfa); return 1; }
+            bed.assign((std::istreambuf_iterator<char>(bi)), std::istreambuf_iterator<char>());
+        }
+        std::vector<const char *> regs;
+        for (const std::string &r : extract_regions) regs.push_back(r.c_str());
+        sr_extract *ex = nullptr;
+        char *sub = nullptr;
+        if (sr_extract_gfa(gfa, extract_bed.empty() ? nullptr : bed.c_str(), regs.data(), regs.size(), &exp_, device, &ex) || sr_extract_text(ex, &sub)) {
+            fprintf(stderr, "Error: %s\n", sr_last_error());
+            sr_extract_free(ex); sr_free(gfa);
+            return 1;
+        }
+        std::ofstream eo(extract_out, std::ios::binary);
+        eo << sub;
+        sr_free(sub);
+        printf("Extracted graph written to %s\n", extract_out.c_str());
+        if (verbose)
+            printf("Extract stage: %llu us on device %d, %llu regions, %llu unknown, %llu out of range, %llu seeds + %llu by context + %llu by merge in "
+                   "%llu rounds = %llu of %llu nodes, %llu edges, %llu subpaths, %llu steps, %llu bases\n",
+                   (unsigned long long)ex->extract_us, device, (unsigned long long)ex->regions, (unsigned long long)ex->unknown,
+                   (unsigned long long)ex->out_of_range, (unsigned long long)ex->seeds, (unsigned long long)ex->by_context,
+                   (unsigned long long)ex->by_merge, (unsigned long long)ex->merge_rounds_run, (unsigned long long)ex->nodes,
+                   (unsigned long long)ex->in_nodes, (unsigned long long)ex->edges, (unsigned long long)ex->subpaths,
+                   (unsigned long long)ex->steps, (unsigned long long)ex->bases);
+        sr_extract_free(ex);
     }
     sr_free(gfa);
     printf("Graph written to %s\n", output.c_str());

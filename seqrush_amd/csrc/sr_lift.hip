@@ -24,6 +24,7 @@
 #include "sr_sort.h"
 #include "sr_stage_host.h"
 #include "sr_stage_dev.h"
+#include "sr_bed_host.h"
 #include "sr_lift_rule.h"
 
 #define LF_BLOCK 256
@@ -168,58 +169,19 @@ int lf_tables(const SrGraph &g, const std::vector<std::string> &names, const sr_
 }
 
 // ------------------------------------------------------------------ the BED lines
-bool lf_number(const std::string &f, uint64_t *out) {
-    if (f.empty()) return false;
-    uint64_t x = 0;
-    for (char c : f) {
-        if (c < '0' || c > '9') return false;
-        const uint64_t d = (uint64_t)(c - '0');
-        if (x > (~0ULL - d) / 10) return false;
-        x = x * 10 + d;
-    }
-    *out = x;
-    return true;
-}
-
-bool lf_starts(const std::string &s, const char *w) { return s.compare(0, strlen(w), w) == 0; }
-
+// the lines are read by sr_bed_host.h; what a name, a range and a label mean to the lift is here
 int lf_queries(const char *bed, const std::vector<std::string> &names, LfTables &t) {
     std::unordered_map<std::string, uint32_t> by_name;
     for (uint32_t p = 0; p < t.P && p < names.size(); p++) by_name.emplace(names[p], p);      // the first path of a name
-    const char *at = bed;
-    for (uint64_t line_no = 1; *at; line_no++) {
-        const char *nl = strchr(at, '\n');
-        std::string line(at, nl ? (size_t)(nl - at) : strlen(at));
-        at = nl ? nl + 1 : at + line.size();
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        if (line.find_first_not_of(" \t") == std::string::npos) continue;
-        if (line[0] == '#' || lf_starts(line, "track") || lf_starts(line, "browser")) continue;
-        std::vector<std::string> f;
-        if (line.find('\t') != std::string::npos) {
-            for (size_t a = 0; f.size() < 4;) {
-                const size_t b = line.find('\t', a);
-                f.push_back(line.substr(a, b == std::string::npos ? b : b - a));
-                if (b == std::string::npos) break;
-                a = b + 1;
-            }
-        } else {
-            for (size_t a = line.find_first_not_of(' '); a != std::string::npos && f.size() < 4;) {
-                const size_t b = line.find(' ', a);
-                f.push_back(line.substr(a, b == std::string::npos ? b : b - a));
-                a = b == std::string::npos ? b : line.find_first_not_of(' ', b);
-            }
-        }
-        const std::string where = "lift: BED line " + std::to_string(line_no) + ": ";
-        if (f.size() < 3) return sr_fail(SR_ERR_INVALID, where + "fewer than three fields");
-        uint64_t start = 0, end = 0;
-        if (!lf_number(f[1], &start)) return sr_fail(SR_ERR_INVALID, where + "start '" + f[1] + "' is not a number");
-        if (!lf_number(f[2], &end)) return sr_fail(SR_ERR_INVALID, where + "end '" + f[2] + "' is not a number");
+    const int r = sr_bed_lines(bed, "lift", [&](const std::vector<std::string> &f, uint64_t start, uint64_t end) {
         const auto it = by_name.find(f[0]);
-        if (it == by_name.end()) { t.unknown++; continue; }
-        if (start >= end || end > t.plen[it->second]) { t.out_of_range++; continue; }
+        if (it == by_name.end()) { t.unknown++; return SR_OK; }
+        if (start >= end || end > t.plen[it->second]) { t.out_of_range++; return SR_OK; }
         t.q_path.push_back(it->second); t.q_start.push_back(start); t.q_end.push_back(end);
         t.label.push_back(f.size() > 3 && !f[3].empty() ? f[3] : f[0] + ":" + f[1] + "-" + f[2]);
-    }
+        return SR_OK;
+    });
+    if (r) return r;
     if ((uint64_t)t.q_path.size() * t.target_path.size() > SR_LIFT_MAX_PAIRS)
         return sr_fail(SR_ERR_UNSUPPORTED, "lift: " + std::to_string(t.q_path.size()) + " queries x " + std::to_string(t.target_path.size()) +
                                                " targets; the tables support at most 2^26 pairs");

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ParamsC, SeqSetC, AlignmentsC, SortParamsC, IterStatsC, InvParamsC, InvStatsC, InvJobC, InvSiteC, GraphStatsC,
-                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, ExtendStatsC, LiftParamsC, LiftC, check,
+                   LayoutParamsC, BinParamsC, PathBinsC, VizParamsC, GrowthParamsC, GrowthC, VariantParamsC, VariantsC, ExtendStatsC, LiftParamsC, LiftC, ExtractParamsC, ExtractC, check,
                    SeqRushError)
 
 SR_MEM_HIGH, SR_MEM_ULTRALOW = 0, 3
@@ -78,6 +78,12 @@ class Args:
     lift_out: Optional[str] = None          # added: --lift-out FILE: where the lifted intervals go (required with --lift)
     lift_to: Optional[str] = None           # added: --lift-to NAME: the one target path (default: every path)
     lift_min_covered: int = 1               # added: --lift-min-covered N
+    extract_regions: tuple = ()             # added: --extract-region REGION (repeatable): NAME or NAME:START-END of paths of the final GFA
+    extract_bed: Optional[str] = None       # added: --extract-bed FILE: regions as BED lines
+    extract_out: Optional[str] = None       # added: --extract-out FILE: where the extracted GFA goes (required with a region or a BED)
+    extract_context_steps: int = 0          # added: --extract-context-steps N
+    extract_merge_distance: int = 100000    # added: --extract-merge-distance N
+    extract_merge_rounds: int = 3           # added: --extract-merge-rounds N
     extend: Optional[str] = None            # added: --extend FILE.gfa: add the sequences of -s to this graph
 
 
@@ -1177,6 +1183,124 @@ def write_lift(text: str, args: "Args"):
         print(line)
 
 
+SR_EXTRACT_DEVICE_HOST = -1
+EXTRACT_KERNELS = ("positions", "seeds", "context", "merge", "numbering", "emission")
+EXTRACT_COUNTERS = ("regions", "unknown", "out_of_range", "in_nodes", "in_edges", "in_steps", "in_paths", "nodes", "edges", "subpaths", "steps",
+                    "bases", "seeds", "by_context", "by_merge", "merge_rounds_run")
+
+
+class Extract:
+    """an owned sr_extract: the subgraph of regions of paths of a GFA text"""
+
+    def __init__(self, text: str, regions=(), bed: Optional[str] = None, device: int = 0, context_steps: int = 0, merge_distance: int = 100000,
+                 merge_rounds: int = 3):
+        for k, v in (("context_steps", context_steps), ("merge_distance", merge_distance), ("merge_rounds", merge_rounds)):
+            if not 0 <= int(v) < 2 ** 64:
+                raise SeqRushError(-1, f"{k} must be in 0 .. 2^64 - 1")
+        if isinstance(regions, str):
+            regions = (regions,)
+        self.L = _lib.load()
+        self.p = C.POINTER(ExtractC)()
+        self.names = _path_names(text)
+        regs = [str(r).encode() for r in regions]
+        arr = (C.c_char_p * max(1, len(regs)))(*regs)
+        prm = ExtractParamsC(int(context_steps), int(merge_distance), int(merge_rounds), 0)
+        check(self.L.sr_extract_gfa(text.encode(), None if bed is None else bed.encode(), C.cast(arr, C.POINTER(C.c_char_p)), len(regs),
+                                    C.byref(prm), int(device), C.byref(self.p)))
+
+    def close(self):
+        if self.p:
+            self.L.sr_extract_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def as_dict(self) -> dict:
+        s = self.p.contents
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].astype(dt, copy=True)
+        d = {k: int(getattr(s, k)) for k in EXTRACT_COUNTERS + ("variant", "extract_us")}
+        d["level"] = arr(s.level, d["in_nodes"], np.uint32)
+        d["node_old"] = arr(s.node_old, d["nodes"], np.uint32)
+        d["edge_from"], d["edge_to"] = arr(s.edge_from, d["edges"], np.uint32), arr(s.edge_to, d["edges"], np.uint32)
+        d["sub_path"] = arr(s.sub_path, d["subpaths"], np.uint32)
+        d["sub_start"], d["sub_end"] = arr(s.sub_start, d["subpaths"], np.uint64), arr(s.sub_end, d["subpaths"], np.uint64)
+        d["sub_off"] = arr(s.sub_off, d["subpaths"] + 1, np.uint64)
+        d["sub_steps"] = arr(s.sub_steps, d["steps"], np.uint32)
+        d["sub_names"] = [f"{self.names[int(p)]}:{int(a)}-{int(b)}" for p, a, b in zip(d["sub_path"], d["sub_start"], d["sub_end"])]
+        d["kernel_us"] = dict(zip(EXTRACT_KERNELS, (int(v) for v in s.kernel_us)))
+        return d
+
+    def gfa(self) -> str:
+        out = C.c_void_p()
+        check(self.L.sr_extract_text(self.p, C.byref(out)))
+        return _take_text(out)
+
+
+def extract(text: str, regions=(), bed: Optional[str] = None, device: int = 0, context_steps: int = 0, merge_distance: int = 100000,
+            merge_rounds: int = 3) -> dict:
+    """the subgraph of any GFA with S / L / P lines and numeric node ids that the regions (`NAME` or `NAME:START-END`
+    strings, and / or the lines of the BED text `bed`) of its paths touch, grown by context_steps L lines and closed over
+    gaps of at most merge_distance bases in merge_rounds rounds.  device >= 0: HIP kernels on that
+    device, -1: the host twin (the same integers and bytes).  -> dict: the counters of sr_extract; level (uint32
+    [in_nodes], all ones = not kept); node_old; edge_from / edge_to; sub_path / sub_start / sub_end / sub_off / sub_steps
+    and sub_names; extract_us, kernel_us"""
+    with Extract(text, regions, bed, device, context_steps, merge_distance, merge_rounds) as v:
+        return v.as_dict()
+
+
+def extract_gfa(text: str, regions=(), bed: Optional[str] = None, device: int = 0, context_steps: int = 0, merge_distance: int = 100000,
+                merge_rounds: int = 3) -> str:
+    """the subgraph of extract() as GFA text, formatted by the library"""
+    with Extract(text, regions, bed, device, context_steps, merge_distance, merge_rounds) as v:
+        return v.gfa()
+
+
+def extract_line(s, device) -> str:
+    """the one line of -v, from an ExtractC"""
+    return (f"Extract stage: {int(s.extract_us)} us on device {device}, {int(s.regions)} regions, {int(s.unknown)} unknown, "
+            f"{int(s.out_of_range)} out of range, {int(s.seeds)} seeds + {int(s.by_context)} by context + {int(s.by_merge)} by merge in "
+            f"{int(s.merge_rounds_run)} rounds = {int(s.nodes)} of {int(s.in_nodes)} nodes, {int(s.edges)} edges, {int(s.subpaths)} subpaths, "
+            f"{int(s.steps)} steps, {int(s.bases)} bases")
+
+
+def check_extract(args: "Args"):
+    """a region or a BED needs --extract-out and the other way round; before any device work"""
+    asked = bool(args.extract_regions) or bool(args.extract_bed)
+    if asked and not args.extract_out:
+        raise SeqRushError(-1, "--extract-region / --extract-bed need --extract-out FILE: the extracted graph has nowhere to go")
+    if args.extract_out and not asked:
+        raise SeqRushError(-1, "--extract-out needs --extract-region REGION or --extract-bed FILE: there is nothing to extract")
+    for flag, on in (("--extract-context-steps", args.extract_context_steps != 0), ("--extract-merge-distance", args.extract_merge_distance != 100000),
+                     ("--extract-merge-rounds", args.extract_merge_rounds != 3)):
+        if on and not asked:
+            raise SeqRushError(-1, f"{flag} is an option of --extract-region / --extract-bed: give both")
+
+
+def write_extract(text: str, args: "Args"):
+    """the --extract-* stage of both Python front ends on the final GFA text"""
+    bed = None
+    if args.extract_bed:
+        try:
+            with open(args.extract_bed) as fh:
+                bed = fh.read()
+        except OSError as e:
+            raise SeqRushError(-8, f"cannot read {args.extract_bed}: {e.strerror}")
+    with Extract(text, tuple(args.extract_regions), bed, args.device, args.extract_context_steps, args.extract_merge_distance,
+                 args.extract_merge_rounds) as v:
+        with open(args.extract_out, "w") as fh:
+            fh.write(v.gfa())
+        line = extract_line(v.p.contents, args.device)
+    print(f"Extracted graph written to {args.extract_out}")
+    if args.verbose:
+        print(line)
+
+
 LAYOUT_STATS =("sgd_ms", "terms_per_iter", "iterations", "subrounds_per_iter", "nodes", "steps", "stage_ms")
 
 
@@ -1616,11 +1740,14 @@ class SeqRush:
             write_vcf(text, args)
         if args.lift:
             write_lift(text, args)
+        if args.extract_out:
+            write_extract(text, args)
 
 
 def run_seqrush(args: Args):
     """src/seqrush.rs:1839-1853"""
     check_lift(args)
+    check_extract(args)
     sequences = load_sequences(args.sequences)
     print(f"Loaded {len(sequences)} sequences")
     plan = None
