@@ -163,7 +163,10 @@ int sr_write_paf(const sr_alignments *a, const sr_seqset *seqs, const char *path
 typedef struct sr_ctx sr_ctx;
 int sr_ctx_create(int device, sr_ctx **out);
 void sr_ctx_destroy(sr_ctx *c);
-/* optional: launch on an externally owned hipStream_t */
+/* optional: launch on an externally owned hipStream_t (NULL: the null stream).  The context's own stream is synchronized
+ * and destroyed here; a caller's stream that the context gives up is NOT waited for: change streams only after
+ * sr_ctx_sync(), or the work still queued on the old stream and the first call on the new one are unordered.  The stream
+ * may be blocking or non-blocking: every call that copies to or from the host waits for the context's stream itself. */
 int sr_ctx_set_stream(sr_ctx *c, void *hip_stream);
 /* pack (2 / 4 / 8 bits per symbol by alphabet; forward + reverse complement) and upload; pair list (sparsified:
  * k-mer sketches on the device), cost-balanced shard, SeqRush::new UF init */

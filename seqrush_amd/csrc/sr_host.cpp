@@ -368,6 +368,27 @@ static void free_dev(sr_ctx *c) {
     c->inv_ev_used = 0;
     if (c->inv_al) { sr_alignments_free(c->inv_al); c->inv_al = nullptr; }
     c->ext_loaded = false; c->ext = SrExtendSeedArgs{}; c->ext_stats = sr_extend_stats{};
+    // the host-side description of the load goes with its buffers: a load that fails half-way, or one that writes only a part
+    // of it (sr_ctx_load_paf has no kernel plan and no workspace report), must not show what the load before it left
+    c->n = 0; c->len.clear(); c->goff.clear(); c->total_len = c->uf_size = 0;
+    c->pair_q.clear(); c->pair_t.clear(); c->cigar_base.clear(); c->batch_first.clear();
+    c->total_pairs_all_ranks = 0; c->dp_cells = 0;
+    c->aa = SrAlignArgs{}; c->ua = SrUniteArgs{};
+    c->fuse_unite = false; c->lds_bytes = c->olds_bytes = 0; c->nwg = 0;
+    c->tail_wg_per_cu = 1; c->tail_rounds = c->prio_rounds = SR_TAIL_ROUNDS_DEFAULT; c->tail_cus = 0;
+    c->workspace_report.clear();
+}
+
+// A load that failed after it had freed the load before it: nothing of either stays -- not the buffers it had allocated so far,
+// not the pair list, sizes or report it had written so far (a failure before that point leaves the context as it was)
+static int unload_if_failed(sr_ctx *c, int r) {
+    if (r && c && !c->loaded) {
+        const std::string keep = g_err;
+        (void)hipStreamSynchronize(c->stream);
+        free_dev(c);
+        g_err = keep;
+    }
+    return r;
 }
 
 // event pair `idx` of kind `kind` (created on first use)
@@ -408,6 +429,9 @@ extern "C" void sr_ctx_destroy(sr_ctx *c) {
     delete c;
 }
 
+// The context's own stream is drained and destroyed; a caller's stream it gives up is not waited for (the caller owns it and
+// may have work of its own there): the rule is sr_ctx_sync() before sr_ctx_set_stream() on a context with work in flight
+// (include/seqrush_amd.h; tests/test_resident_gpu.py changes streams on a loaded context that way)
 extern "C" int sr_ctx_set_stream(sr_ctx *c, void *hip_stream) {
     if (!c) return fail(SR_ERR_INVALID, "null ctx");
     if (c->own_stream && c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
@@ -1435,12 +1459,12 @@ static int load_impl(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const
 #undef DEV_UPLOAD
 
 extern "C" int sr_ctx_load(sr_ctx *c, const sr_seqset *seqs, const sr_params *p) {
-    return load_impl(c, seqs, p, nullptr, nullptr, 0, false);
+    return unload_if_failed(c, load_impl(c, seqs, p, nullptr, nullptr, 0, false));
 }
 extern "C" int sr_ctx_load_pairs(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const uint32_t *query_idx,
                                  const uint32_t *target_idx, uint64_t count) {
     if (count && (!query_idx || !target_idx)) return fail(SR_ERR_INVALID, "null pair list");
-    return load_impl(c, seqs, p, query_idx, target_idx, count, true);
+    return unload_if_failed(c, load_impl(c, seqs, p, query_idx, target_idx, count, true));
 }
 
 extern "C" int sr_ctx_pairs(const sr_ctx *c, uint32_t **q_out, uint32_t **t_out, uint64_t *count) {
@@ -1486,13 +1510,15 @@ extern "C" int sr_ctx_reset_uf(sr_ctx *c) {
 }
 
 // sr_ctx_load of the plan's merged set with the pair filter, then the seed tables and the seed (include/seqrush_amd.h)
-extern "C" int sr_ctx_load_extend(sr_ctx *c, const sr_extend_plan *plan, const sr_params *p) {
+static int load_extend(sr_ctx *c, const sr_extend_plan *plan, const sr_params *p) {
     if (!c || !plan || !p) return fail(SR_ERR_INVALID, "null argument");
     if (plan->n_new == 0) return fail(SR_ERR_INVALID, "extend: no new sequences: there is nothing to align");
     int r = load_impl(c, &plan->merged, p, nullptr, nullptr, 0, false, false, false, plan->n_old);
     if (r) return r;
-    if (plan->old_bases > c->total_len || plan->S == 0 || plan->sinc[plan->S - 1] != plan->old_bases)
+    if (plan->old_bases > c->total_len || plan->S == 0 || plan->sinc[plan->S - 1] != plan->old_bases) {
+        c->loaded = false;
         return fail(SR_ERR_INVALID, "extend: the plan's tables do not match its merged set");
+    }
     const uint64_t before = c->ext_stats.pairs_before, after = c->ext_stats.pairs_after;
     sr_extend_plan_stats(plan, &c->ext_stats);
     c->ext_stats.pairs_before = before; c->ext_stats.pairs_after = after;
@@ -1512,6 +1538,9 @@ extern "C" int sr_ctx_load_extend(sr_ctx *c, const sr_extend_plan *plan, const s
     HIPCHK(hipStreamSynchronize(c->stream));                 // (the plan's vectors may go away after this)
     c->loaded = true; c->ext_loaded = true;
     return enqueue_extend_seed(c);
+}
+extern "C" int sr_ctx_load_extend(sr_ctx *c, const sr_extend_plan *plan, const sr_params *p) {
+    return unload_if_failed(c, load_extend(c, plan, p));
 }
 
 extern "C" int sr_ctx_extend_stats(sr_ctx *c, sr_extend_stats *out) {
@@ -2053,7 +2082,7 @@ extern "C" int sr_ctx_load_iterative(sr_ctx *c, const sr_seqset *seqs, const sr_
     if (defaulted) {                                   // :957-967: any other strategy -> tree:3,3,0.1,16
         q.sparsify_kind = SR_SPARSE_TREE; q.tree_k_nearest = 3; q.tree_k_farthest = 3; q.tree_rand_frac = 0.1; q.tree_kmer = 16;
     }
-    int r = load_impl(c, seqs, &q, nullptr, nullptr, 0, true, true);
+    int r = unload_if_failed(c, load_impl(c, seqs, &q, nullptr, nullptr, 0, true, true));
     if (r) return r;
     void *d;
     if ((r = dev_alloc(c, &d, sizeof(SrIterState)))) return r;
@@ -2750,7 +2779,7 @@ static inline uint8_t paf_query_base(const uint8_t *q, uint64_t qlen, bool rc, u
     return rc ? comp_base(q[qlen - 1 - pos]) : q[pos];
 }
 
-extern "C" int sr_ctx_load_paf(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const char *paf_path) {
+static int load_paf(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const char *paf_path) {
     if (!c || !seqs || !p || !paf_path) return fail(SR_ERR_INVALID, "null argument");
     if (seqs->n == 0) return fail(SR_ERR_INVALID, "no sequences");
     if (!seqs->names) return fail(SR_ERR_INVALID, "PAF input needs sequence names");
@@ -2911,6 +2940,9 @@ extern "C" int sr_ctx_load_paf(sr_ctx *c, const sr_seqset *seqs, const sr_params
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loaded = true; c->from_paf = true;
     return SR_OK;
+}
+extern "C" int sr_ctx_load_paf(sr_ctx *c, const sr_seqset *seqs, const sr_params *p, const char *paf_path) {
+    return unload_if_failed(c, load_paf(c, seqs, p, paf_path));
 }
 
 extern "C" int sr_unite_paf(const sr_seqset *seqs, const sr_params *p, const char *paf_path, uint64_t *parent_out) {
