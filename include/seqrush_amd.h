@@ -73,7 +73,7 @@ typedef struct {
     int32_t exclude_self;       /* reference passes false (:731) */
     int32_t memory_mode;        /* SR_MEM_ULTRALOW = reference (wfa.rs:57) */
     int32_t sparsify_kind;      /* SR_SPARSE_* (grammar seqrush.rs:356-431).  allwave's selection rules are absent from the
-                                   reference tree: the definitions (sr_host.cpp "pair list", sr_sketch.hip) are this
+                                   reference tree: the definitions (sr_pairs.cpp "pair list", sr_sketch.hip) are this
                                    project's own and unpinned, random:F included */
     double sparsify_factor;     /* random:F / connectivity:P */
     uint64_t sparsify_seed;
@@ -82,7 +82,7 @@ typedef struct {
     /* pair shard for multi-GPU: this call handles shard `shard_rank` of `shard_count` of the (sparsified) row-major
      * ordered pair list.  The shards are cost-balanced: pairs sorted by |q|*|t| (self pairs: |q|), longest first, each
      * dealt to the rank with the least work so far (longest-processing-time-first; every rank computes the same
-     * assignment; equal lengths degenerate to index mod shard_count -- sr_host.cpp shard_pairs) */
+     * assignment; equal lengths degenerate to index mod shard_count -- sr_pairs.cpp shard_pairs) */
     uint32_t shard_rank, shard_count;
     /* tree:neighbor[,stranger[,random[,k-mer]]] (seqrush.rs:378-418; extract_tree_pairs_separated call :941-947) */
     uint32_t tree_k_nearest, tree_k_farthest;
@@ -288,7 +288,7 @@ int sr_tail_shape(int impl, int block_levels, int wave_build, int off16, int rin
 
 /* -------- iterative mode (`seqrush --iterative`, align_and_unite_iterative src/seqrush.rs:867-1132) ---------------
  * Tree entries ({i<j} picked by the k-NN selection of -x tree:, row-major) are aligned and united first; then the random
- * entries (the other pairs of the tree: list, in a seeded shuffle, sr_host.cpp "pair list") in chunks of 10, with a
+ * entries (the other pairs of the tree: list, in a seeded shuffle, sr_pairs.cpp "pair list") in chunks of 10, with a
  * component count after every full chunk; the run stops once 10 checks in a row saw no change (:1034-1122).  Each entry
  * aligns (i,i) (i,j) (j,i) (j,j).  A -x other than tree: is replaced by tree:3,3,0.1,16 (tree_defaulted).  One context,
  * no shards.  The union-find holds exactly the processed alignments; the stop point does not depend on the schedule. */

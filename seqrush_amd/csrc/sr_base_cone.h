@@ -1,4 +1,4 @@
-// sr_base_cone.h -- the backward cone of a base case (blocked kernel, blk_setup; host twin sr_base_cone_reach in sr_host.cpp,
+// sr_base_cone.h -- the backward cone of a base case (blocked kernel, blk_setup; host twin sr_base_cone_reach in sr_twins.cpp,
 // which tests/test_base_cone_host.py checks against a brute-force model of the recurrences), shared like sr_iter_rule.h.
 //
 // A base case ends in the cell (k_end = tlen - plen, offset tlen) of its end component, at a level below the lj levels it

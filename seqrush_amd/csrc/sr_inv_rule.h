@@ -1,5 +1,5 @@
 // sr_inv_rule.h -- the rule of --patch-inversions (the reference's inversion-aware runner, src/inversion_aware_seqrush.rs:118-255
-// over src/cigar_analysis.rs:23-147), shared by the device scan (sr_inv.hip) and the host twins (sr_host.cpp), like
+// over src/cigar_analysis.rs:23-147), shared by the device scan (sr_inv.hip) and the host twins (sr_inv_host.cpp), like
 // sr_iter_rule.h for the iterative mode.
 //   site       a match op ending at (qa, ta) opens a look-ahead over the ops after it, up to the next match op or the end of
 //              the CIGAR: qgap = query-only + mismatch columns, tgap = target-only + mismatch columns (cigar_analysis.rs:54-78).

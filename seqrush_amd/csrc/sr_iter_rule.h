@@ -1,5 +1,5 @@
 // sr_iter_rule.h -- the stop rule of the iterative mode (--iterative, align_and_unite_iterative src/seqrush.rs:1034-1122),
-// shared by the device decide kernel (sr_iter.hip) and the host twin sr_iterative_stop_host (sr_host.cpp), like
+// shared by the device decide kernel (sr_iter.hip) and the host twin sr_iterative_stop_host (sr_twins.cpp), like
 // sr_sgd_term.h for the layout.  One check runs after every CHECK_INTERVAL random entries; the count is compared with
 // the previous check's (the first check with the count after the tree entries), `stable` grows on equality and resets on
 // a change, and the run stops at the check where it reaches STABILITY_THRESHOLD.

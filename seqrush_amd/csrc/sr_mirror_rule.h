@@ -1,5 +1,5 @@
 // sr_mirror_rule.h -- when the alignment of (t, q) is the transpose of the alignment of (q, t) (blocked kernel: mirrored
-// emission, sr_align_blk.inc; host twins sr_mirror_* in sr_host.cpp, which tests/test_mirror_host.py checks by enumeration),
+// emission, sr_align_blk.inc; host twins sr_mirror_* in sr_twins.cpp, which tests/test_mirror_host.py checks by enumeration),
 // shared like sr_base_cone.h.  DESIGN.md section 4.3.
 //
 // Transposing a pair swaps pattern and text: diagonal k becomes -k, I becomes D, offsets (furthest-reaching points) and

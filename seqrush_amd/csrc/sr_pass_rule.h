@@ -1,5 +1,5 @@
 // sr_pass_rule.h -- the tables of one pass of the blocked kernel (blk_setup of sr_blk_pass.inc; host twin sr_pass_tables_host in
-// sr_host.cpp, which tests/test_pass_rule_host.py checks against a serial restatement), shared like sr_base_cone.h.
+// sr_twins.cpp, which tests/test_pass_rule_host.py checks against a serial restatement), shared like sr_base_cone.h.
 //
 // A pass computes the B levels s0 .. s0+B-1 of every active aligner.  Its tables have a per-level part -- the range
 // [klo, khi] of diagonals a level can reach, for a base case intersected with the backward cone of its end, and the cells

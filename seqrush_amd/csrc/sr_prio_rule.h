@@ -1,5 +1,5 @@
 // sr_prio_rule.h -- issue priority of the tile code of co-resident workgroups of the blocked kernel (sr_align_blk.inc;
-// host twin sr_tile_prio_role_host in sr_host.cpp, which tests/test_prio_rule_host.py checks), shared like sr_mirror_rule.h.
+// host twin sr_tile_prio_role_host in sr_twins.cpp, which tests/test_prio_rule_host.py checks), shared like sr_mirror_rule.h.
 // DESIGN.md section 4.1.
 //
 // A SIMD holds one wave of each workgroup resident on its CU, and VALU issue is arbitrated by priority, then by age.  The

@@ -54,5 +54,5 @@ int sr_graph_growth_run(const SrGraph &g, const uint32_t *group_of, uint32_t n_g
 // stream; names = the path names the parser returned (the reference is chosen by name); *out as sr_variants_gfa returns it
 int sr_graph_variants_run(const SrGraph &g, const std::vector<std::string> &names, const sr_variant_params &prm, int device, void *stream,
                           sr_variants **out);
-int sr_fail(int code, const std::string &msg);     // sr_host.cpp: sets sr_last_error()
+int sr_fail(int code, const std::string &msg);     // sr_params.cpp: sets sr_last_error()
 void sr_sort_note_write_ms(double ms);              // slot [3] of sr_sort_stats(), also added to the stage's wall time [9]

@@ -19,7 +19,7 @@
 #define SR_VAR_SKIPPED 2
 #define SR_VAR_TRAVERSAL 3
 
-// the project's complement (comp_base of sr_host.cpp): lower case maps to upper case, every other byte to itself
+// the project's complement (comp_base of sr_ctx.h): lower case maps to upper case, every other byte to itself
 SR_HD static inline uint8_t sr_var_comp(uint8_t b) {
     switch (b) {
     case 'A': case 'a': return 'T'; case 'T': case 't': return 'A';

@@ -178,7 +178,7 @@ NONE, SECONDARY = 0xffffffff, 0x80000000
 
 
 def mirror_rule(pairs, batch_first, workgroups):
-    """the rule in the comment above mirror_map (sr_host.cpp), restated -> (entries, primaries per batch)"""
+    """the rule in the comment above mirror_map (sr_pairs.cpp), restated -> (entries, primaries per batch)"""
     out, per_batch = [NONE] * len(pairs), []
     for f, l in zip(batch_first, batch_first[1:]):
         first, n = {}, 0
@@ -206,7 +206,7 @@ def arena_batches(lens, pairs, arena_ops):
 
 
 def shard(lens, pairs, rank, count):
-    """shard_pairs (sr_host.cpp) restated: pairs by cost (|q| * |t|, self pairs |q|), longest first and stable, each to the
+    """shard_pairs (sr_pairs.cpp) restated: pairs by cost (|q| * |t|, self pairs |q|), longest first and stable, each to the
     least loaded rank (lowest rank on ties); a rank keeps its pairs in list order"""
     cost = [lens[q] if q == t else lens[q] * lens[t] for q, t in pairs]
     load, mine = [0] * count, []

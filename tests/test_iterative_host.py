@@ -92,7 +92,7 @@ def unit53(h):
 
 
 def ref_lists(n, sel, seed, rf):
-    """the documented split (sr_host.cpp "pair list"): tree entries row-major, random entries by (hash, i, j)"""
+    """the documented split (sr_pairs.cpp "pair list"): tree entries row-major, random entries by (hash, i, j)"""
     tree, rnd = [], []
     for i in range(n):
         for j in range(i + 1, n):

@@ -4,7 +4,7 @@ SR_NO_MIRROR=1 and what the CPU oracle gives: strand, score, raw CIGAR bytes of 
 describe the alignment as the oracle counts it ([0]..[5]) must not move, the rows loaded and stored must fall.  Inputs and the
 oracle's answers (once per process): tests/mirror_inputs.py.
 
-A batch with no more pairs than the launch has workgroups gets no partners (sr_host.cpp mirror_map: every pair has a
+A batch with no more pairs than the launch has workgroups gets no partners (sr_pairs.cpp mirror_map: every pair has a
 workgroup of its own there and mirroring could only lengthen the launch), and these inputs have 25 to 64 pairs on a GPU
 with a thousand workgroup slots.  So every case that is about mirroring runs with fewer workgroups than pairs (SR_NWG=8
 unless the case sets its own): that is what "mirroring on" means for an input of this size.

@@ -1,7 +1,7 @@
 """CPU side of the mode-by-mirroring tests (tests/mode_tie_inputs.py; device side: test_modes_mirrored_gpu.py): the conditions
 on the three inputs as exact counts (PINNED: a later change of a generator cannot quietly make the device tests vacuous), and
 the mirror map of every mode's actual pair list in its actual batch layout -- sr_mirror_map against a restatement of the rule
-in the comment above mirror_map (sr_host.cpp) -- with the number of partners per list at 2 and 8 workgroups (PARTNERS), which
+in the comment above mirror_map (sr_pairs.cpp) -- with the number of partners per list at 2 and 8 workgroups (PARTNERS), which
 the device file takes its expectations from.  No GPU."""
 import pytest
 
